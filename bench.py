@@ -14,7 +14,7 @@ the same K affine points.  value = N * 2^20 * steps / wall time
 flight instead (the round-1 way, for comparison); `config.single_msm_latency_ms`
 gives the strictly sequential figure.
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 Prints ONE JSON line on rank 0.
 """
@@ -26,9 +26,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# hardware queues the HIP runtime spreads this process's streams over (default 4): the package sets the same default on
-# import; here too because the runtime reads it at its first call, which torch may make first (see snark-verifier_amd/__init__.py)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 AGG_JOBS_IN_FLIGHT = 16  # aggregation jobs kept in flight (one context each) in the `_pipelined` lines of the second metric
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
@@ -69,6 +66,28 @@ def dist_ms(samples):
     med = xs[n // 2] if n % 2 else 0.5 * (xs[n // 2 - 1] + xs[n // 2])
     return {"estimator": "median", "calls": n, "median_ms": med, "min_ms": xs[0], "mean_ms": sum(xs) / n,
             "p95_ms": xs[min(n - 1, -(-95 * n // 100) - 1)], "max_ms": xs[-1]}
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, last_step, batch=None):
+    """--dump-outputs: what the timed path handed its caller, as float32 .npy files (every value is a byte, so exact).
+    msm_result.npy: the last timed step's affine point, shape (64,) -- x then y, 32-byte little-endian canonical each;
+    msm_batch_results.npy (batch mode): the K points of the timed batch call, shape (K, 64), or a fixed seeded sample of
+    its rows (sorted, seed 0) should K x 256 B pass the size limit."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"msm_result": np.frombuffer(last_step, dtype=np.uint8).astype(np.float32)}
+    if batch is not None:
+        rows = np.frombuffer(batch, dtype=np.uint8).reshape(-1, 64).astype(np.float32)
+        keep = (DUMP_LIMIT_BYTES - arrays["msm_result"].nbytes) // rows[0].nbytes
+        if len(rows) > keep:
+            rows = rows[np.sort(np.random.default_rng(0).choice(len(rows), size=keep, replace=False))]
+        arrays["msm_batch_results"] = rows
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(ctx, d_scalars, d_points, sample_log2):
@@ -191,7 +210,7 @@ def secondary_metrics(sv, torch, ctxs, cpu=True):
             same = all(bytes(a.cpu().numpy()) == bytes(acc[0].cpu().numpy()) for a in acc[1:])
             out["aggregate_%d_proofs_pipelined" % nproofs] = {
                 "ms_per_job": ms, "proofs_per_s": nproofs / ms * 1e3, "msm_terms": n1 + n2,
-                "includes_decide": True, "jobs_in_flight": len(ctxs), "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+                "includes_decide": True, "jobs_in_flight": len(ctxs),
                 "results_identical": same, "timing": "best of 3 timed regions of 4 x 16 jobs", "best_of": 3, "estimator": "min", "calls": 3,
                 "NOT_the_named_config": "16 jobs in flight on 16 contexts / hardware queues: a throughput figure",
                 "roofline": aggregate_roofline(nproofs, ms)}
@@ -725,14 +744,25 @@ def cpu_baseline_aggregate(ds, dp, offs, n1, nproofs, n2):
 # The driver parses the LAST stdout line and keeps only a few KB of tail (round 5: a 26.5 KB line was cut mid-way and the
 # round went unmeasured).  So the last line carries the contract keys, the roofline, the CPU baseline and the named
 # configs -- under 4 KB, asserted -- and everything else (stage tables, secondary legs, notes, launch attempts) goes to
-# `details` (gpurun_out/bench_details.json unless SNARKV_BENCH_DETAILS says otherwise), which the line names.
+# `details` (SNARKV_BENCH_DETAILS, else the default path in _write_details; the temporary directory when that cannot be
+# written, e.g. a read-only checkout), which the line names.
 LINE_LIMIT = 4096
 
 
-def _details_path():
+def _write_details(line):
+    """the full record to the details file; returns its path.  A location that cannot be written must not cost the line."""
+    import tempfile
+
     p = os.environ.get("SNARKV_BENCH_DETAILS") or os.path.join(ROOT, "gpurun_out", "bench_details.json")
-    os.makedirs(os.path.dirname(os.path.abspath(p)), exist_ok=True)
-    return p
+    for path in (p, os.path.join(tempfile.gettempdir(), "snarkv_bench_details_%d.json" % os.getpid())):
+        try:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                json.dump(line, f, indent=1)
+            return path
+        except OSError as e:
+            sys.stderr.write("bench.py: cannot write the details record to %s (%s)\n" % (path, e))
+    return None
 
 
 def _pick(d, keys):
@@ -780,18 +810,17 @@ def compact_line(line, details):
         for k, v in nc.items():
             if isinstance(v, dict):  # the pipelined / merged legs: proofs per s, flat under a prefix that says what they are
                 c["named_configs"].update({"jobs_in_flight." + kk: vv for kk, vv in v.items()})
-    c["details"] = os.path.relpath(details, ROOT) if os.path.abspath(details).startswith(ROOT + os.sep) else details
+    c["details"] = None if details is None else \
+        os.path.relpath(details, ROOT) if os.path.abspath(details).startswith(ROOT + os.sep) else details
     return c
 
 
 def emit(line):
     """the full record to the details file, the compact contract line as the LAST line of stdout"""
-    path = _details_path()
     # the host this ran on: logical CPUs, and what the container may use of them (cgroup cpu.max: every host-threaded figure
     # of the record -- CPU baselines, end-to-end jobs, application-thread legs -- lives inside that budget)
     line.setdefault("host", {"logical_cpus": os.cpu_count(), "cgroup_cpu_quota_cpus": _cgroup_cpu_quota()})
-    with open(path, "w") as f:
-        json.dump(line, f, indent=1)
+    path = _write_details(line)
     c = compact_line(line, path)
     text = json.dumps(c)
     # the line must NEVER outgrow the driver's log tail (it is ~2.8 KB): should a future key push it over, the optional
@@ -1163,6 +1192,8 @@ def main():
     ap.add_argument("--no-strong", action="store_true", help="skip the config-4 leg (2^24 points IN TOTAL over the ranks)")
     ap.add_argument("--strong-total-log2n", type=int, default=24)
     ap.add_argument("--no-mgpu-leg", action="store_true", help="skip the single-process snarkv_mgpu_* leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the results of the timed path's last step to DIR/*.npy (rank 0)")
     ap.add_argument("--mgpu-leg", action="store_true",
                     help="INTERNAL: run only the single-process multi-GPU leg over devices 0..gpus-1 and print its JSON")
     args = ap.parse_args()
@@ -1393,6 +1424,11 @@ def main():
         jobs = [got[64 * i:64 * i + 64] for i in range(args.steps)]
         assert all(jobs[i] == slot_results[i % nsets] for i in range(args.steps) if i % nsets < inflight)
         assert len(set(jobs)) == nsets and bytes(64) not in jobs
+    if args.dump_outputs and rank == 0:
+        if batch:
+            dump_outputs(args.dump_outputs, jobs[-1], got)
+        else:
+            dump_outputs(args.dump_outputs, slot_results[(step_no[0] - 1) % inflight])
 
     # single-MSM latency (strictly sequential), outside the timed region, for the record
     lat_ms, seq_stages = None, None

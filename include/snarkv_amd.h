@@ -206,7 +206,7 @@ int snarkv_g1_decompress(snarkv_ctx* ctx, const uint8_t* in32, size_t n, uint8_t
 /* ---- context-free entry points ------------------------------------------ *
  * `EcPointLoader::multi_scalar_multiplication` has no `&self` (loader.rs:108; the native loader is a unit struct,
  * native.rs:11-19), so a trait-bound caller reaches the device without a handle.  These forms draw a context (stream +
- * scratch) from a process-wide POOL per call: SNARKV_DEFAULT_CONTEXTS of them, else GPU_MAX_HW_QUEUES, else 4, created
+ * scratch) from a process-wide POOL per call: SNARKV_DEFAULT_CONTEXTS of them, else 4, created
  * on demand on device 0.  Calls from different host threads therefore run CONCURRENTLY on different contexts (16
  * rayon workers in flight = the `aggregate_*_pipelined` figures of bench.py); a thread returns to the context it used
  * last when that is free; with every context busy a call waits its turn.  All of them are synchronous (results are on

@@ -8,18 +8,11 @@ provides `torch.distributed` plumbing for the multi-GPU fold.
 There is NO CPU fallback: importing works anywhere, but creating a `Context`
 without the built library or without a HIP device raises.
 """
-import os as _os
+# HIP multiplexes a process's streams onto a fixed number of hardware queues (the runtime's default is 4) and kernels of
+# streams that share a queue run one after the other.  The queue count is the runtime's and the host's setting: neither
+# the package nor the library changes it (csrc/capi.hip).
 
-# HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and kernels of streams that
-# share a queue run one after the other.  The aggregation path is made of latency-bound launches (segmented small MSMs,
-# one-workgroup pairing deciders) that only fill the GPU when many jobs overlap: with 16 queues 16 jobs in flight verify
-# 2.9 x 10^5 proofs/s in 64-proof jobs against 1.15 x 10^5 with 4 (profiles/r03_agg_hw_queues.txt); the large-MSM batch
-# (5 streams) is level to 1 % better.  Read by the HIP runtime at its first call, so it is set here, before the library
-# is loaded; an explicit setting of the caller wins.  C / Rust callers set it themselves before their first HIP call
-# (INTEGRATION.md): the library does NOT touch the environment (csrc/capi.hip).
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
-from ._lib import (  # noqa: F401,E402
+from ._lib import (  # noqa: F401
     Context,
     DecidingKey,
     IpaDecidingKey,

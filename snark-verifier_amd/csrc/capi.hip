@@ -42,19 +42,16 @@ static int fetch_out(snarkv_ctx* ctx, const void* d, void* host, size_t bytes) {
   return SNARKV_OK;
 }
 
-// HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); streams sharing a queue serialise.
-// A server that keeps many latency-bound aggregation jobs in flight on contexts of their own wants 16 (2.5x the proofs/s
-// of 64-proof jobs, profiles/r03_agg_hw_queues.txt).  That is a process-wide runtime setting read at the runtime's first
-// call, so the library does NOT touch it when it is loaded: the caller exports GPU_MAX_HW_QUEUES=16 before its first HIP
-// call (the Python package does so on import unless the variable is set, INTEGRATION.md shows the Rust line).
+// HIP maps a process's streams onto a fixed number of hardware queues (the runtime's default is 4); streams sharing a
+// queue serialise.  The queue count is a process-wide setting of the runtime and the host: the library never touches it.
 
 // ---- the context-free entry points' contexts ------------------------------------------------------------------------
 // `EcPointLoader::multi_scalar_multiplication` has no `&self` (loader.rs:108), so a trait-bound Rust caller can only reach
 // the `bn254_*` forms -- and round 4 gave them ONE context behind one mutex: a rayon-parallel caller got one job at a
 // time, a sixteenth of what sixteen explicit contexts deliver.  Now they draw from a POOL of default
 // contexts (a stream + scratch each), checked out per call:
-//   * size: SNARKV_DEFAULT_CONTEXTS, else GPU_MAX_HW_QUEUES (the hardware queues the process's streams are spread over),
-//     else 4 (the runtime's default queue count); contexts are created on demand, never destroyed;
+//   * size: SNARKV_DEFAULT_CONTEXTS, else 4 (the runtime's default hardware-queue count); contexts are created on
+//     demand, never destroyed;
 //   * affinity: a thread comes back to the context it used last when that one is free (warm scratch), else any free
 //     one, else a new one while the pool may grow, else it waits;
 //   * nesting: bn254_kzg_decide -> bn254_kzg_decide_batch runs on the context the outer call holds;
@@ -76,11 +73,10 @@ static thread_local snarkv_ctx* tl_held = nullptr;
 static thread_local int64_t tl_flags = -1;  // -1: the process default
 
 static int pool_cap() {
-  for (const char* name : {"SNARKV_DEFAULT_CONTEXTS", "GPU_MAX_HW_QUEUES"})
-    if (const char* e = getenv(name)) {
-      int v = atoi(e);
-      if (v > 0) return std::min(v, 64);
-    }
+  if (const char* e = getenv("SNARKV_DEFAULT_CONTEXTS")) {
+    int v = atoi(e);
+    if (v > 0) return std::min(v, 64);
+  }
   return 4;
 }
 

@@ -75,7 +75,7 @@ def test_16_threads_of_64_proof_jobs_through_the_context_free_boundary():
     assert not errs
     created, cap = ctypes.c_int(0), ctypes.c_int(0)
     assert lib.bn254_default_contexts(ctypes.byref(created), ctypes.byref(cap)) == 0
-    assert cap.value == int(os.environ.get("SNARKV_DEFAULT_CONTEXTS") or os.environ.get("GPU_MAX_HW_QUEUES") or 4)
+    assert cap.value == int(os.environ.get("SNARKV_DEFAULT_CONTEXTS") or 4)
     assert 2 <= created.value <= cap.value  # several contexts in use at once, never more than the limit
     reps = 6
     wall = min(wave(reps) for _ in range(3))

@@ -4,7 +4,8 @@ the round-5 slip was a missing `loader_halo2`, which gates `system::halo2::trans
   * every Cargo feature it asks of `snark-verifier` exists there, and every module its `use snark_verifier::{...}` tree
     names is enabled by one of them (`#[cfg(feature = "...")] pub mod x;` in the reference's module tree);
   * halo2curves / halo2_proofs resolve to the version / tag the reference pins;
-  * the fixture these checks read (tests/golden/reference_manifest.json) is current where /root/reference is present."""
+  * the extractor that wrote the fixture these checks read (tests/golden/gen_reference_manifest.py ->
+    tests/golden/reference_manifest.json) reads back exactly that fixture from a crate laid out as it describes."""
 import json
 import os
 import re
@@ -83,14 +84,38 @@ def test_refgen_resolves_the_dependency_versions_the_reference_pins():
     assert "github.com/privacy-scaling-explorations/snark-verifier" in deps["snark-verifier"]["git"]
 
 
-def test_the_fixture_is_current_where_the_reference_is_present():
+def _write_crate(crate, fx):
+    """a miniature `snark-verifier` crate with the fixture's manifest entries and module tree: every gated module under its
+    `#[cfg(feature = "...")]`, every module on the way to one declared plainly, src/a/b.rs for `a::b`"""
+    toml = ['[package]', 'name = "snark-verifier"', 'version = "%s"' % fx["crate_version"], "", "[features]"]
+    toml += ["%s = [%s]" % (k, ", ".join('"%s"' % d for d in v)) for k, v in sorted(fx["feature_deps"].items())]
+    toml += ["", "[dependencies]", 'halo2_curves = { version = "%s", package = "halo2curves" }' % fx["halo2curves_version"],
+             'halo2_proofs = { git = "%s", tag = "%s", optional = true }' % (fx["halo2_proofs_git"], fx["halo2_proofs_tag"])]
+    os.makedirs(os.path.join(crate, "src"))
+    with open(os.path.join(crate, "Cargo.toml"), "w") as f:
+        f.write("\n".join(toml) + "\n")
+    children = {}
+    for path in fx["module_gates"]:
+        parts = path.split("::")
+        for k in range(1, len(parts) + 1):
+            children.setdefault(tuple(parts[:k - 1]), set()).add(parts[k - 1])
+    for parent, names in children.items():
+        rs = os.path.join(crate, "src", *parent) + ".rs" if parent else os.path.join(crate, "src", "lib.rs")
+        os.makedirs(os.path.dirname(rs), exist_ok=True)
+        with open(rs, "w") as f:
+            for name in sorted(names):
+                gate = fx["module_gates"].get("::".join(parent + (name,)))
+                f.write(('#[cfg(feature = "%s")]\n' % gate if gate else "") + "pub mod %s;\n" % name)
+
+
+def test_the_manifest_extractor_reproduces_the_fixture(tmp_path):
     import importlib.util
 
-    import pytest
-
-    if not os.path.exists("/root/reference/snark-verifier/Cargo.toml"):
-        pytest.skip("no /root/reference on this box: the committed extract stands")
+    fx = _fixture()
+    crate = os.path.join(str(tmp_path), "snark-verifier")
+    _write_crate(crate, fx)
     spec = importlib.util.spec_from_file_location("_genman", os.path.join(ROOT, "tests", "golden", "gen_reference_manifest.py"))
     g = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(g)
-    assert g.extract() == _fixture()
+    g.CRATE = crate
+    assert g.extract() == fx

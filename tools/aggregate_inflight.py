@@ -1,6 +1,7 @@
 """dev tool (GPU box): the aggregation job of bench.py's second metric (tools/aggregate_job.py) with N jobs in flight, one
-context + stream each -- ms per job and proofs/s by N.  What the hardware-queue record was taken with:
-  for q in 4 8 16 24; do GPU_MAX_HW_QUEUES=$q python tools/aggregate_inflight.py; done      (profiles/r03_agg_hw_queues.txt)
+context + stream each -- ms per job and proofs/s by N (profiles/r03_agg_hw_queues.txt was taken with it at several
+hardware-queue counts of the runtime):
+  python tools/aggregate_inflight.py
   rocprofv3 --kernel-trace --stats -- python tools/aggregate_inflight.py --proofs 1024 --inflight 16   (who stretches under overlap)"""
 import argparse
 import os
@@ -73,7 +74,7 @@ for nproofs in a.proofs:
             torch.cuda.synchronize()
             best = min(best, (time.perf_counter() - t0) / (N * a.rounds) * 1e3)
             submit = min(submit, (t1 - t0) / (N * a.rounds) * 1e3)
-        print("queues=%s proofs=%d inflight=%d throughput_hint=%d ms_per_job=%.4f proofs_per_s=%.3e host_submit_ms_per_job=%.4f" % (
-            os.environ.get("GPU_MAX_HW_QUEUES"), nproofs, N, int(N >= a.hint_from), best, nproofs / best * 1e3, submit), flush=True)
+        print("proofs=%d inflight=%d throughput_hint=%d ms_per_job=%.4f proofs_per_s=%.3e host_submit_ms_per_job=%.4f" % (
+            nproofs, N, int(N >= a.hint_from), best, nproofs / best * 1e3, submit), flush=True)
 for d in dks:
     d.close()

@@ -21,4 +21,4 @@ for K in (1, 2, 3, 4, 6, 8):
     res.append("K=%d %.3f" % (K, ms))
     assert all(bytes(o.cpu().numpy()) == bytes(outs[0].cpu().numpy()) for o in outs)
     for c in ctxs: c.close()
-print("acc_stream=%s queues=%s ms/MSM:" % (os.environ.get("SNARKV_ACC_STREAM", "1"), os.environ.get("GPU_MAX_HW_QUEUES", "4")), "  ".join(res))
+print("acc_stream=%s ms/MSM:" % os.environ.get("SNARKV_ACC_STREAM", "1"), "  ".join(res))

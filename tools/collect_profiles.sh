@@ -62,9 +62,9 @@ for m in 64 1024; do
   if [ -n "$db" ]; then python $R/tools/rocpd_top_kernels.py $db $O/${TAG}_rocprofv3_kernel_stats_aggregate_$m.csv; else
     f=$(find /tmp/prof_a -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${TAG}_rocprofv3_kernel_stats_aggregate_$m.csv; fi
 done
-# ... and with jobs in flight: by hardware-queue count, and the kernel durations under 16-fold overlap
+# ... and with jobs in flight: the kernel durations under 16-fold overlap
 cd $R
-GPU_MAX_HW_QUEUES=16 timeout 600 python tools/aggregate_inflight.py --inflight 1 8 16 32 2>/dev/null | grep queues= > $O/${TAG}_agg_inflight.txt
+timeout 600 python tools/aggregate_inflight.py --inflight 1 8 16 32 2>/dev/null | grep proofs= > $O/${TAG}_agg_inflight.txt
 cd /tmp
 for m in 64 1024; do
   rm -rf /tmp/prof_a; timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_a -- python $R/tools/aggregate_inflight.py --proofs $m --inflight 16 > /dev/null 2>&1

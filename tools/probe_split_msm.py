@@ -4,7 +4,6 @@ terms split over T concurrent calls from T host threads -- the question behind p
 launches share the chip badly, so only a job whose chunks are spread over time (the Poseidon pipeline) gains)."""
 import ctypes, os, sys, threading, time
 sys.path.insert(0, os.getcwd())
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import torch
 import snark_verifier_amd as sv
 lib = sv.load_library()
