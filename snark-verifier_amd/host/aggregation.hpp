@@ -12,7 +12,6 @@
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
-#include <functional>
 #include <iterator>
 #include <map>
 #include <mutex>
@@ -28,6 +27,44 @@ namespace snarkv_host {
 struct AggregationTimings {  // milliseconds, wall clock
   double read_proofs = 0, fr_algebra = 0, msm_device = 0, accumulate = 0, decide = 0, total = 0;
 };
+
+// The host job's settings: read from the environment ONCE per call, on the caller's thread, and handed down by const
+// reference.  No pool thread reads the environment (getenv is not safe against a concurrent setenv), and one call sees
+// one value of every knob -- the route chosen in capi.cpp and the job that runs on it included.
+struct HostJobSettings {
+  size_t hint_min = 0;          // SNARKV_HOST_HINT_MIN (0: unset, `hint_threshold` decides)
+  bool point_prefetch = true;   // unless SNARKV_HOST_NO_POINT_PREFETCH: transcripts decode grouped points (transcript.hpp)
+  size_t pipeline_min = 256;    // SNARKV_HOST_PIPELINE_MIN: from how many proofs `aggregate` runs pipelined; 0: never
+  size_t pipeline_chunk = 128;  // SNARKV_HOST_PIPELINE_CHUNK: proofs per chunk of the pipeline (2 per pool thread)
+
+  static HostJobSettings from_env() {
+    HostJobSettings s;
+    if (const char* e = getenv("SNARKV_HOST_HINT_MIN")) s.hint_min = (size_t)std::max(2, atoi(e));
+    s.point_prefetch = !getenv("SNARKV_HOST_NO_POINT_PREFETCH");
+    if (const char* e = getenv("SNARKV_HOST_PIPELINE_MIN")) s.pipeline_min = (size_t)std::max(0, atoi(e));
+    if (const char* e = getenv("SNARKV_HOST_PIPELINE_CHUNK")) s.pipeline_chunk = (size_t)std::max(1, atoi(e));
+    return s;
+  }
+  // From how many host-hashed proofs on the device decodes the batch's points.  The launch costs ~0.35-0.55 ms whatever
+  // the batch and saves each proof 13 host square roots (0.13 ms in scalar code): worth it from the third proof per thread
+  // on.  On a CPU with AVX-512 IFMA a transcript decodes the points of one `read_n_ec_points` TOGETHER (transcript.hpp
+  // `g1_decompress_x8`: one square-root chain per group, ~35 us per proof instead of 124) and the launch never pays:
+  // 64 proofs 2.77 -> 2.31 ms, 256: 4.22 -> 3.98, 1 024 (pipelined): 8.9 -> 8.2 ms (profiles/r06_ab_pipeline.txt).
+  size_t hint_threshold(unsigned threads) const {
+    if (hint_min) return hint_min;
+    if (poseidon_ifma::available() && point_prefetch) return (size_t)-1;
+    return std::max<size_t>(32, 2 * (size_t)threads + 1);
+  }
+};
+
+// Runs `f` whatever way the scope is left.
+template <class F>
+struct ScopeExit {
+  F f;
+  ~ScopeExit() { f(); }
+};
+template <class F>
+ScopeExit(F) -> ScopeExit<F>;
 
 // MOS: Gwc19 | Bdfg21.  TR: EvmTranscript | PoseidonTranscript | PoseidonTranscriptOnDevice: the transcript of the INNER
 // proofs.  The accumulation step (`As::create_proof`) runs on a fresh transcript of the same family, as the reference's
@@ -72,24 +109,16 @@ struct Aggregator {
     size_t P = 0;                  // points per proof
     bool any() const { return P != 0 && !ok.empty(); }
   };
-  // From how many host-hashed proofs on the device decodes the batch's points.  The launch costs ~0.35-0.55 ms whatever
-  // the batch and saves each proof 13 host square roots (0.13 ms in scalar code): worth it from the third proof per thread
-  // on.  On a CPU with AVX-512 IFMA a transcript decodes the points of one `read_n_ec_points` TOGETHER (transcript.hpp
-  // `g1_decompress_x8`: one square-root chain per group, ~35 us per proof instead of 124) and the launch never pays:
-  // 64 proofs 2.77 -> 2.31 ms, 256: 4.22 -> 3.98, 1 024 (pipelined): 8.9 -> 8.2 ms (profiles/r06_ab_pipeline.txt).
-  static size_t hint_min_default(unsigned threads) {
-    if (poseidon_ifma::available() && !getenv("SNARKV_HOST_NO_POINT_PREFETCH")) return (size_t)-1;
-    return std::max<size_t>(32, 2 * (size_t)threads + 1);
-  }
   static void decompress_hints(const KzgSuccinctVerifyingKey& svk, const PlonkProtocol& pr,
                                const std::vector<std::vector<std::vector<Fr>>>& instances,
-                               const std::vector<std::vector<uint8_t>>& proofs, unsigned threads, PointHints& h,
-                               bool use_pool = true) {  // false: the caller must not wait for the host pool (it is busy reading)
+                               const std::vector<std::vector<uint8_t>>& proofs, unsigned threads,
+                               const HostJobSettings& s, PointHints& h) {
     const size_t n = proofs.size();
     const int T = 5, RATE = 4, R_F = 8, R_P = 60;
     h.row.assign(n, (size_t)-1);
     h.P = 0;
     PoseidonTranscriptT<RecordingSponge> t0(proofs[0], T, RATE, R_F, R_P);
+    t0.set_point_prefetch(s.point_prefetch);
     if (!SV::read_proof(svk, pr, instances[0], t0).ok()) return;
     const std::vector<size_t> offs = t0.point_offsets();
     const size_t len0 = proofs[0].size();
@@ -102,14 +131,9 @@ struct Aggregator {
     std::vector<uint8_t> in(32 * P * who.size());
     h.pts.resize(64 * P * who.size());
     h.ok.resize(P * who.size());
-    auto gather = [&](size_t k) {
+    parallel_for(who.size(), threads, [&](size_t k) {
       for (size_t q = 0; q < P; ++q) memcpy(&in[32 * (k * P + q)], proofs[who[k]].data() + offs[q], 32);
-    };
-    if (use_pool) {
-      parallel_for(who.size(), threads, gather, 64);
-    } else {
-      for (size_t k = 0; k < who.size(); ++k) gather(k);
-    }
+    }, 64);
     DeviceScope dev;
     if (bn254_g1_decompress(in.data(), P * who.size(), h.pts.data(), h.ok.data()) != SNARKV_OK)
       throw std::runtime_error(std::string("bn254_g1_decompress: ") + snarkv_last_error());
@@ -119,7 +143,8 @@ struct Aggregator {
   static Error read_proofs_device_hashed(const KzgSuccinctVerifyingKey& svk, const PlonkProtocol& pr,
                                          const std::vector<std::vector<std::vector<Fr>>>& instances,
                                          const std::vector<std::vector<uint8_t>>& proofs, unsigned threads,
-                                         std::vector<PlonkProof<MOS>>& pfs) {
+                                         std::vector<PlonkProof<MOS>>& pfs,
+                                         const HostJobSettings& s = HostJobSettings::from_env()) {
     const size_t n = proofs.size();
     const int T = 5, RATE = 4, R_F = 8, R_P = 60;  // examples/evm-verifier-with-accumulator.rs:36-39
     constexpr bool trace = SNARKV_HOST_TRACE != 0;  // dev aid: the four stages of this phase on stderr
@@ -141,6 +166,7 @@ struct Aggregator {
       const size_t len0 = proofs[0].size(), stride = (len0 + 15) & ~(size_t)15;
       for (size_t i = 1; i < n && fused; ++i) fused = proofs[i].size() == len0;
       PoseidonTranscriptT<RecordingSponge> t0(proofs[0], T, RATE, R_F, R_P);
+      t0.set_point_prefetch(s.point_prefetch);
       t0.record_layout();
       fused = fused && len0 > 0 && SV::read_proof(svk, pr, instances[0], t0).ok();
       std::vector<uint32_t> offs;
@@ -204,6 +230,7 @@ struct Aggregator {
           // in this pass exactly as it does on the host-hashed route
           parallel_for(n, threads, [&](size_t i) {
             PoseidonTranscriptT<ReplaySponge> t(proofs[i], T, RATE, R_F, R_P);
+            t.set_point_prefetch(s.point_prefetch);
             t.set_point_hints(&pts[64 * P * i], &okv[P * i], P, /*strict=*/true);  // the challenges hash THESE decodings
             t.sponge().challenges.resize(S);
             for (size_t q = 0; q < S; ++q) Fr::from_bytes(&chal[32 * (i * S + q)], &t.sponge().challenges[q]);
@@ -234,7 +261,7 @@ struct Aggregator {
     hints.row.assign(n, (size_t)-1);  // (a batch of one proof asks for no hints: every row stays "none")
     double t_pass0 = 0;
     if (n >= 2) {
-      decompress_hints(svk, pr, instances, proofs, threads, hints);
+      decompress_hints(svk, pr, instances, proofs, threads, s, hints);
       t_pass0 = lap();
     }
     const std::vector<uint8_t>&hint_pts = hints.pts, &hint_ok = hints.ok;
@@ -243,6 +270,7 @@ struct Aggregator {
     // pass 1: parse (points not covered by pass 0 are decompressed here) and record what the sponge would see
     parallel_for(n, threads, [&](size_t i) {
       PoseidonTranscriptT<RecordingSponge> t(proofs[i], T, RATE, R_F, R_P);
+      t.set_point_prefetch(s.point_prefetch);
       // (a flag of 0 = no hint: an invalid encoding is re-examined, and rejected, by the host function)
       if (hint_row[i] != (size_t)-1 && !hint_ok.empty())
         t.set_point_hints(&hint_pts[64 * P * hint_row[i]], &hint_ok[P * hint_row[i]], P);
@@ -278,6 +306,7 @@ struct Aggregator {
     // pass 2: parse again with the real challenges
     parallel_for(n, threads, [&](size_t i) {
       PoseidonTranscriptT<ReplaySponge> t(proofs[i], T, RATE, R_F, R_P);
+      t.set_point_prefetch(s.point_prefetch);
       t.set_decoded_points(decoded[i].data(), decoded[i].size());
       t.sponge().challenges.resize(S);
       for (size_t q = 0; q < S; ++q) Fr::from_bytes(&out[32 * (i * S + q)], &t.sponge().challenges[q]);
@@ -296,86 +325,102 @@ struct Aggregator {
     return Error{};
   }
 
+  // What the front half of a job keeps per proof (both routes: `succinct_verify_all` and the pipelined reader)
+  struct PerProof {
+    std::vector<PlonkProof<MOS>> pfs;
+    std::vector<typename SV::Pairs> jobs;  // proof i's two MSMs at 2 i and 2 i + 1
+    std::vector<Error> errs;
+    std::vector<double> t_read;  // ms in proof i's read_proof
+    explicit PerProof(size_t n) : pfs(n), jobs(2 * n), errs(n), t_read(n, 0.0) {}
+  };
+  // One proof of the front half: `read_proof` on a TR transcript (with the batch's point hints, if any; the device-hashed
+  // route has filled pfs[i] already), then the host half of `verify` -- the pair lists of its two MSMs.  A bad proof
+  // leaves its error in errs[i] and returns false.
+  static bool verify_one(size_t i, const KzgSuccinctVerifyingKey& svk, const PlonkProtocol& pr,
+                         const std::vector<std::vector<std::vector<Fr>>>& instances,
+                         const std::vector<std::vector<uint8_t>>& proofs, const PointHints& hints,
+                         const HostJobSettings& s, PerProof& pp) {
+    using clk = std::chrono::steady_clock;
+    auto a = clk::now();
+    if constexpr (!std::is_same<TR, PoseidonTranscriptOnDevice>::value) {
+      TR t(proofs[i]);
+      if constexpr (std::is_same<TR, PoseidonTranscript>::value) {
+        t.set_point_prefetch(s.point_prefetch);
+        if (hints.any() && hints.row[i] != (size_t)-1)
+          t.set_point_hints(&hints.pts[64 * hints.P * hints.row[i]], &hints.ok[hints.P * hints.row[i]], hints.P);
+      }
+      auto pf = SV::read_proof(svk, pr, instances[i], t);
+      if (!pf.ok()) {
+        pp.errs[i] = pf.err;
+        return false;
+      }
+      pp.pfs[i] = std::move(*pf.value);
+    }
+    pp.t_read[i] = std::chrono::duration<double, std::milli>(clk::now() - a).count();
+    auto p2 = SV::msm_pairs(svk, pr, instances[i], pp.pfs[i]);
+    if (!p2.ok()) {
+      pp.errs[i] = p2.err;
+      return false;
+    }
+    pp.jobs[2 * i] = std::move(p2.value->first);
+    pp.jobs[2 * i + 1] = std::move(p2.value->second);
+    return true;
+  }
+  // The busy time of a pass of `verify_one` (`wall` ms on `threads` threads, `grain` proofs per claim) as {read, algebra}:
+  // the per-proof read share is timed, the algebra share is the rest of the pass
+  static std::pair<double, double> split_busy(double wall, const std::vector<double>& t_read, unsigned threads, size_t grain) {
+    double read_sum = 0;
+    for (double x : t_read) read_sum += x;
+    const unsigned used = std::max(1u, std::min<unsigned>(threads, (unsigned)std::max<size_t>(1, t_read.size() / grain)));
+    const double frac = std::min(1.0, std::max(0.0, (read_sum / used) / std::max(wall, 1e-9)));
+    return {wall * frac, wall * (1.0 - frac)};
+  }
+
   // The front half of a job: succinct-verify every proof -- `read_proof` + the host half of `verify` on `threads` host
   // threads, all 2 n MSMs in ONE segmented launch -- and return, per proof, its new accumulator followed by the old ones
   // it carried (verifier/plonk.rs:58-92).
   static Result<std::vector<std::vector<KzgAccumulator>>> succinct_verify_all(
       const KzgSuccinctVerifyingKey& svk, const PlonkProtocol& pr, const std::vector<std::vector<std::vector<Fr>>>& instances,
-      const std::vector<std::vector<uint8_t>>& proofs, unsigned threads, AggregationTimings* tm = nullptr) {
+      const std::vector<std::vector<uint8_t>>& proofs, unsigned threads, AggregationTimings* tm = nullptr,
+      const HostJobSettings& s = HostJobSettings::from_env()) {
     using R = Result<std::vector<std::vector<KzgAccumulator>>>;
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const size_t n = proofs.size();
     if (n == 0 || instances.size() != n) return R::Err(Error{Error::InvalidInstances, "one instance set per proof"});
     auto t0 = clk::now();
-    std::vector<PlonkProof<MOS>> pfs(n);
-    std::vector<Error> errs(n);
-    std::vector<typename SV::Pairs> jobs(2 * n);
-    std::vector<double> t_read(n, 0.0);
+    PerProof pp(n);
     constexpr bool kDeviceHash = std::is_same<TR, PoseidonTranscriptOnDevice>::value;
     // a Keccak proof costs ~60 us of host work, waking a pool worker ~10 us, a Poseidon proof ~0.5 ms: two proofs per
     // worker are worth a wake-up (64 proofs: 0.55 -> 0.17 ms of host time against 16 per worker; gpurun_out probe, r3)
-    size_t grain = std::is_same<TR, PoseidonTranscript>::value ? 1 : 2;
-    if (const char* e = getenv("SNARKV_HOST_GRAIN")) grain = (size_t)std::max(1, atoi(e));  // tuning knob
+    constexpr size_t grain = std::is_same<TR, PoseidonTranscript>::value ? 1 : 2;
     double device_hash_ms = 0;
     if constexpr (kDeviceHash) {
-      Error e = read_proofs_device_hashed(svk, pr, instances, proofs, threads, pfs);
+      Error e = read_proofs_device_hashed(svk, pr, instances, proofs, threads, pp.pfs, s);
       if (!e.ok()) return R::Err(e);
       device_hash_ms = ms(t0, clk::now());
     }
     // Poseidon proofs hashed on the HOST (round 5: the sponge on AVX-512 IFMA makes 64 threads faster at it than the
     // device's one-lane-per-transcript kernel): the batch's compressed points are still decompressed by ONE device launch
-    // and offered to the transcripts as hints -- the square roots were half of a host-read proof
+    // and offered to the transcripts as hints -- the square roots were half of a host-read proof (`hint_threshold`)
     PointHints hints;
-    constexpr bool kHostPoseidon = std::is_same<TR, PoseidonTranscript>::value;
-    if constexpr (kHostPoseidon) {
-      size_t min_batch = hint_min_default(threads);
-      if (const char* e = getenv("SNARKV_HOST_HINT_MIN")) min_batch = (size_t)std::max(2, atoi(e));  // tuning / A-B knob
-      if (n >= min_batch) decompress_hints(svk, pr, instances, proofs, threads, hints);
+    if constexpr (std::is_same<TR, PoseidonTranscript>::value) {
+      if (n >= s.hint_threshold(threads)) decompress_hints(svk, pr, instances, proofs, threads, s, hints);
     }
-    // one pass per proof: read_proof, then the host half of verify (the pair lists of its two MSMs)
-    parallel_for(n, threads, [&](size_t i) {
-      auto a = clk::now();
-      if constexpr (!kDeviceHash) {
-        TR t(proofs[i]);
-        if constexpr (kHostPoseidon) {
-          if (hints.any() && hints.row[i] != (size_t)-1)
-            t.set_point_hints(&hints.pts[64 * hints.P * hints.row[i]], &hints.ok[hints.P * hints.row[i]], hints.P);
-        }
-        auto pf = SV::read_proof(svk, pr, instances[i], t);
-        if (!pf.ok()) {
-          errs[i] = pf.err;
-          return;
-        }
-        pfs[i] = std::move(*pf.value);
-      }
-      t_read[i] = ms(a, clk::now());
-      auto p2 = SV::msm_pairs(svk, pr, instances[i], pfs[i]);
-      if (!p2.ok()) {
-        errs[i] = p2.err;
-        return;
-      }
-      jobs[2 * i] = std::move(p2.value->first);
-      jobs[2 * i + 1] = std::move(p2.value->second);
-    }, grain);
-    for (auto& e : errs)
+    parallel_for(n, threads, [&](size_t i) { verify_one(i, svk, pr, instances, proofs, hints, s, pp); }, grain);
+    for (auto& e : pp.errs)
       if (!e.ok()) return R::Err(e);
     auto t2 = clk::now();
-    auto pts = L::multi_scalar_multiplication_batch(jobs);
+    auto pts = L::multi_scalar_multiplication_batch(pp.jobs);
     auto t3 = clk::now();
     std::vector<std::vector<KzgAccumulator>> out(n);
     for (size_t i = 0; i < n; ++i) {
       out[i].push_back(KzgAccumulator{pts[2 * i], pts[2 * i + 1]});
-      out[i].insert(out[i].end(), pfs[i].old_accumulators.begin(), pfs[i].old_accumulators.end());
+      out[i].insert(out[i].end(), pp.pfs[i].old_accumulators.begin(), pp.pfs[i].old_accumulators.end());
     }
     if (tm) {
-      double host = ms(t0, t2), read_sum = 0;
-      for (double x : t_read) read_sum += x;
-      // the per-proof read share is timed; the algebra share is the rest of the parallel pass
-      unsigned used = std::max(1u, std::min<unsigned>(threads, (unsigned)std::max<size_t>(1, n / grain)));
-      double frac = std::min(1.0, std::max(0.0, (read_sum / used) / std::max(host, 1e-9)));
-      tm->read_proofs = host * frac;
-      tm->fr_algebra = host * (1.0 - frac);
+      const double host = ms(t0, t2);
+      std::tie(tm->read_proofs, tm->fr_algebra) = split_busy(host, pp.t_read, threads, grain);
       if (kDeviceHash) {  // the read phase was timed as a whole (two parsing passes + the device launch)
         tm->read_proofs = device_hash_ms;
         tm->fr_algebra = host - device_hash_ms;
@@ -404,47 +449,34 @@ struct Aggregator {
   // at the same CPU time: profiles/r06_ab_pipeline.txt.
   // Timings: `read_proofs`, `fr_algebra`, `msm_device` are the helper threads' BUSY times and run under `accumulate`
   // (the caller's wall time from the first wait to the accumulated point); `total` is wall time.
-  static size_t pipeline_min() {
-    if (const char* e = getenv("SNARKV_HOST_PIPELINE_MIN")) return (size_t)std::max(0, atoi(e));  // 0: never
-    return 256;
-  }
   static Result<KzgAccumulator> aggregate_pipelined(const KzgSuccinctVerifyingKey& svk, const PlonkProtocol& pr,
                                                     const std::vector<std::vector<std::vector<Fr>>>& instances,
                                                     const std::vector<std::vector<uint8_t>>& proofs, unsigned threads,
-                                                    AggregationTimings* tm) {
+                                                    AggregationTimings* tm, const HostJobSettings& s) {
     using R = Result<KzgAccumulator>;
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const size_t n = proofs.size();
     if (n == 0 || instances.size() != n) return R::Err(Error{Error::InvalidInstances, "one instance set per proof"});
-    size_t chunk = 128;  // 2 proofs per pool thread
-    if (const char* e = getenv("SNARKV_HOST_PIPELINE_CHUNK")) chunk = (size_t)std::max(1, atoi(e));  // tuning knob
+    const size_t chunk = s.pipeline_chunk;
     // chunk boundaries: the FIRST chunk is half a chunk -- the sponge, which bounds the job, idles until the first
     // accumulators arrive (a read pass + a launch), and both are shorter for fewer proofs
     std::vector<size_t> cut(1, 0);
-    if (n > 2 * chunk && chunk >= 2 && !getenv("SNARKV_HOST_PIPELINE_NO_RAMP")) cut.push_back(chunk / 2);
+    if (n > 2 * chunk && chunk >= 2) cut.push_back(chunk / 2);
     while (cut.back() < n) cut.push_back(std::min(n, cut.back() + chunk));
     const size_t K = cut.size() - 1;
     auto t0 = clk::now();
     PointHints hints;
-    {
-      size_t min_batch = hint_min_default(threads);
-      if (const char* e = getenv("SNARKV_HOST_HINT_MIN")) min_batch = (size_t)std::max(2, atoi(e));
-      if (n >= min_batch) decompress_hints(svk, pr, instances, proofs, threads, hints);
-    }
+    if (n >= s.hint_threshold(threads)) decompress_hints(svk, pr, instances, proofs, threads, s, hints);
     // (Measured and dropped: the hint launch on a thread of its own while the first proofs are read without hints, and a
     // first chunk of a quarter chunk -- the first accumulators are bounded by the launch latency of a small MSM (~0.65 ms)
     // either way, the early proofs pay 13 host square roots each, and the job came out level at +12 % CPU time.)
-    std::vector<PlonkProof<MOS>> pfs(n);
-    std::vector<Error> errs(n);
-    std::vector<typename SV::Pairs> jobs(2 * n);
+    PerProof pp(n);
     std::vector<std::vector<KzgAccumulator>> out(n);
     // device threads: chunk k goes to thread k % D.  A chunk's launch is a latency chain (0.75 ms for 128 proofs against
     // 1.25 for all 1 024), so ONE thread issuing them back to back is as slow as the sponge (8 x 0.75 ms against 6.4) and
     // every hiccup of it starves the absorber; two keep two launches in flight on their own default contexts.
-    size_t D = 2;
-    if (const char* e = getenv("SNARKV_HOST_PIPELINE_DEVICE_THREADS")) D = (size_t)std::max(1, std::min(8, atoi(e)));
-    D = std::min(D, K);
+    const size_t D = std::min<size_t>(2, K);
     std::vector<std::atomic<size_t>> msm_ready(K);  // 1 = chunk k's accumulators are in `out`
     for (auto& f : msm_ready) f.store(0, std::memory_order_relaxed);
     std::atomic<bool> stop{false};
@@ -494,22 +526,6 @@ struct Aggregator {
       read_left[k].store(cut[k + 1] - cut[k], std::memory_order_relaxed);
       read_ready[k].store(0, std::memory_order_relaxed);
     }
-    std::thread reader;
-    std::vector<std::thread> device;
-    struct JoinAll {  // whatever way this function is left (a std::thread that cannot be started, say): stop and join
-      std::thread& r;
-      std::vector<std::thread>& d;
-      std::function<void()> stop_all;
-      ~JoinAll() {
-        bool any = r.joinable();
-        for (auto& t : d) any = any || t.joinable();
-        if (!any) return;
-        stop_all();
-        if (r.joinable()) r.join();
-        for (auto& t : d)
-          if (t.joinable()) t.join();
-      }
-    } join_all{reader, device, halt};
     // Item order of the pass: the pool hands out `claim` consecutive items at a time, so with the proofs in plain order the
     // first chunk (64 proofs) would go to 32 workers, two proofs each, while the other 32 start on the second chunk.  The
     // FIRST item of every early claim is a proof of the first chunk instead: every worker's first proof belongs to it, and
@@ -525,52 +541,35 @@ struct Aggregator {
       }
       while (next < n) order[t++] = (uint32_t)next++;
     }
+    std::thread reader;
+    std::vector<std::thread> device;
+    // Whatever way this function is left (a std::thread that cannot be started, say): stop the helpers and join them.
+    // Everything the helpers capture by reference MUST be declared above this guard: unwinding destroys it only after
+    // the guard has joined them.
+    ScopeExit join_all{[&] {
+      halt();
+      if (reader.joinable()) reader.join();
+      for (auto& t : device)
+        if (t.joinable()) t.join();
+    }};
     reader = std::thread([&] {
       try {
-        std::vector<double> t_read(n, 0.0);
         auto a = clk::now();
         parallel_for(n, threads, [&](size_t item) {
           const size_t i = order[item];
           const size_t k = chunk_of[i];
           bool good = false;
-          struct Done {  // whatever way the task ends: the chunk's count goes down, its last GOOD proof publishes it
-            std::function<void()> f;
-            ~Done() { f(); }
-          } done{[&] {
+          ScopeExit done{[&] {  // whatever way the task ends: the chunk's count goes down, its last GOOD proof publishes it
             if (!good) halt();
             if (read_left[k].fetch_sub(1, std::memory_order_acq_rel) == 1 && !stop.load(std::memory_order_acquire)) {
               bool bad = false;
-              for (size_t q = cut[k]; q < cut[k + 1] && !bad; ++q) bad = !errs[q].ok();
+              for (size_t q = cut[k]; q < cut[k + 1] && !bad; ++q) bad = !pp.errs[q].ok();
               if (!bad) publish(read_ready[k], 1);
             }
           }};
-          auto b = clk::now();
-          TR t(proofs[i]);
-          if (hints.any() && hints.row[i] != (size_t)-1)
-            t.set_point_hints(&hints.pts[64 * hints.P * hints.row[i]], &hints.ok[hints.P * hints.row[i]], hints.P);
-          auto pf = SV::read_proof(svk, pr, instances[i], t);
-          if (!pf.ok()) {
-            errs[i] = pf.err;
-            return;
-          }
-          pfs[i] = std::move(*pf.value);
-          t_read[i] = ms(b, clk::now());
-          auto p2 = SV::msm_pairs(svk, pr, instances[i], pfs[i]);
-          if (!p2.ok()) {
-            errs[i] = p2.err;
-            return;
-          }
-          jobs[2 * i] = std::move(p2.value->first);
-          jobs[2 * i + 1] = std::move(p2.value->second);
-          good = true;
+          good = verify_one(i, svk, pr, instances, proofs, hints, s, pp);
         }, 1);
-        const double wall = ms(a, clk::now());
-        double rs = 0;
-        for (size_t i = 0; i < n; ++i) rs += t_read[i];
-        const unsigned used = std::max(1u, std::min<unsigned>(threads, (unsigned)n));
-        const double frac = std::min(1.0, std::max(0.0, (rs / used) / std::max(wall, 1e-9)));
-        busy_read = wall * frac;
-        busy_algebra = wall * (1.0 - frac);
+        std::tie(busy_read, busy_algebra) = split_busy(ms(a, clk::now()), pp.t_read, threads, 1);
       } catch (...) {
         thrown[0] = std::current_exception();
         halt();
@@ -583,11 +582,11 @@ struct Aggregator {
             if (!wait_for(read_ready[k], 0)) break;
             const size_t lo = cut[k], hi = cut[k + 1];
             auto a = clk::now();
-            std::vector<typename SV::Pairs> part(std::make_move_iterator(jobs.begin() + 2 * lo), std::make_move_iterator(jobs.begin() + 2 * hi));
+            std::vector<typename SV::Pairs> part(std::make_move_iterator(pp.jobs.begin() + 2 * lo), std::make_move_iterator(pp.jobs.begin() + 2 * hi));
             auto pts = L::multi_scalar_multiplication_batch(part, /*use_pool=*/false);  // (the pool is the reader's)
             for (size_t i = lo; i < hi; ++i) {
               out[i].push_back(KzgAccumulator{pts[2 * (i - lo)], pts[2 * (i - lo) + 1]});
-              out[i].insert(out[i].end(), pfs[i].old_accumulators.begin(), pfs[i].old_accumulators.end());
+              out[i].insert(out[i].end(), pp.pfs[i].old_accumulators.begin(), pp.pfs[i].old_accumulators.end());
             }
             busy_msm[d] += ms(a, clk::now());
             publish(msm_ready[k], 1);
@@ -605,16 +604,10 @@ struct Aggregator {
     accs.reserve(n);
     Error absorb_err;
     std::exception_ptr thrown_here;
-    const bool ptrace = getenv("SNARKV_HOST_PIPELINE_TRACE") != nullptr;  // dev aid: the caller's timeline on stderr
-    double t_first = 0, t_waited = 0;
     try {
       for (size_t k = 0; k < K && absorb_err.ok(); ++k) {
-        auto w0 = clk::now();
         if (!wait_for(msm_ready[k], 0)) break;
-        if (k == 0) t_first = ms(t0, clk::now());
-        else t_waited += ms(w0, clk::now());
-        const size_t lo = cut[k], hi = cut[k + 1];
-        for (size_t i = lo; i < hi && absorb_err.ok(); ++i)
+        for (size_t i = cut[k]; i < cut[k + 1] && absorb_err.ok(); ++i)
           for (auto& a : out[i]) {
             absorb_err = at.common_ec_point(a.lhs);
             if (absorb_err.ok()) absorb_err = at.common_ec_point(a.rhs);
@@ -631,18 +624,13 @@ struct Aggregator {
     for (auto& e : thrown)
       if (e) std::rethrow_exception(e);
     if (thrown_here) std::rethrow_exception(thrown_here);
-    for (auto& e : errs)
+    for (auto& e : pp.errs)
       if (!e.ok()) return R::Err(e);
     if (!absorb_err.ok()) return R::Err(absorb_err);
     if (accs.empty()) throw Panic("create_proof with no instances (reference: assert!, accumulation.rs:159)");
-    auto t_abs = clk::now();
     KzgAsProof proof;
     proof.r = at.squeeze_challenge();
     auto acc = KzgAs<MOS>::verify(KzgAsVerifyingKey{}, accs, proof);
-    if (ptrace)
-      fprintf(stderr, "aggregate_pipelined: %zu proofs, %zu chunks: threads up %.3f, first accumulators %.3f, starved later %.3f, "
-                      "absorbed + joined %.3f, squeeze + KzgAs::verify %.3f ms\n", n, K, ms(t0, t1), t_first, t_waited, ms(t0, t_abs),
-              ms(t_abs, clk::now()));
     if (tm) {
       auto t2 = clk::now();
       tm->read_proofs = busy_read;
@@ -659,15 +647,15 @@ struct Aggregator {
   static Result<KzgAccumulator> aggregate(const KzgSuccinctVerifyingKey& svk, const PlonkProtocol& pr,
                                           const std::vector<std::vector<std::vector<Fr>>>& instances,
                                           const std::vector<std::vector<uint8_t>>& proofs, unsigned threads,
-                                          AggregationTimings* tm = nullptr) {
+                                          AggregationTimings* tm = nullptr,
+                                          const HostJobSettings& s = HostJobSettings::from_env()) {
     using R = Result<KzgAccumulator>;
     using clk = std::chrono::steady_clock;
     if constexpr (std::is_same<TR, PoseidonTranscript>::value) {
-      const size_t pmin = pipeline_min();
-      if (pmin && proofs.size() >= pmin && threads > 1 && !HostPool::in_worker())
-        return aggregate_pipelined(svk, pr, instances, proofs, threads, tm);
+      if (s.pipeline_min && proofs.size() >= s.pipeline_min && threads > 1 && !HostPool::in_worker())
+        return aggregate_pipelined(svk, pr, instances, proofs, threads, tm, s);
     }
-    auto per_proof = succinct_verify_all(svk, pr, instances, proofs, threads, tm);
+    auto per_proof = succinct_verify_all(svk, pr, instances, proofs, threads, tm, s);
     if (!per_proof.ok()) return R::Err(per_proof.err);
     auto t3 = clk::now();
     std::vector<KzgAccumulator> accs;
@@ -694,7 +682,8 @@ struct Aggregator {
                                                       const std::vector<std::vector<std::vector<Fr>>>& instances,
                                                       const std::vector<std::vector<uint8_t>>& proofs,
                                                       const std::vector<uint32_t>& sizes, unsigned threads,
-                                                      AggregationTimings* tm = nullptr) {
+                                                      AggregationTimings* tm = nullptr,
+                                                      const HostJobSettings& s = HostJobSettings::from_env()) {
     using R = Result<ManyResult>;
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -705,7 +694,7 @@ struct Aggregator {
     }
     if (sizes.empty() || total != proofs.size()) return R::Err(Error{Error::InvalidInstances, "job sizes do not add up to the proofs"});
     dk.handle();  // G2 line tables: per-key setup, not per-proof work
-    auto per_proof = succinct_verify_all(dk.svk, pr, instances, proofs, threads, tm);
+    auto per_proof = succinct_verify_all(dk.svk, pr, instances, proofs, threads, tm, s);
     if (!per_proof.ok()) return R::Err(per_proof.err);
     auto t3 = clk::now();
     // per job: the accumulation transcript and the pair lists of `KzgAs::verify` (host), independent across jobs
@@ -757,10 +746,11 @@ struct Aggregator {
   static Error aggregate_and_decide(const KzgDecidingKey& dk, const PlonkProtocol& pr,
                                     const std::vector<std::vector<std::vector<Fr>>>& instances,
                                     const std::vector<std::vector<uint8_t>>& proofs, unsigned threads,
-                                    AggregationTimings* tm = nullptr, KzgAccumulator* acc_out = nullptr) {
+                                    AggregationTimings* tm = nullptr, KzgAccumulator* acc_out = nullptr,
+                                    const HostJobSettings& s = HostJobSettings::from_env()) {
     using clk = std::chrono::steady_clock;
     dk.handle();  // G2 line tables: per-key setup, not per-proof work
-    auto acc = aggregate(dk.svk, pr, instances, proofs, threads, tm);
+    auto acc = aggregate(dk.svk, pr, instances, proofs, threads, tm, s);
     if (!acc.ok()) return acc.err;
     if (acc_out) *acc_out = *acc.value;
     auto a = clk::now();

@@ -33,15 +33,13 @@ namespace {
 // (SNARKV_HOST_POSEIDON_DEVICE_MIN); with the AVX-512 IFMA sponge and the batch's points decompressed by the device as
 // hints the host reads 512 proofs in ~1.2 ms and 1 024 in 2.3 ms (device: 3.3 / 3.6 ms), level end to end at 1 024 with
 // the wider tail -- so there the host keeps batches below 1 024 (profiles/r05_host_poseidon.txt).
-// `pipelined`: the caller is `snarkv_host_aggregate` (ONE job), whose host route overlaps the reading, the MSMs and the
-// accumulation sponge from SNARKV_HOST_PIPELINE_MIN proofs on (host/aggregation.hpp `aggregate_pipelined`): the job is
-// then bounded by the one thread that absorbs the accumulators whatever hashed the proofs, and the device launch's 3 ms
-// would only delay its start -- as long as the pool has the threads to read a chunk faster than the sponge absorbs one.
-static int poseidon_auto_route(size_t n, bool pipelined = false) {
-  if (pipelined && HostPool::get().size() >= 32) {
-    const size_t pmin = Aggregator<Gwc19, PoseidonTranscript>::pipeline_min();
-    if (pmin && n >= pmin) return SNARKV_HOST_TRANSCRIPT_POSEIDON;
-  }
+// `pipeline_min`: from how many proofs the caller's job runs pipelined (0: never; callers other than `snarkv_host_aggregate`
+// pass none).  That caller runs ONE job, whose host route overlaps the reading, the MSMs and the accumulation sponge from
+// that many proofs on (host/aggregation.hpp `aggregate_pipelined`): the job is then bounded by the one thread that absorbs
+// the accumulators whatever hashed the proofs, and the device launch's 3 ms would only delay its start -- as long as the
+// pool has the threads to read a chunk faster than the sponge absorbs one.
+static int poseidon_auto_route(size_t n, size_t pipeline_min = 0) {
+  if (pipeline_min && HostPool::get().size() >= 32 && n >= pipeline_min) return SNARKV_HOST_TRANSCRIPT_POSEIDON;
   // (round 6: 5.2 us permutations and grouped point decoding -- 64 threads read 1 024 proofs in 2.3 ms, the device in 3.5)
   const size_t device_min = poseidon_ifma::available() ? 3 * (size_t)SNARKV_HOST_POSEIDON_DEVICE_MIN : (size_t)SNARKV_HOST_POSEIDON_DEVICE_MIN;
   return n >= device_min ? SNARKV_HOST_TRANSCRIPT_POSEIDON_DEVICE : SNARKV_HOST_TRANSCRIPT_POSEIDON;
@@ -90,13 +88,14 @@ std::vector<KzgAccumulator> accs_from_bytes(const uint8_t* accs128, uint32_t m) 
 template <class MOS, class TR>
 Error read_all(const KzgSuccinctVerifyingKey& svk, const PlonkProtocol& pr,
                const std::vector<std::vector<std::vector<Fr>>>& insts, const std::vector<std::vector<uint8_t>>& pbytes,
-               bool strict, std::vector<PlonkProof<MOS>>& pfs, bool* trailing) {
+               bool strict, const HostJobSettings& s, std::vector<PlonkProof<MOS>>& pfs, bool* trailing) {
   const size_t n = pbytes.size();
   pfs.resize(n);
   std::vector<Error> errs(n);
   std::vector<uint8_t> left(n, 0);
   parallel_for(n, HostPool::get().size(), [&](size_t i) {
     TR t(pbytes[i]);
+    if constexpr (std::is_same<TR, PoseidonTranscript>::value) t.set_point_prefetch(s.point_prefetch);
     auto pf = PlonkSuccinctVerifier<MOS>::read_proof(svk, pr, insts[i], t);
     if (!pf.ok()) {
       errs[i] = pf.err;
@@ -123,16 +122,17 @@ int succinct_verify_batch(const PlonkProtocol& pr, const KzgDecidingKey& dk, int
   std::vector<PlonkProof<MOS>> pfs;
   bool trailing = false;
   Error e;
+  const HostJobSettings s = HostJobSettings::from_env();
   if (transcript == SNARKV_HOST_TRANSCRIPT_POSEIDON_AUTO)
     transcript = poseidon_auto_route(n);
   if (transcript == SNARKV_HOST_TRANSCRIPT_EVM) {
-    e = read_all<MOS, EvmTranscript>(dk.svk, pr, insts, pbytes, strict, pfs, &trailing);
+    e = read_all<MOS, EvmTranscript>(dk.svk, pr, insts, pbytes, strict, s, pfs, &trailing);
   } else if (transcript == SNARKV_HOST_TRANSCRIPT_POSEIDON) {
-    e = read_all<MOS, PoseidonTranscript>(dk.svk, pr, insts, pbytes, strict, pfs, &trailing);
+    e = read_all<MOS, PoseidonTranscript>(dk.svk, pr, insts, pbytes, strict, s, pfs, &trailing);
   } else if (transcript == SNARKV_HOST_TRANSCRIPT_POSEIDON_DEVICE) {
     pfs.resize(n);
     e = Aggregator<MOS, PoseidonTranscriptOnDevice>::read_proofs_device_hashed(dk.svk, pr, insts, pbytes,
-                                                                               HostPool::get().size(), pfs);
+                                                                               HostPool::get().size(), pfs, s);
   } else {
     return arg_error("unknown transcript kind");
   }
@@ -150,10 +150,11 @@ int succinct_verify_batch(const PlonkProtocol& pr, const KzgDecidingKey& dk, int
 
 template <class MOS, class TR>
 int aggregate_run(const PlonkProtocol& pr, const KzgDecidingKey& dk, const std::vector<std::vector<std::vector<Fr>>>& insts,
-                  const std::vector<std::vector<uint8_t>>& proofs, unsigned threads, double* timings_ms, uint8_t* acc_out) {
+                  const std::vector<std::vector<uint8_t>>& proofs, unsigned threads, const HostJobSettings& s,
+                  double* timings_ms, uint8_t* acc_out) {
   AggregationTimings tm;
   KzgAccumulator acc;
-  Error e = Aggregator<MOS, TR>::aggregate_and_decide(dk, pr, insts, proofs, threads, &tm, &acc);
+  Error e = Aggregator<MOS, TR>::aggregate_and_decide(dk, pr, insts, proofs, threads, &tm, &acc, s);
   if (timings_ms) {
     timings_ms[0] = tm.read_proofs;
     timings_ms[1] = tm.fr_algebra;
@@ -224,13 +225,14 @@ int aggregate_mos(const PlonkProtocol& pr, const KzgDecidingKey& dk, int transcr
   std::vector<std::vector<uint8_t>> pbytes;
   wire::split_batch(instances, ilen, proofs, prlen, n, insts, pbytes);
   if (threads == 0) threads = HostPool::get().size();
+  const HostJobSettings s = HostJobSettings::from_env();  // ONE snapshot: the route and the job see the same knobs
   if (transcript == SNARKV_HOST_TRANSCRIPT_POSEIDON_AUTO)
-    transcript = poseidon_auto_route(n, true);
+    transcript = poseidon_auto_route(n, s.pipeline_min);
   switch (transcript) {
-    case SNARKV_HOST_TRANSCRIPT_EVM: return aggregate_run<MOS, EvmTranscript>(pr, dk, insts, pbytes, threads, timings_ms, acc_out);
-    case SNARKV_HOST_TRANSCRIPT_POSEIDON: return aggregate_run<MOS, PoseidonTranscript>(pr, dk, insts, pbytes, threads, timings_ms, acc_out);
+    case SNARKV_HOST_TRANSCRIPT_EVM: return aggregate_run<MOS, EvmTranscript>(pr, dk, insts, pbytes, threads, s, timings_ms, acc_out);
+    case SNARKV_HOST_TRANSCRIPT_POSEIDON: return aggregate_run<MOS, PoseidonTranscript>(pr, dk, insts, pbytes, threads, s, timings_ms, acc_out);
     case SNARKV_HOST_TRANSCRIPT_POSEIDON_DEVICE:
-      return aggregate_run<MOS, PoseidonTranscriptOnDevice>(pr, dk, insts, pbytes, threads, timings_ms, acc_out);
+      return aggregate_run<MOS, PoseidonTranscriptOnDevice>(pr, dk, insts, pbytes, threads, s, timings_ms, acc_out);
     default: return arg_error("unknown transcript kind");
   }
 }

@@ -743,25 +743,7 @@ static int aggregate_impl(int tkind, const uint8_t* protocol, size_t plen, const
     KzgDecidingKey dk(G1Affine::from_bytes(dk320), G2Affine::from_bytes(dk320 + 64), G2Affine::from_bytes(dk320 + 192));
     std::vector<std::vector<std::vector<Fr>>> insts;
     std::vector<std::vector<uint8_t>> pbytes;
-    const uint8_t* ip = instances;
-    const uint8_t* pp = proofs;
-    for (uint32_t i = 0; i < n; ++i) {
-      PReader rd{ip, instances + ilen};
-      uint32_t cols = rd.u32();
-      for (uint32_t c = 0; c < cols; ++c) {
-        uint32_t m = rd.u32();
-        rd.need(32 * (size_t)m);
-        rd.p += 32 * (size_t)m;
-      }
-      insts.push_back(parse_instances(ip, (size_t)(rd.p - ip)));
-      ip = rd.p;
-      if ((size_t)(proofs + prlen - pp) < 4) throw Panic("truncated proofs");
-      uint32_t len;
-      memcpy(&len, pp, 4);
-      if ((size_t)(proofs + prlen - pp) < 4 + (size_t)len) throw Panic("proof length runs past the buffer");
-      pbytes.emplace_back(pp + 4, pp + 4 + len);
-      pp += 4 + len;
-    }
+    wire::split_batch(instances, ilen, proofs, prlen, n, insts, pbytes);
     // tkind: 0 Keccak, 1 Poseidon hashed on the host, 2 Poseidon hashed on the device
     if (tkind == 0) return aggregate_run<MOS, EvmTranscript>(pr, dk, insts, pbytes, threads, timings_ms, acc_out128);
     if (tkind == 1) return aggregate_run<MOS, PoseidonTranscript>(pr, dk, insts, pbytes, threads, timings_ms, acc_out128);

@@ -1104,11 +1104,12 @@ class PoseidonTranscriptT : public Transcript {
     return Result<Fr>::Ok(s);
   }
   // The next n points sit side by side in the stream: decode (up to 8 of) them together -- one square-root chain for the
-  // group instead of one per point.  Skipped when the decodings come from elsewhere (a replay pass, device hints).
+  // group instead of one per point.  Skipped when the decodings come from elsewhere (a replay pass, device hints) and
+  // when switched off (`set_point_prefetch`).
   void prefetch_points(size_t n) override {
     pf_n_ = 0;
     const size_t first = point_offsets_.size();
-    if (next_decoded_ < n_decoded_in_ || first < n_hints_ || getenv("SNARKV_HOST_NO_POINT_PREFETCH")) return;
+    if (!point_prefetch_ || next_decoded_ < n_decoded_in_ || first < n_hints_) return;
     n = std::min<size_t>(std::min<size_t>(n, kPrefetchMax), (stream_.size() - std::min(pos_, stream_.size())) / 32);
     if (n < 2) return;
     for (size_t g = 0; g < n; g += 8) {  // groups of eight lanes
@@ -1187,6 +1188,7 @@ class PoseidonTranscriptT : public Transcript {
   G1Affine pf_pts_[kPrefetchMax];
   uint8_t pf_ok_[kPrefetchMax] = {};
   size_t pf_pos_ = 0, pf_n_ = 0;
+  bool point_prefetch_ = true;
   bool strict_hints_ = false;
   bool record_layout_ = false;
   uint32_t pending_src_ = 0xFFFFFFFFu;          // the source of the element(s) the next common_* call absorbs
@@ -1222,6 +1224,8 @@ class PoseidonTranscriptT : public Transcript {
   void set_point_hints(const uint8_t* pts64, const uint8_t* ok, size_t n, bool strict = false) {
     hint_pts_ = pts64, hint_ok_ = ok, n_hints_ = n, strict_hints_ = strict;
   }
+  // false: every point decoded on its own in scalar code (the A/B knob SNARKV_HOST_NO_POINT_PREFETCH, aggregation.hpp)
+  void set_point_prefetch(bool on) { point_prefetch_ = on; }
 };
 using PoseidonTranscript = PoseidonTranscriptT<Poseidon>;
 

@@ -1,9 +1,9 @@
 """Stress of the pipelined Poseidon aggregation job (host/aggregation.hpp aggregate_pipelined) on the GPU box: for `secs`
-seconds, random sub-batches of the 1 024-proof fixture with random chunk sizes / device-thread counts / first-chunk ramp,
-a third of them with one to three corrupted proofs at random places (a flipped evaluation bit, a broken point encoding, a
-scalar made non-canonical), each job run pipelined AND unpipelined: the two outcomes -- verdict + accumulator, or error code +
-text -- must be identical every time; several jobs from several application threads at once every tenth round.  A hang
-shows as the caller's timeout.
+seconds, random sub-batches of the 1 024-proof fixture with random chunk sizes (one-chunk and many-chunk jobs: one and
+two device threads), a third of them with one to three corrupted proofs at random places (a flipped evaluation bit, a
+broken point encoding, a scalar made non-canonical), each job run pipelined AND unpipelined: the two outcomes -- verdict +
+accumulator, or error code + text -- must be identical every time; several jobs from several application threads at once
+every tenth round.  A hang shows as the caller's timeout.
     python tests/tools/stress_pipeline.py [secs] [seed]"""
 import os
 import random
@@ -42,14 +42,9 @@ def main():
         except H.HostError as e:
             return ("err", e.code, str(e))
 
-    def setenv(pmin, chunk, dthreads, ramp):
+    def setenv(pmin, chunk):
         os.environ["SNARKV_HOST_PIPELINE_MIN"] = pmin
         os.environ["SNARKV_HOST_PIPELINE_CHUNK"] = str(chunk)
-        os.environ["SNARKV_HOST_PIPELINE_DEVICE_THREADS"] = str(dthreads)
-        if ramp:
-            os.environ.pop("SNARKV_HOST_PIPELINE_NO_RAMP", None)
-        else:
-            os.environ["SNARKV_HOST_PIPELINE_NO_RAMP"] = "1"
 
     t0, rounds, bad_rounds, concurrent = time.time(), 0, 0, 0
     while time.time() - t0 < secs:
@@ -73,10 +68,10 @@ def main():
                         pb[o + ln - 64 + k] = 0xFF
         pb = bytes(pb)
         threads = rng.choice([64, 64, 16, 3])
-        chunk, dthreads, ramp = rng.choice([1, 7, 32, 64, 100, 128, 256, 5000]), rng.choice([1, 2, 3]), rng.random() < 0.7
-        setenv("0", chunk, dthreads, ramp)
+        chunk = rng.choice([1, 7, 32, 64, 100, 128, 256, 5000])
+        setenv("0", chunk)
         ref = outcome(ib, pb, m, threads)
-        setenv("2", chunk, dthreads, ramp)
+        setenv("2", chunk)
         if rounds % 10 == 9:  # several application threads at once, each with its own copy of the job
             concurrent += 1
             got = [None] * 4
@@ -89,8 +84,8 @@ def main():
             got = [outcome(ib, pb, m, threads)]
         for g in got:
             if g != ref:
-                print("MISMATCH: lo %d m %d threads %d chunk %d dthreads %d ramp %s\n  unpipelined %r\n  pipelined   %r"
-                      % (lo, m, threads, chunk, dthreads, ramp, ref[:2], g[:2]))
+                print("MISMATCH: lo %d m %d threads %d chunk %d\n  unpipelined %r\n  pipelined   %r"
+                      % (lo, m, threads, chunk, ref[:2], g[:2]))
                 sys.exit(1)
         rounds += 1
     print("pipeline stress ok: %d rounds (%d with corrupted proofs, %d with four jobs at once), %.0f s" % (rounds, bad_rounds, concurrent, time.time() - t0))

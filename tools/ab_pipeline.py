@@ -27,7 +27,6 @@ def main():
     ap.add_argument("--calls", type=int, default=25)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--chunks", default="64,128,256")
-    ap.add_argument("--dthreads", default="1,2")
     ap.add_argument("--sizes", default="1024")
     ap.add_argument("--fixture", default="bench_plonk_gwc19_poseidon_1024.bin")
     ap.add_argument("--mos", type=int, default=0)
@@ -53,13 +52,12 @@ def main():
             off += 4 + 32 * int.from_bytes(inst[off:off + 4], "little")
         ioffs.append(off)
     # (name, transcript route, environment of the call; None = unset)
-    base = {"SNARKV_HOST_PIPELINE_MIN": None, "SNARKV_HOST_PIPELINE_CHUNK": None, "SNARKV_HOST_PIPELINE_DEVICE_THREADS": None}
+    base = {"SNARKV_HOST_PIPELINE_MIN": None, "SNARKV_HOST_PIPELINE_CHUNK": None}
     variants = [("host route, pipeline off", 1, dict(base, SNARKV_HOST_PIPELINE_MIN="0")),
                 ("device route (no pipeline exists)", 2, dict(base, SNARKV_HOST_PIPELINE_MIN="0"))]
     for c in args.chunks.split(","):
-        for d in args.dthreads.split(","):
-            variants.append(("host route, pipelined, chunk %s, %s device thread(s)" % (c, d), 1,
-                             dict(base, SNARKV_HOST_PIPELINE_MIN="2", SNARKV_HOST_PIPELINE_CHUNK=c, SNARKV_HOST_PIPELINE_DEVICE_THREADS=d)))
+        variants.append(("host route, pipelined, chunk %s" % c, 1,
+                         dict(base, SNARKV_HOST_PIPELINE_MIN="2", SNARKV_HOST_PIPELINE_CHUNK=c)))
     variants.append(("auto route (as shipped)", 3, dict(base)))
     for m in [int(x) for x in args.sizes.split(",")]:
         m = min(m, fx["n"])
