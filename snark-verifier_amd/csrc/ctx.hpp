@@ -45,8 +45,9 @@ enum Slot {
   SLOT_CURSOR,
   SLOT_BLOCKSUMS,
   SLOT_ENTRIES,
-  SLOT_SEG_IDS,
-  SLOT_SEG_PARTIALS,
+  SLOT_PIECES,       // S5 piece descriptors (uint4)
+  SLOT_SPLIT_PARTS,  // partials of the pieces of split buckets
+  SLOT_PIECE_HIST,   // S5 length x workgroup histogram
   SLOT_BUCKETS,
   SLOT_CHUNK_PARTIALS,
   SLOT_WINDOW_SUMS,
@@ -56,7 +57,7 @@ enum Slot {
   SLOT_SORT_TMP,
   SLOT_SHIFTED,
   SLOT_GLV,
-  SLOT_BIG_LIST,
+  SLOT_FIX_LISTS,    // k_fixup's lists: small split | big split | degenerate buckets
   SLOT_MISC2,
   SLOT_TERM_CHAIN,
   SLOT_TERM_MAGS,

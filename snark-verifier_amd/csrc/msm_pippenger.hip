@@ -20,12 +20,17 @@
 //   S4 k_sort_level2     one workgroup per (window, high bits): LDS counting
 //                        sort by the low digit bits; emits the bucket-sorted
 //                        stream plus per-bucket counts/offsets
-//   P4 k_accumulate      every lane owns a FIXED-LENGTH run of the sorted
-//                        stream (kRun entries) -- load-balanced whatever the
-//                        scalar distribution -- and emits a head partial, a
-//                        tail partial and complete interior buckets
+//   S5 k_piece_hist/emit a bucket becomes pieces of at most L entries (L = the
+//                        cap: above every bucket of a uniform 2^20 MSM), and
+//                        the pieces are counting-sorted by length, longest first
+//   P4 k_accumulate      every lane owns ONE piece, the lanes of a wavefront
+//                        pieces of equal length: a wave-uniform first copy and
+//                        trip count, one store per lane -- a whole bucket, or
+//                        the partial of a split one
 //                        (the `buckets[d-1].add_assign(base)` of msm.rs:291-296)
-//   P5 k_combine         per bucket: stitch the partials of the runs it spans
+//   P5 k_fixup           the buckets P4 left: split buckets (stitch the
+//                        partials) and degenerate ones (careful redo); it
+//                        walks device-side lists, empty for uniform scalars
 //   P6 k_bucket_reduce   running-sum trick of msm.rs:298-302, chunked so that
 //                        >= 64 K lanes work; the chunk weights (chunk index x
 //                        chunk sum) come from one suffix scan over the 64 lanes
@@ -40,7 +45,7 @@
 //                        projective partial for the multi-GPU fold.
 //
 // Field arithmetic is the lazy 9x29-bit form (fq29.h, g1_29.h): branch-free
-// "fast" adders, one degenerate-ZZ check per run and a careful redo only when an
+// "fast" adders, one degenerate-ZZ check per bucket and a careful redo only when an
 // exceptional case (P = +-Q, identity) was met.
 //
 // MFMA is deliberately unused: there is no dense contraction, the work is
@@ -63,7 +68,7 @@
 namespace snarkv {
 
 #ifndef SNARKV_KRUN
-#define SNARKV_KRUN 64
+#define SNARKV_KRUN 128  // piece cap of one MSM at a time once the launch is large enough (latency_run_length)
 #endif
 #ifndef SNARKV_KCHUNK
 #define SNARKV_KCHUNK 8
@@ -112,23 +117,18 @@ namespace snarkv {
 constexpr int kHalves = SNARKV_GLV ? 2 : 1;       // virtual points per input point: P and phi(P), or P alone
 constexpr int kDigitWords = SNARKV_GLV ? 4 : 8;   // words of a digit source: a 127-bit GLV half / the 255-bit scalar
 constexpr int kDigitBits = 32 * kDigitWords;      // W * c covers this: magnitude bits + the recoding carry
-constexpr int kRun = SNARKV_KRUN;      // P4: entries per lane (a context with the throughput hint uses kRunThroughput)
+constexpr int kRun = SNARKV_KRUN;      // S5/P4: piece cap (a context with the throughput hint uses kRunThroughput)
 #ifndef SNARKV_KRUN_THROUGHPUT
-#define SNARKV_KRUN_THROUGHPUT 96
+#define SNARKV_KRUN_THROUGHPUT 128
 #endif
-// Longer runs = fewer head/tail partials for k_combine and fewer bucket-head entries that occupy an addition slot without
-// adding (interleaved A/B, profiles/r02_ab_krun*.txt: 64 -> 96 entries = -3.5 % per MSM with several MSMs in flight),
-// but 2^24 entries / 96 / 64 = 2 731 wavefronts no longer fill the 3 072 slots of the machine: one MSM alone runs
-// k_accumulate 1.11 -> 1.26 ms.  So the run length follows the context's hint (snarkv_ctx_set_throughput_hint).
+// The cap on a piece (entries per k_accumulate lane).  A bucket of a uniform 2^20 MSM at c = 16 holds Poisson(64)
+// entries, never more than ~110 over its 2^18 buckets: with a cap of 128 every bucket is ONE piece, the wave count is the
+// bucket count / 64 (4 096), and there is nothing to stitch.  Skewed scalars still split into full-length pieces.
 constexpr int kRunThroughput = SNARKV_KRUN_THROUGHPUT;
 constexpr int kChunk = SNARKV_KCHUNK;  // P6: buckets per lane
 constexpr uint32_t kSortCap = 7168;     // S4: items a workgroup sorts entirely in LDS (56 KiB of the 64 KiB dynamic limit)
 constexpr uint32_t kSortTarget = 3072;  // S1: average items per (window, high bits) key
 constexpr uint32_t kMaxKeys = 16384;    // S1: LDS counters per tile workgroup (64 KiB)
-constexpr uint32_t kBigSpan = 24;       // P5: buckets spanning more runs go to the cooperative kernel
-constexpr uint32_t kBigGrid = 8192;  // P5: workgroups of k_combine_big (they walk the list of oversized buckets; 128 measured level)
-constexpr uint32_t kMaxBig = 8192;   // S1: (window, high bits) keys per window <= 128
-constexpr uint32_t kNoBucket = 0xFFFFFFFFu;
 
 struct PipParams {
   uint32_t n;
@@ -143,7 +143,7 @@ struct PipParams {
   uint32_t tile;   // scalars per tile workgroup
   uint32_t mstride;  // row stride of the key x tile matrix (odd: no power-of-two channel aliasing)
   uint32_t w0;       // index of the first window held (bucket-sharded reduce of a window range; 0 otherwise)
-  uint32_t krun;     // entries per run (kRun, or kRunThroughput on a context with the throughput hint)
+  uint32_t krun;     // piece cap L: entries per k_accumulate lane at most (latency_run_length, or kRunThroughput)
   uint32_t wper;     // batched tail over several MSMs' grids laid end to end: windows per MSM (0: one MSM)
   uint32_t chunk_log2;  // P6: log2 of the buckets per k_bucket_reduce lane (kLog2Chunk; larger in a batched tail)
   uint32_t mont;     // P0: 1 = scalars and points arrive in halo2curves' in-memory form (a * 2^256 mod r / mod p): SNARKV_FLAG_MONTGOMERY
@@ -535,8 +535,6 @@ __global__ void __launch_bounds__(SNARKV_L2_THREADS) SNARKV_LEVEL2_ATTR
     hist[k] = run;  // becomes the cursor (slice-relative)
     run += cnt;
   }
-  // the big-bucket counter of k_combine (a per-MSM fill done by the kernel that runs before its user, not a memset)
-  if (key == p.nkeys - 1 && threadIdx.x == 0) misc[4] = 0u;
   __syncthreads();
   if (fast) {
 #pragma unroll
@@ -554,18 +552,96 @@ __global__ void __launch_bounds__(SNARKV_L2_THREADS) SNARKV_LEVEL2_ATTR
   }
 }
 
+// --------------------------------------------------------------- S5
+// Piece schedule.  A bucket of cnt entries becomes ceil(cnt / L) PIECES of at most L = p.krun consecutive sorted entries
+// (an empty bucket one piece of length 0), and the pieces are counting-sorted by length, longest first, so that the 64
+// lanes of a k_accumulate wavefront own pieces of (nearly) equal length: every lane starts its bucket at the same step,
+// the trip count is wave-uniform and a lane stores its result once.  With L above the largest bucket (uniform scalars,
+// the throughput cap) every piece is a whole bucket and nothing is left to stitch.
+// The histogram is a matrix of kSchedRows(L) rows x nsb columns (one column per workgroup of kSchedBuckets buckets):
+//   row L - len   pieces of length len (0 <= len <= L)
+//   row L + 1     split buckets of at most kBigPieces pieces  (the fix-up's lane-per-bucket list)
+//   row L + 2     split buckets of more pieces                (the fix-up's cooperative list)
+// scanned row-major by the k_scan_* kernels: row r, column blk = where that workgroup's items of row r go.
+// Partials of split pieces live in two slot regions indexed by entry positions, so that they need no allocation: the
+// full pieces of a split bucket at o (entries o + j L) in slot o / L + j (each full piece holds exactly one entry index
+// = L - 1 mod L, no two pieces share a slot), its remainder piece in slot o / L of the second region (two split buckets
+// start more than L entries apart).
+constexpr uint32_t kSchedBuckets = 2048;  // buckets per schedule workgroup (256 lanes x 8)
+constexpr uint32_t kMaxPiece = 256;       // largest cap (LDS rows of the schedule)
+constexpr uint32_t kBigPieces = 24;       // split buckets of more pieces are stitched by a whole workgroup
+constexpr uint32_t kFixGrid = 1024;       // most workgroups of k_fixup (it walks device-side lists)
+constexpr uint32_t kPieceWhole = 0x80000000u;  // descriptor .y: bit 31 = the piece is its whole bucket, low bits = length
+__host__ __device__ constexpr uint32_t sched_rows(uint32_t L) { return L + 3; }
+
+__global__ void __launch_bounds__(256)
+    k_piece_hist(const uint32_t* __restrict__ counts, PipParams p, uint32_t nsb, uint32_t* __restrict__ H,
+                 uint32_t* __restrict__ misc) {
+  SNARKV_RAISE_PRIO();
+  __shared__ uint32_t hist[sched_rows(kMaxPiece)];
+  const uint32_t L = p.krun, rows = sched_rows(L);
+  for (uint32_t k = threadIdx.x; k < rows; k += blockDim.x) hist[k] = 0u;
+  // the fix-up's degenerate-bucket counter (a per-MSM fill done by a kernel that runs before its user, not a memset)
+  if (blockIdx.x == 0 && threadIdx.x == 0) misc[4] = 0u;
+  __syncthreads();
+  const uint32_t lo = blockIdx.x * kSchedBuckets, hi = lo + kSchedBuckets < p.nb ? lo + kSchedBuckets : p.nb;
+  for (uint32_t b = lo + threadIdx.x; b < hi; b += blockDim.x) {
+    const uint32_t c = counts[b];
+    if (c <= L) {
+      atomicAdd(&hist[L - c], 1u);
+      continue;
+    }
+    const uint32_t nfull = c / L, r = c - nfull * L;
+    atomicAdd(&hist[0], nfull);
+    if (r) atomicAdd(&hist[L - r], 1u);
+    atomicAdd(&hist[nfull + (r ? 1u : 0u) > kBigPieces ? L + 2 : L + 1], 1u);
+  }
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < rows; k += blockDim.x) H[(size_t)k * nsb + blockIdx.x] = hist[k];
+}
+
+// The same walk over the buckets, after the scan: one descriptor {first entry, length | whole, bucket, partial slot}
+// per piece at its sorted position, and the split buckets into the fix-up's lists.
+__global__ void __launch_bounds__(256)
+    k_piece_emit(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets, PipParams p, uint32_t nsb,
+                 const uint32_t* __restrict__ H, uint32_t split_slots, uint4* __restrict__ pieces,
+                 uint32_t* __restrict__ small_list, uint32_t* __restrict__ big_list) {
+  SNARKV_RAISE_PRIO();
+  __shared__ uint32_t cur[sched_rows(kMaxPiece)];
+  const uint32_t L = p.krun, rows = sched_rows(L);
+  for (uint32_t k = threadIdx.x; k < rows; k += blockDim.x) cur[k] = H[(size_t)k * nsb + blockIdx.x];
+  const uint32_t small0 = H[(size_t)(L + 1) * nsb], big0 = H[(size_t)(L + 2) * nsb];  // where the lists' rows start
+  __syncthreads();
+  const uint32_t lo = blockIdx.x * kSchedBuckets, hi = lo + kSchedBuckets < p.nb ? lo + kSchedBuckets : p.nb;
+  for (uint32_t b = lo + threadIdx.x; b < hi; b += blockDim.x) {
+    const uint32_t c = counts[b], o = offsets[b];
+    if (c <= L) {  // the whole bucket (length 0: k_accumulate stores the identity)
+      pieces[atomicAdd(&cur[L - c], 1u)] = make_uint4(o, c | kPieceWhole, b, 0u);
+      continue;
+    }
+    const uint32_t nfull = c / L, r = c - nfull * L, slot = o / L;
+    const uint32_t at = atomicAdd(&cur[0], nfull);
+    for (uint32_t j = 0; j < nfull; ++j) pieces[at + j] = make_uint4(o + j * L, L, b, slot + j);
+    if (r) pieces[atomicAdd(&cur[L - r], 1u)] = make_uint4(o + nfull * L, r, b, split_slots + slot);
+    if (nfull + (r ? 1u : 0u) > kBigPieces) big_list[atomicAdd(&cur[L + 2], 1u) - big0] = b;
+    else small_list[atomicAdd(&cur[L + 1], 1u) - small0] = b;
+  }
+}
+
 // --------------------------------------------------------------- P4
-// One lane = one run of kRun consecutive sorted entries.  Emits the partial of
-// the run's first bucket (head), of its last bucket if different (tail), and
-// writes complete interior buckets straight to `buckets`.  Branch-free adders
-// and NO degeneracy test here: a flush is a plain store, so the lanes of a wave
-// (which change bucket at different iterations) never wait for each other's
-// checks.  P5 tests every bucket once and redoes the rare bad one carefully.
+// One lane = one piece (descriptor t of the length-sorted schedule).  The wavefront's trip count is the longest piece
+// among its lanes (lane 0's, by the sort), clamped to the cap by construction: a bad descriptor can neither make a lane
+// loop longer nor make it read or write outside the stream, the grid or the partial slots.  Step 0 is a wave-uniform
+// copy of the first point; every later step is one branch-free mixed addition, masked off for lanes whose piece is
+// shorter.  A whole bucket gets its ONE degeneracy test here (a fast addition that met P = +-Q, or a sum that is the
+// identity, leaves ZZ = 0 mod p, sticky) and is stored, or handed to k_fixup's degenerate list; a piece of a split
+// bucket stores its partial.
 // An entry is {bucket id, point index | sign << 31}; the point is gathered from the Montgomery table (G1Packed: ONE
 // 64-byte sector) and its 9 x 29-bit limbs are cut out of the 256-bit words in registers.
 // (Measured and removed, round 3: a batched-affine pair level in front of this kernel, in two forms -- bit-exact, 25-37 %
 // slower per MSM because its passes are random 64-byte gathers at 3.6-3.8 TB/s: profiles/r03_ab_pair_tree.txt, git tag
-// exp/pair-tree.)
+// exp/pair-tree.  Round 7: lanes on FIXED-LENGTH runs of the stream with head / tail partials stitched by k_combine,
+// git tag exp/fixed-runs.)
 constexpr uint32_t kEntryIdx = 0x7FFFFFFFu;  // point index bits of an entry's .y (bit 31 = negate)
 
 __device__ __forceinline__ G1Affine29 entry_point(const G1Packed& k, uint32_t y) {
@@ -574,75 +650,70 @@ __device__ __forceinline__ G1Affine29 entry_point(const G1Packed& k, uint32_t y)
   return p;
 }
 
-template <int RUN>
 __global__ void __launch_bounds__(64, SNARKV_ACC_WAVES)
-    k_accumulate(const uint2* __restrict__ entries, const uint32_t* __restrict__ total_ptr,
-                 const G1Packed* __restrict__ pts, G1Xyzz29* __restrict__ buckets, uint32_t* __restrict__ seg_ids,
-                 G1Xyzz29* __restrict__ seg_parts) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    k_accumulate(const uint4* __restrict__ pieces, const uint32_t* __restrict__ npieces_ptr,
+                 const uint32_t* __restrict__ total_ptr, const uint2* __restrict__ entries,
+                 const G1Packed* __restrict__ pts, G1Xyzz29* __restrict__ buckets, G1Xyzz29* __restrict__ parts,
+                 uint32_t part_slots, uint32_t* __restrict__ deg_count, uint32_t* __restrict__ deg_list, PipParams p) {
+  const uint32_t npieces = *npieces_ptr;
+  if (blockIdx.x * 64u >= npieces) return;  // the launch is sized by a host bound: whole idle wavefronts leave
+  const uint32_t t = blockIdx.x * 64u + threadIdx.x;
   const uint32_t stop = *total_ptr;
-  const uint64_t begin64 = (uint64_t)t * RUN;
-  if (begin64 >= stop) return;
-  const uint32_t begin = (uint32_t)begin64;
-  const uint32_t end = (stop - begin > (uint32_t)RUN) ? begin + RUN : stop;
-  const size_t slot = t;
-  uint32_t cur = entries[begin].x;
-  bool first = true, fresh = true;
-  G1Xyzz29 acc = xyzz29_identity();
-  // a bucket's part of the run is finished: head partial, or complete interior bucket
-  auto flush = [&]() {
-    if (first) {
-      seg_ids[2 * slot] = cur;
-      seg_parts[2 * slot] = acc;
-      first = false;
-    } else {
-      buckets[cur] = acc;  // complete interior bucket
-    }
+  uint4 d = make_uint4(0u, 0u, 0u, 0u);
+  if (t < npieces) d = pieces[t];
+  const uint32_t first = d.x, b = d.z;
+  uint32_t len = d.y & ~kPieceWhole;
+  const bool whole = (d.y & kPieceWhole) != 0;
+  const bool valid = t < npieces && b < p.nb && len <= p.krun && first <= stop && len <= stop - first &&
+                     (whole || d.w < part_slots);
+  if (!valid) len = 0;
+  uint32_t trip = len;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) trip = max(trip, (uint32_t)__shfl_xor((int)trip, off, 64));
+  trip = __builtin_amdgcn_readfirstlane(trip);  // wave-uniform, <= p.krun
+  // software pipeline: the (entry -> point) gather of step e+1 is issued before the ~2 200-instruction mixed addition
+  // of step e; two steps per trip with ping-pong registers, so the prefetched point is consumed where it was loaded.
+  // The gathers are UNCONDITIONAL (a lane past its piece re-reads its last entry; an empty one entry 0, the point index
+  // clamped to the table): a load under a divergent branch makes the compiler wait for every outstanding load before
+  // the next addition, i.e. exposes the full gather latency at every step.
+  const uint32_t last = len ? first + len - 1 : 0u, nvirt = (uint32_t)kHalves * p.n;
+  uint2 ent0, ent1;
+  G1Packed p0, p1;
+  auto fetch = [&](uint32_t e, uint2& ent, G1Packed& pk) {
+    ent = entries[min(first + e, last)];
+    pk = pts[min(ent.y & kEntryIdx, nvirt - 1u)];
   };
-  // software pipeline: the (entry -> point) gather of step e+1 is issued before the ~2 200-instruction
-  // mixed addition of step e; two steps per trip with ping-pong registers, so the prefetched point is
-  // consumed where it was loaded instead of being copied (18 moves per entry)
-  auto step = [&](const uint2& ent, const G1Packed& pk) {
-    if (ent.x != cur) {
-      flush();
-      cur = ent.x;
-      fresh = true;
-    }
-    G1Affine29 p = entry_point(pk, ent.y);
-    if (fresh) {
-      acc.x = p.x;
-      acc.y = p.y;
+  G1Xyzz29 acc = xyzz29_identity();
+  fetch(0, ent0, p0);
+  if (trip) {
+    fetch(1, ent1, p1);
+    if (len) {
+      const G1Affine29 q = entry_point(p0, ent0.y);
+      acc.x = q.x;
+      acc.y = q.y;
       acc.zz = fq29_one();
       acc.zzz = fq29_one();
-      fresh = false;
-    } else {
-      xyzz29_madd_fast(acc, p);
-    }
-  };
-  uint2 ent0 = entries[begin], ent1 = ent0;
-  G1Packed p0 = pts[ent0.y & kEntryIdx], p1 = p0;
-#pragma unroll 1
-  for (uint32_t e = begin; e < end; e += 2) {
-    if (e + 1 < end) {
-      ent1 = entries[e + 1];
-      p1 = pts[ent1.y & kEntryIdx];
-    }
-    step(ent0, p0);
-    if (e + 1 < end) {
-      if (e + 2 < end) {
-        ent0 = entries[e + 2];
-        p0 = pts[ent0.y & kEntryIdx];
-      }
-      step(ent1, p1);
     }
   }
-  if (first) {
-    seg_ids[2 * slot] = cur;
-    seg_parts[2 * slot] = acc;
-    seg_ids[2 * slot + 1] = kNoBucket;
+#pragma unroll 1
+  for (uint32_t e = 1; e < trip; e += 2) {
+    fetch(e + 1, ent0, p0);
+    if (e < len) xyzz29_madd_fast(acc, entry_point(p1, ent1.y));
+    if (e + 1 < trip) {
+      fetch(e + 2, ent1, p1);
+      if (e + 1 < len) xyzz29_madd_fast(acc, entry_point(p0, ent0.y));
+    }
+  }
+  if (!valid) return;
+  if (!whole) {
+    parts[d.w] = acc;
+  } else if (len == 0) {
+    buckets[b] = xyzz29_identity();  // empty bucket: stored here, the grid is never memset
+  } else if (xyzz29_is_degenerate(acc)) {
+    const uint32_t i = atomicAdd(deg_count, 1u);  // rare: duplicate / opposite points in one bucket
+    if (i < p.nb) deg_list[i] = b;
   } else {
-    seg_ids[2 * slot + 1] = cur;
-    seg_parts[2 * slot + 1] = acc;
+    buckets[b] = acc;
   }
 }
 
@@ -663,96 +734,46 @@ __device__ __noinline__ void bucket_from_entries_careful(const uint2* __restrict
   *out = sanitize ? xyzz29_sanitize(acc) : acc;
 }
 
-// the run slots [s0, s1] that hold partials of a bucket whose entries are entries[o, o + cnt): runs are cut every
-// p.krun entries from the start of the sorted stream
-__device__ __forceinline__ void run_span(const PipParams& p, uint32_t o, uint32_t cnt, size_t& s0, size_t& s1) {
-  s0 = o / p.krun;
-  s1 = (o + cnt - 1) / p.krun;
+// partial slot of piece j of a split bucket whose entries start at o (S5)
+__device__ __forceinline__ uint32_t piece_slot(uint32_t o, uint32_t j, uint32_t nfull, uint32_t L, uint32_t split_slots) {
+  return j < nfull ? o / L + j : split_slots + o / L;
 }
 
-// One lane per bucket: stitch the partials of the runs it spans (or pick up the
-// value P4 wrote for an interior bucket), then the ONE degeneracy test of the
-// bucket: a fast addition that met an exceptional case left ZZ = 0 (mod p)
-// (sticky through every later addition; an exact-zero ZZ partial is the same
-// signal, a run never legitimately produces the identity).
-// (Measured and removed, round 3: run-boundary lanes for the buckets that span exactly two runs -- level in a batch,
-// 13 % slower alone: profiles/r03_ab_combine_pack.txt, git tag exp/combine-pairs.)
-__global__ void __launch_bounds__(64)
-    k_combine(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets, PipParams p,
-              const uint2* __restrict__ entries, const G1Packed* __restrict__ pts,
-              const uint32_t* __restrict__ seg_ids, const G1Xyzz29* __restrict__ seg_parts,
-              G1Xyzz29* __restrict__ buckets, uint32_t* __restrict__ big_count, uint32_t* __restrict__ big_list) {
-  SNARKV_RAISE_PRIO();
-  uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= p.nb) return;
-  uint32_t cnt = counts[b];
-  if (cnt == 0) {  // empty bucket = the identity (all-zero ZZ): stored here, the grid is never memset
-    buckets[b] = xyzz29_identity();
-    return;
-  }
-  uint32_t o = offsets[b];
-  size_t s0, s1;
-  run_span(p, o, cnt, s0, s1);
-  if (s1 - s0 >= kBigSpan) {  // skewed scalars: hand the bucket to k_combine_big
-    uint32_t slot = atomicAdd(big_count, 1u);
-    if (slot < kMaxBig) {
-      big_list[slot] = b;
-      return;
-    }
-  }
-  G1Xyzz29 acc = xyzz29_identity();
-  bool touched = false, bad = false;
-  for (size_t s = s0; s <= s1; ++s) {
-    for (int h = 0; h < 2; ++h) {
-      if (seg_ids[2 * s + h] == b) {
-        G1Xyzz29 part = seg_parts[2 * s + h];
-        bad = bad || xyzz29_is_identity(part);
-        xyzz29_add_skipid_fast(acc, part, bad);
-        touched = true;
-      }
-    }
-  }
-  if (!touched) acc = buckets[b];  // interior to one run: P4 stored it
-  bad = bad || xyzz29_is_degenerate(acc);
-  if (bad) bucket_from_entries_careful(entries, pts, o, cnt, 0, 1, true, &buckets[b]);
-  else if (touched) buckets[b] = acc;
-}
-
-// Buckets that span many runs (skewed scalar distributions: e.g. all scalars
-// equal puts n entries into one bucket per window): one 256-lane workgroup per
-// bucket, lane-strided careful adds + LDS tree.  If any partial is degenerate
-// the whole bucket is recomputed carefully from its entries.
+// The buckets k_accumulate could not finish, from three device-side lists (all empty for uniform scalars):
+//   big     split buckets of more than kBigPieces pieces (skewed scalars: e.g. all scalars equal put n entries into one
+//           bucket per window): one 256-lane workgroup each, lane-strided careful adds of the partials + LDS tree; if
+//           any partial is degenerate the bucket is recomputed carefully from its entries, lane-strided
+//   small   the other split buckets, one lane each: stitch the partials with fast adders, ONE degeneracy test
+//   degen.  whole buckets that failed k_accumulate's test, one lane each: recomputed carefully from the entries
+// The grid is a host bound (at most kFixGrid workgroups) and walks the lists.
 __global__ void __launch_bounds__(256)
-    k_combine_big(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets,
-                  const uint2* __restrict__ entries, const G1Packed* __restrict__ pts,
-                  const uint32_t* __restrict__ seg_ids, const G1Xyzz29* __restrict__ seg_parts,
-                  G1Xyzz29* __restrict__ buckets, const uint32_t* __restrict__ big_count,
-                  const uint32_t* __restrict__ big_list, PipParams p) {
+    k_fixup(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets, const uint2* __restrict__ entries,
+            const G1Packed* __restrict__ pts, const G1Xyzz29* __restrict__ parts, uint32_t split_slots,
+            G1Xyzz29* __restrict__ buckets, const uint32_t* __restrict__ H, uint32_t nsb, const uint32_t* __restrict__ misc,
+            const uint32_t* __restrict__ small_list, const uint32_t* __restrict__ big_list,
+            const uint32_t* __restrict__ deg_list, PipParams p) {
   SNARKV_RAISE_PRIO();
   __shared__ G1Xyzz29 sh[256];
   __shared__ int any_bad;
-  uint32_t nbig = *big_count < kMaxBig ? *big_count : kMaxBig;
-  // the grid walks the list (normally empty: uniform scalars have no bucket over kBigSpan runs); capping the grid at
-  // 128 workgroups was measured level (one MSM alone -0.5 %, the batch +0.9 %)
+  const uint32_t L = p.krun;
+  const uint32_t small0 = H[(size_t)(L + 1) * nsb], big0 = H[(size_t)(L + 2) * nsb];
+  const uint32_t nsmall = big0 - small0, nbig = misc[6] - big0;
+  const uint32_t ndeg = misc[4] < p.nb ? misc[4] : p.nb;
   for (uint32_t bi = blockIdx.x; bi < nbig; bi += gridDim.x) {
-    uint32_t b = big_list[bi];
-    uint32_t o = offsets[b], cnt = counts[b];
-    size_t s0, s1;
-    run_span(p, o, cnt, s0, s1);
+    const uint32_t b = big_list[bi];
+    const uint32_t o = offsets[b], cnt = counts[b], nfull = cnt / L, np = nfull + (cnt % L ? 1u : 0u);
     if (threadIdx.x == 0) any_bad = 0;
     __syncthreads();
     G1Xyzz29 acc = xyzz29_identity();
     bool bad = false;
-    for (size_t s = s0 + threadIdx.x; s <= s1; s += 256)
-      for (int h = 0; h < 2; ++h)
-        if (seg_ids[2 * s + h] == b) {
-          G1Xyzz29 part = seg_parts[2 * s + h];
-          bad = bad || xyzz29_is_degenerate(part);
-          xyzz29_add_careful(acc, part);
-        }
+    for (uint32_t j = threadIdx.x; j < np; j += blockDim.x) {
+      const G1Xyzz29 part = parts[piece_slot(o, j, nfull, L, split_slots)];
+      bad = bad || xyzz29_is_degenerate(part);
+      xyzz29_add_careful(acc, part);
+    }
     if (bad) atomicOr(&any_bad, 1);
     __syncthreads();
-    if (any_bad) bucket_from_entries_careful(entries, pts, o, cnt, threadIdx.x, 256, false, &sh[threadIdx.x]);
+    if (any_bad) bucket_from_entries_careful(entries, pts, o, cnt, threadIdx.x, blockDim.x, false, &sh[threadIdx.x]);
     else sh[threadIdx.x] = acc;
     __syncthreads();
     for (uint32_t st = 128; st >= 1; st >>= 1) {
@@ -765,6 +786,24 @@ __global__ void __launch_bounds__(256)
     }
     if (threadIdx.x == 0) buckets[b] = xyzz29_sanitize(sh[0]);
     __syncthreads();  // sh / any_bad are reused by the next bucket of this workgroup
+  }
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nsmall + ndeg; i += gridDim.x * blockDim.x) {
+    const bool split = i < nsmall;
+    const uint32_t b = split ? small_list[i] : deg_list[i - nsmall];
+    const uint32_t o = offsets[b], cnt = counts[b];
+    bool bad = !split;
+    G1Xyzz29 acc = xyzz29_identity();
+    if (split) {
+      const uint32_t nfull = cnt / L, np = nfull + (cnt % L ? 1u : 0u);
+      for (uint32_t j = 0; j < np; ++j) {
+        const G1Xyzz29 part = parts[piece_slot(o, j, nfull, L, split_slots)];
+        bad = bad || xyzz29_is_identity(part);
+        xyzz29_add_skipid_fast(acc, part, bad);
+      }
+      bad = bad || xyzz29_is_degenerate(acc);
+    }
+    if (bad) bucket_from_entries_careful(entries, pts, o, cnt, 0, 1, true, &buckets[b]);
+    else buckets[b] = acc;
   }
 }
 
@@ -1018,19 +1057,22 @@ static int balance_window_bits(int c) {
   return (kDigitBits + W - 1) / W;
 }
 
-// Entries per k_accumulate lane for ONE MSM at a time.  A lane is a serial chain (~5 us per entry when the SIMD is shared
-// three ways), so below ~2^20 points 64-entry runs leave the machine to a few hundred wavefronts that each run for
-// 0.33 ms whatever n is (measured: k_accumulate 0.33 ms at 2^16 AND 2^17 points).  Shorter runs = more lanes, at the price
-// of more head / tail partials for k_combine: the shortest of 16 / 32 / 64 that keeps the launch within ~1.5 rounds of
-// the 3 072 wave slots, and 32 rather than 16 when even 16 would not fill two thirds of them.  Measured single-MSM
-// latency at 2^16 / 2^17 / 2^18 / 2^19 points: 1.15 / 1.19 / 1.35 / 1.66 -> 1.03 / 1.13 / 1.14 / 1.46 ms
-// (profiles/r02_sweep_run_length.txt).  With several MSMs in flight (hint, batch) the long runs stay.
+// Piece cap for ONE MSM at a time.  A lane is a serial chain (~5 us per entry when the SIMD is shared three ways), so
+// below ~2^20 points whole buckets leave the machine to a few hundred wavefronts that each run for 0.33 ms whatever n is
+// (measured with 64-entry runs: k_accumulate 0.33 ms at 2^16 AND 2^17 points).  A shorter cap = more lanes, at the price
+// of split buckets whose partials k_fixup stitches: 16 or 32 when the stream cut that fine keeps the launch within ~1.5
+// rounds of the 3 072 wave slots, and 32 rather than 16 when even 16 would not fill two thirds of them.  Measured
+// single-MSM latency at 2^16 / 2^17 / 2^18 / 2^19 points with runs of that length: 1.15 / 1.19 / 1.35 / 1.66 -> 1.03 /
+// 1.13 / 1.14 / 1.46 ms (profiles/r02_sweep_run_length.txt).  Larger launches take the cap kRun: whole buckets.  With
+// several MSMs in flight (hint, batch) the cap is kRunThroughput.
 static uint32_t latency_run_length(uint64_t entries) {
   auto waves = [&](uint64_t run) { return (entries + 64 * run - 1) / (64 * run); };
   if (waves(16) <= 4608) return waves(16) >= 2048 ? 16u : 32u;
   if (waves(32) <= 4608) return 32u;
   return (uint32_t)kRun;
 }
+static_assert(kRun >= 32 && kRun <= (int)kMaxPiece && kRunThroughput >= 16 && kRunThroughput <= (int)kMaxPiece,
+              "piece caps fit the schedule's LDS rows");
 
 int launch_msm_pippenger(snarkv_ctx* ctx, const void* d_scalars, const void* d_points, size_t n, int window_bits,
                          void* d_out, bool partial_out, void* d_buckets_out) {
@@ -1040,8 +1082,8 @@ int launch_msm_pippenger(snarkv_ctx* ctx, const void* d_scalars, const void* d_p
 
 // The same launch cut into its three phases, each enqueued on a stream of the caller's choice (the batch scheduler of
 // capi.hip runs the phases of MANY MSMs in phase order):
-//   PIP_PHASE_SORT  P0-P4  prepare, scan, partition + sort               (reads the inputs, fills ctx's scratch)
-//   PIP_PHASE_ACC   P5     bucket accumulation + combine                 (scratch -> bucket grid)
+//   PIP_PHASE_SORT  P0-S5  prepare, scan, partition + sort, piece schedule  (reads the inputs, fills ctx's scratch)
+//   PIP_PHASE_ACC   P4-P5  bucket accumulation + fix-up                     (scratch -> bucket grid)
 //   PIP_PHASE_TAIL  P6-P9  bucket reduce, shift chains, final            (bucket grid -> d_out)
 // `ctx` owns the scratch (its own stream is not used unless passed as `st`); `d_grid`, when given, is the bucket grid
 // to fill in place of the context's own (a batch lays its MSMs' grids end to end for one batched tail).  Every call
@@ -1087,32 +1129,39 @@ int launch_msm_pippenger_phases(snarkv_ctx* ctx, hipStream_t st, int phases, con
     return SNARKV_ERR_LENGTH;
   }
   p.krun = ctx->throughput_mode ? (uint32_t)kRunThroughput : latency_run_length(max_entries);
-  const uint32_t max_runs = (uint32_t)((max_entries + p.krun - 1) / p.krun) + 1;  // run slots (head / tail partial each)
+  // S5 geometry: pieces <= one per bucket + one per L entries; partial slots: two regions of one slot per L entries
+  const uint32_t max_pieces = (uint32_t)std::min<uint64_t>((uint64_t)p.nb + max_entries / p.krun, 0xFFFFFFFFull - 63);
+  const uint32_t split_slots = (uint32_t)(max_entries / p.krun) + 1;
+  const uint32_t nsb = (p.nb + kSchedBuckets - 1) / kSchedBuckets;
+  const uint32_t hcount = sched_rows(p.krun) * nsb;
+  const uint32_t hscan_blocks = (hcount + 1023) / 1024;
   uint32_t mcount = p.nkeys * p.mstride;
   uint32_t scan_blocks = (mcount + 1023) / 1024;
   uint32_t chunks_per_window = (p.B + kChunk - 1) / kChunk;
   uint32_t blocks_per_window = (chunks_per_window + 63) / 64;
 
-  void *d_pts, *d_glv, *d_counts, *d_offsets, *d_M, *d_blocksum, *d_entries, *d_tmp, *d_seg_ids, *d_seg_parts,
-      *d_buckets, *d_wave, *d_shift, *d_misc, *d_big;
+  void *d_pts, *d_glv, *d_counts, *d_offsets, *d_M, *d_blocksum, *d_entries, *d_tmp, *d_pieces, *d_hist, *d_parts,
+      *d_buckets, *d_wave, *d_shift, *d_misc, *d_lists;
   SNARKV_TRY(ctx_reserve(ctx, SLOT_POINTS_MONT, kHalves * n * sizeof(G1Packed), &d_pts));
   SNARKV_TRY(ctx_reserve(ctx, SLOT_GLV, n * 32, &d_glv));
   SNARKV_TRY(ctx_reserve(ctx, SLOT_COUNTS, (size_t)p.nb * 4, &d_counts));
   SNARKV_TRY(ctx_reserve(ctx, SLOT_OFFSETS, (size_t)p.nb * 4, &d_offsets));
   SNARKV_TRY(ctx_reserve(ctx, SLOT_CURSOR, (size_t)mcount * 4, &d_M));
-  SNARKV_TRY(ctx_reserve(ctx, SLOT_BLOCKSUMS, (size_t)scan_blocks * 4 + 64, &d_blocksum));
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_BLOCKSUMS, (size_t)std::max(scan_blocks, hscan_blocks) * 4 + 64, &d_blocksum));
   SNARKV_TRY(ctx_reserve(ctx, SLOT_ENTRIES, max_entries * 8, &d_entries));
   SNARKV_TRY(ctx_reserve(ctx, SLOT_SORT_TMP, max_entries * 8, &d_tmp));
-  SNARKV_TRY(ctx_reserve(ctx, SLOT_SEG_IDS, (size_t)max_runs * 8, &d_seg_ids));
-  SNARKV_TRY(ctx_reserve(ctx, SLOT_SEG_PARTIALS, (size_t)max_runs * 2 * sizeof(G1Xyzz29), &d_seg_parts));
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_PIECES, (size_t)max_pieces * sizeof(uint4), &d_pieces));
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_PIECE_HIST, (size_t)hcount * 4, &d_hist));
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_SPLIT_PARTS, (size_t)split_slots * 2 * sizeof(G1Xyzz29), &d_parts));
   if (d_grid) d_buckets = d_grid;
   else SNARKV_TRY(ctx_reserve(ctx, SLOT_BUCKETS, (size_t)p.nb * sizeof(G1Xyzz29), &d_buckets));
   SNARKV_TRY(ctx_reserve(ctx, SLOT_CHUNK_PARTIALS, 2 * (size_t)blocks_per_window * p.W * sizeof(G1Xyzz29), &d_wave));
   SNARKV_TRY(ctx_reserve(ctx, SLOT_SHIFTED, (size_t)p.W * sizeof(G1Xyzz29), &d_shift));
   SNARKV_TRY(ctx_reserve(ctx, SLOT_MISC, 64, &d_misc));
-  SNARKV_TRY(ctx_reserve(ctx, SLOT_BIG_LIST, (size_t)kMaxBig * 4, &d_big));
-  uint32_t* d_total = (uint32_t*)d_misc;  // [0] entries of the sorted stream, [4] big-bucket counter of k_combine
-  uint32_t* d_big_count = d_total + 4;
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_FIX_LISTS, (size_t)p.nb * 3 * 4, &d_lists));  // small split | big split | degenerate
+  uint32_t* d_total = (uint32_t*)d_misc;  // [0] entries of the sorted stream, [4] degenerate buckets, [6] S5 scan total
+  uint32_t* d_small = (uint32_t*)d_lists, *d_bigl = d_small + p.nb, *d_deg = d_bigl + p.nb;
+  const uint32_t* d_npieces = (const uint32_t*)d_hist + (size_t)(p.krun + 1) * nsb;  // start of the split-list rows
 
   const bool tm = ctx->stage_timing && phases == PIP_PHASE_ALL;
   const bool tm_acc = ctx->stage_timing && phases == PIP_PHASE_ACC;  // a batch times its accumulations: ev[3] .. ev[4] .. ev[5]
@@ -1128,7 +1177,7 @@ int launch_msm_pippenger_phases(snarkv_ctx* ctx, hipStream_t st, int phases, con
   STAGE_MARK();  // 0
   if (phases & PIP_PHASE_SORT) {
     // (no hipMemsetAsync anywhere: the matrix' padding column, the counters and the empty buckets are filled by
-    // k_prepare / k_sort_level2 / k_combine themselves -- 60 fill launches per 20-job batch less, level in time)
+    // k_prepare / k_piece_hist / k_accumulate themselves -- 60 fill launches per 20-job batch less, level in time)
     hipLaunchKernelGGL(k_prepare, dim3(p.nblk), dim3(SNARKV_PREP_THREADS), (size_t)p.nkeys * 4, st, (const uint32_t*)d_scalars,
                        (const uint32_t*)d_points, (G1Packed*)d_pts, (uint4*)d_glv, p, (uint32_t*)d_M);
     STAGE_MARK();  // 1: prepare (GLV split, phi(P), to Montgomery) + digit histogram
@@ -1150,34 +1199,38 @@ int launch_msm_pippenger_phases(snarkv_ctx* ctx, hipStream_t st, int phases, con
     const size_t lds2 = ((size_t)nbins_l2 + SNARKV_L2_THREADS + 1) * 4 + (size_t)kSortCap * 8;  // < 64 KiB: nbins <= 1 024
     hipLaunchKernelGGL(k_sort_level2, dim3(p.nkeys), dim3(SNARKV_L2_THREADS), lds2, st, (const uint2*)d_tmp, (const uint32_t*)d_M,
                        d_total, p, (uint2*)d_entries, (uint32_t*)d_counts, (uint32_t*)d_offsets);
+    // S5: the piece schedule (the scan's blocksums are free again: k_scan_add above has consumed them)
+    hipLaunchKernelGGL(k_piece_hist, dim3(nsb), dim3(256), 0, st, (const uint32_t*)d_counts, p, nsb, (uint32_t*)d_hist,
+                       d_total);
+    hipLaunchKernelGGL(k_scan_local, dim3(hscan_blocks), dim3(256), 0, st, (uint32_t*)d_hist, (uint32_t*)d_blocksum, hcount);
+    hipLaunchKernelGGL(k_scan_blocksums, dim3(1), dim3(1024), 0, st, (uint32_t*)d_blocksum, hscan_blocks, d_total + 6);
+    hipLaunchKernelGGL(k_scan_add, dim3(hscan_blocks), dim3(256), 0, st, (uint32_t*)d_hist, (const uint32_t*)d_blocksum,
+                       hcount);
+    hipLaunchKernelGGL(k_piece_emit, dim3(nsb), dim3(256), 0, st, (const uint32_t*)d_counts, (const uint32_t*)d_offsets, p,
+                       nsb, (const uint32_t*)d_hist, split_slots, (uint4*)d_pieces, d_small, d_bigl);
   }
   STAGE_MARK();  // 3: partition + level-2 sort
   // (Scheduling experiments measured and dropped -- a shared accumulate stream across in-flight MSMs, s_setprio on / off,
   // an occupancy cap on k_accumulate: DESIGN.md section 4.  The plateau is total issued work, not scheduling.)
   if (tm_acc) SNARKV_HIP(hipEventRecord(ctx->ev[3], st));
-  if (phases & PIP_PHASE_ACC) {
-    auto acc_kernel = p.krun == 16u ? k_accumulate<16> : p.krun == 32u ? k_accumulate<32>
-                      : p.krun == (uint32_t)kRun ? k_accumulate<kRun> : k_accumulate<kRunThroughput>;
-    hipLaunchKernelGGL(acc_kernel, dim3((max_runs + 63) / 64), dim3(64), 0, st, (const uint2*)d_entries,
-                       (const uint32_t*)d_total, (const G1Packed*)d_pts, (G1Xyzz29*)d_buckets, (uint32_t*)d_seg_ids,
-                       (G1Xyzz29*)d_seg_parts);
-  }
+  if (phases & PIP_PHASE_ACC)
+    hipLaunchKernelGGL(k_accumulate, dim3((max_pieces + 63) / 64), dim3(64), 0, st, (const uint4*)d_pieces, d_npieces,
+                       (const uint32_t*)d_total, (const uint2*)d_entries, (const G1Packed*)d_pts, (G1Xyzz29*)d_buckets,
+                       (G1Xyzz29*)d_parts, 2 * split_slots, d_total + 4, d_deg, p);
   STAGE_MARK();  // 4: bucket accumulate
   if (tm_acc) SNARKV_HIP(hipEventRecord(ctx->ev[4], st));
   if (phases & PIP_PHASE_ACC) {
-    hipLaunchKernelGGL(k_combine, dim3((p.nb + 63) / 64), dim3(64), 0, st, (const uint32_t*)d_counts,
-                       (const uint32_t*)d_offsets, p, (const uint2*)d_entries, (const G1Packed*)d_pts,
-                       (const uint32_t*)d_seg_ids, (const G1Xyzz29*)d_seg_parts, (G1Xyzz29*)d_buckets, d_big_count,
-                       (uint32_t*)d_big);
-    // one workgroup per oversized bucket; idle workgroups exit at once
-    const uint32_t big_grid = std::min<uint32_t>(max_runs / kBigSpan + 1, kBigGrid);
-    hipLaunchKernelGGL(k_combine_big, dim3(big_grid), dim3(256), 0, st, (const uint32_t*)d_counts,
-                       (const uint32_t*)d_offsets, (const uint2*)d_entries, (const G1Packed*)d_pts,
-                       (const uint32_t*)d_seg_ids, (const G1Xyzz29*)d_seg_parts, (G1Xyzz29*)d_buckets,
-                       (const uint32_t*)d_big_count, (const uint32_t*)d_big, p);
+    // grid from a host bound on the lists: a split bucket holds more than L entries, a degenerate one is rare (its
+    // lanes walk the list); idle workgroups exit at once
+    const uint64_t split_bound = std::min<uint64_t>(p.nb, max_entries / (p.krun + 1) + 1);
+    const uint32_t fix_grid = (uint32_t)std::min<uint64_t>((split_bound + 255) / 256, kFixGrid);
+    hipLaunchKernelGGL(k_fixup, dim3(fix_grid), dim3(256), 0, st, (const uint32_t*)d_counts, (const uint32_t*)d_offsets,
+                       (const uint2*)d_entries, (const G1Packed*)d_pts, (const G1Xyzz29*)d_parts, split_slots,
+                       (G1Xyzz29*)d_buckets, (const uint32_t*)d_hist, nsb, (const uint32_t*)d_total,
+                       (const uint32_t*)d_small, (const uint32_t*)d_bigl, (const uint32_t*)d_deg, p);
     if (tm_acc) SNARKV_HIP(hipEventRecord(ctx->ev[5], st));
   }
-  STAGE_MARK();  // 5: bucket combine
+  STAGE_MARK();  // 5: bucket fix-up (split and degenerate buckets)
   if (d_buckets_out) {  // bucket-sharded variant: hand the (sanitised) bucket sums out and stop here
     if (phases & PIP_PHASE_ACC)
       SNARKV_HIP(hipMemcpyAsync(d_buckets_out, d_buckets, (size_t)p.nb * sizeof(G1Xyzz29), hipMemcpyDeviceToDevice, st));
