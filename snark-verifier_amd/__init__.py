@@ -35,9 +35,13 @@ from ._lib import (  # noqa: F401
 )
 
 from . import host_api  # noqa: F401,E402  (C API of the C++ host mirror: include/snarkv_host.h)
+from . import ipa_prover  # noqa: F401,E402  (the IPA prover on the device: include/snarkv_ipa_prover.h)
+from .ipa_prover import IpaProver  # noqa: F401,E402
 
 __all__ = [
     "host_api",
+    "ipa_prover",
+    "IpaProver",
     "Context",
     "DecidingKey",
     "IpaDecidingKey",

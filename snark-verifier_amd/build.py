@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsnarkv_amd.so")
-UNITS = ["capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "mgpu", "decompress"]
+UNITS = ["capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "ipa_prover", "mgpu", "decompress"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
@@ -23,6 +23,7 @@ def _deps():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp", ".inc"))]
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_amd.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_pallas.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_prover.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
 
@@ -66,7 +67,7 @@ def _link(lib, res, extra):
 
 
 # The pasta build of the curve-generic units (csrc/pallas.hip explains the flags).
-PALLAS_UNITS = ["pallas", "msm_pippenger", "msm_naive", "ipa"]
+PALLAS_UNITS = ["pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
 

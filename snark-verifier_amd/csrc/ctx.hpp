@@ -118,6 +118,15 @@ struct snarkv_dk {
   uint8_t g1[64];
 };
 
+// the IPA deciding key (ipa.hip); the prover session (ipa_prover.hip) reads its points
+struct snarkv_ipa_dk {
+  int device;
+  uint32_t k;
+  void* d_points;  // the points held: 64 B canonical affine each, as the Pippenger entry point takes them
+  size_t first;    // index of the first point held in the 2^k-point key (0 unless a multi-GPU shard)
+  size_t count;    // points held (2^k unless a shard)
+};
+
 namespace snarkv {
 
 // The encoding of a call = the context's default flags | the call's own: kept in ctx->mont while the call enqueues its

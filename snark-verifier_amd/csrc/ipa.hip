@@ -10,14 +10,6 @@
 #include "ctx.hpp"
 #include "fr29.h"
 
-struct snarkv_ipa_dk {
-  int device;
-  uint32_t k;
-  void* d_points;  // the points held: 64 B canonical affine each, as the Pippenger entry point takes them
-  size_t first;    // index of the first point held in the 2^k-point key (0 unless a multi-GPU shard)
-  size_t count;    // points held (2^k unless a shard)
-};
-
 namespace snarkv {
 
 // coeff[j] = prod over the set bits i of j of xi[k-1-i]   (h_coeffs with scalar = 1: the

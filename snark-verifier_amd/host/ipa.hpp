@@ -19,14 +19,23 @@
 //
 // The scheme is generic over `C: CurveAffine`; the reference's tests use pallas,
 // this mirror BN254 G1 -- the curve the device kernels are built for.  The prover
-// halves (`Ipa::create_proof`, `IpaAs::create_proof`) live in oracle/ipa.py only:
-// they make the test proofs and are not part of the verification path.
+// halves (`Ipa::create_proof`, `IpaAs::create_proof`, ipa.rs:39-124, accumulation.rs:148-226)
+// drive the device session of include/snarkv_ipa_prover.h and write through `Transcript`.
 #pragma once
+#include <functional>
 #include <memory>
 #include <optional>
 #include <vector>
 
+#include "../../include/snarkv_ipa_prover.h"
 #include "pcs.hpp"
+
+// the prover session of the library the mirror is linked against (include/snarkv_ipa_prover.h)
+#if defined(SNARKV_HOST_PALLAS)
+#define SNARKV_IPA_PROVER(name) snarkv_pallas_##name
+#else
+#define SNARKV_IPA_PROVER(name) snarkv_##name
+#endif
 
 namespace snarkv_host {
 
@@ -133,7 +142,16 @@ struct IpaProof {
   }
 };
 
+struct IpaDecidingKey;
+
 struct Ipa {
+  // ipa.rs:39-124 on the device session: the rounds (inner products, MSMs, folds) run there, the transcript here.
+  // `omega` is the blind of the commitment (zk keys only); `rng` plays `C::Scalar::random(rng)`, called in the
+  // reference's order (the n values of p_bar, then omega_bar).
+  static Result<IpaAccumulator> create_proof(const IpaDecidingKey& dk, std::vector<Fr> p, const Fr& z,
+                                             const std::optional<Fr>& omega, Transcript& t,
+                                             const std::function<Fr()>& rng);
+
   // ipa.rs:127-136
   static Result<IpaProof> read_proof(const IpaSuccinctVerifyingKey& svk, Transcript& t) {
     return IpaProof::read(svk, t);
@@ -304,6 +322,10 @@ struct IpaAs {
     return Ipa::succinct_verify(vk, c, proof.z, v, proof.ipa);
   }
 
+  // accumulation.rs:148-226 (`AccumulationSchemeProver::create_proof`): ipa_as_create_proof below
+  static Result<IpaAccumulator> create_proof(const IpaDecidingKey& dk, const std::vector<IpaAccumulator>& instances,
+                                             Transcript& t, const std::function<Fr()>& rng);
+
   // decider.rs:47-55: U == commit(G, h).  h_coeffs (ipa.rs:405-421) is built on the device straight
   // into the scalar buffer of ONE 2^k-term Pippenger over the resident committing key.
   static Error decide(const IpaDecidingKey& dk, const IpaAccumulator& acc) { return decide_all(dk, {acc}); }
@@ -329,6 +351,154 @@ struct IpaAs {
     return Error{};
   }
 };
+
+// ------------------------------------------------------------------ prover (device session)
+namespace ipa_prover_detail {
+// a context of its own per proof: the session's calls are synchronous on it (include/snarkv_ipa_prover.h)
+struct Ctx {
+  snarkv_ctx* c = nullptr;
+  Ctx() {
+    if (SNARKV_IPA_PROVER(ctx_create)(0, nullptr, &c) != SNARKV_OK)
+      throw std::runtime_error(std::string("ctx_create: ") + SNARKV_DEV_LAST_ERROR());
+  }
+  ~Ctx() {
+    if (c) SNARKV_IPA_PROVER(ctx_destroy)(c);
+  }
+  Ctx(const Ctx&) = delete;
+  Ctx& operator=(const Ctx&) = delete;
+};
+inline void check(int rc, const char* what) {
+  if (rc != SNARKV_OK) throw std::runtime_error(std::string(what) + ": " + SNARKV_DEV_LAST_ERROR());
+}
+inline std::vector<uint8_t> pack(const std::vector<Fr>& v) {
+  std::vector<uint8_t> out(32 * v.size());
+  for (size_t i = 0; i < v.size(); ++i) v[i].to_bytes(&out[32 * i]);
+  return out;
+}
+// `IpaProvingKey::commit` (ipa.rs:221-229) over the first poly.size() bases (+ omega S)
+inline G1Affine commit(Ctx& ctx, const snarkv_ipa_dk* dk, const std::vector<Fr>& poly, const Fr* omega, const G1Affine* s) {
+  std::vector<uint8_t> pb = pack(poly);
+  uint8_t om[32];
+  if (omega) omega->to_bytes(om);
+  G1Affine out;
+  check(SNARKV_IPA_PROVER(ipa_commit)(ctx.c, dk, pb.data(), poly.size(), omega ? om : nullptr, omega ? s->b : nullptr,
+                                      out.b),
+        "ipa_commit");
+  return out;
+}
+}  // namespace ipa_prover_detail
+
+inline Result<IpaAccumulator> Ipa::create_proof(const IpaDecidingKey& dk, std::vector<Fr> p, const Fr& z,
+                                                const std::optional<Fr>& omega, Transcript& t,
+                                                const std::function<Fr()>& rng) {
+  namespace D = ipa_prover_detail;
+  using R = Result<IpaAccumulator>;
+  const size_t k = dk.svk.k, n = (size_t)1 << k;
+  if (p.size() != n) throw Panic("create_proof: p must have 2^k coefficients (reference: zip over the bases, ipa.rs:95)");
+  if (dk.svk.s.has_value() != omega.has_value()) throw Panic("create_proof: omega goes with a zk key (reference: unwrap, ipa.rs:58)");
+  const snarkv_ipa_dk* h = dk.handle();
+  D::Ctx ctx;
+  if (dk.svk.s) {  // ipa.rs:52-68
+    std::vector<Fr> p_bar(n);
+    for (auto& v : p_bar) v = rng();
+    Fr ev = Fr::zero();
+    for (size_t i = n; i-- > 0;) ev = ev * z + p_bar[i];
+    p_bar[0] = p_bar[0] - ev;
+    const Fr omega_bar = rng();
+    Error e = t.write_ec_point(D::commit(ctx, h, p_bar, &omega_bar, &*dk.svk.s));
+    if (!e.ok()) return R::Err(e);
+    const Fr alpha = t.squeeze_challenge();
+    e = t.write_scalar(*omega + alpha * omega_bar);
+    if (!e.ok()) return R::Err(e);
+    for (size_t i = 0; i < n; ++i) p[i] = p[i] + alpha * p_bar[i];
+  }
+  const Fr xi_0 = t.squeeze_challenge();
+  std::vector<uint8_t> pb = D::pack(p);
+  uint8_t z32[32], xi0_32[32];
+  z.to_bytes(z32);
+  xi_0.to_bytes(xi0_32);
+  snarkv_ipa_prover* sp = nullptr;
+  D::check(SNARKV_IPA_PROVER(ipa_prover_begin)(ctx.c, h, pb.data(), n, z32, dk.svk.h.b, xi0_32, &sp), "ipa_prover_begin");
+  std::unique_ptr<snarkv_ipa_prover, void (*)(snarkv_ipa_prover*)> session(sp, SNARKV_IPA_PROVER(ipa_prover_destroy));
+  IpaAccumulator acc;
+  for (size_t i = 0; i < k; ++i) {  // ipa.rs:80-118
+    G1Affine l, r;
+    D::check(SNARKV_IPA_PROVER(ipa_prover_round)(sp, l.b, r.b), "ipa_prover_round");
+    Error e = t.write_ec_point(l);
+    if (e.ok()) e = t.write_ec_point(r);
+    if (!e.ok()) return R::Err(e);
+    const Fr xi = t.squeeze_challenge();
+    uint8_t x32[32];
+    xi.to_bytes(x32);
+    D::check(SNARKV_IPA_PROVER(ipa_prover_fold)(sp, x32), "ipa_prover_fold");
+    acc.xi.push_back(xi);
+  }
+  uint8_t c32[32];
+  D::check(SNARKV_IPA_PROVER(ipa_prover_finish)(sp, acc.u.b, c32), "ipa_prover_finish");
+  Fr c;
+  if (!Fr::from_bytes(c32, &c)) throw std::runtime_error("ipa_prover_finish: non-canonical c");
+  Error e = t.write_ec_point(acc.u);  // ipa.rs:121-122
+  if (e.ok()) e = t.write_scalar(c);
+  if (!e.ok()) return R::Err(e);
+  return R::Ok(std::move(acc));
+}
+
+// accumulation.rs:148-226: the IpaAs prover.  h = sum alpha^i h_coeffs(xi_i) (+ alpha^m (b, a, 0, ...)) is formed on
+// the host, as in the reference; the opening of h at z is `Ipa::create_proof` on the device.
+inline Result<IpaAccumulator> ipa_as_create_proof(const IpaDecidingKey& dk, const std::vector<IpaAccumulator>& instances,
+                                                  Transcript& t, const std::function<Fr()>& rng) {
+  namespace D = ipa_prover_detail;
+  using R = Result<IpaAccumulator>;
+  if (instances.size() < 2) throw Panic("IpaAs::create_proof: at least two accumulators (reference: assert!, accumulation.rs:156)");
+  const size_t k = dk.svk.k, n = (size_t)1 << k;
+  std::optional<std::pair<Fr, Fr>> ab;
+  std::optional<Fr> omega;
+  if (dk.svk.s) {  // accumulation.rs:163-176
+    const Fr a = rng(), b = rng();
+    G1Affine u;
+    {
+      D::Ctx ctx;
+      u = D::commit(ctx, dk.handle(), {b, a}, nullptr, nullptr);  // g[1] a + g[0] b
+    }
+    Error e = t.write_scalar(a);
+    if (e.ok()) e = t.write_scalar(b);
+    if (e.ok()) e = t.write_ec_point(u);
+    if (!e.ok()) return R::Err(e);
+    ab = std::make_pair(a, b);
+    omega = rng();
+    e = t.write_scalar(*omega);
+    if (!e.ok()) return R::Err(e);
+  }
+  for (auto& acc : instances) {  // accumulation.rs:178-183
+    if (acc.xi.size() != k) throw Panic("IpaAs::create_proof: accumulator with xi.len() != k");
+    for (auto& x : acc.xi) {
+      Error e = t.common_scalar(x);
+      if (!e.ok()) return R::Err(e);
+    }
+    Error e = t.common_ec_point(acc.u);
+    if (!e.ok()) return R::Err(e);
+  }
+  const Fr alpha = t.squeeze_challenge();
+  const Fr z = t.squeeze_challenge();
+  std::vector<Fr> h(n, Fr::zero());  // accumulation.rs:186-207
+  Fr pw = Fr::one();
+  for (auto& acc : instances) {
+    const std::vector<Fr> hc = h_coeffs(acc.xi, Fr::one());
+    for (size_t j = 0; j < n; ++j) h[j] = h[j] + pw * hc[j];
+    pw = pw * alpha;
+  }
+  if (ab) {
+    h[0] = h[0] + pw * ab->second;
+    h[1] = h[1] + pw * ab->first;
+  }
+  return Ipa::create_proof(dk, std::move(h), z, omega, t, rng);
+}
+
+template <class MOS>
+inline Result<IpaAccumulator> IpaAs<MOS>::create_proof(const IpaDecidingKey& dk, const std::vector<IpaAccumulator>& instances,
+                                                       Transcript& t, const std::function<Fr()>& rng) {
+  return ipa_as_create_proof(dk, instances, t, rng);
+}
 
 // ------------------------------------------------------------------ Bgh19
 // bgh19.rs:98-153.  The IPA part arrives in halo2's order (S, xi, z, rounds, c, blind, G) and

@@ -191,3 +191,72 @@ extern "C" int SNARKV_DRV(plonk_ipa_verify_batch)(int tkind, const uint8_t* prot
     return IpaAs<Bgh19>::decide_all(dk, *accs.value).ok() ? 1 : 0;
   });
 }
+
+// ---- prover (ipa.rs:39-124, accumulation.rs:148-226) on the device session --------------------------------------
+// `rand32` holds the n_rand scalars `rng()` plays, in the order the prover draws them (running out is a panic).
+// proof_out (cap bytes) receives the transcript's stream, *plen its length; acc_out the new accumulator (pack_acc).
+namespace {
+std::function<Fr()> ipa_rng_of(const uint8_t* rand32, size_t n_rand, size_t* used) {
+  return [=]() {
+    if (*used >= n_rand) throw Panic("ipa create_proof: rng ran out of scalars");
+    Fr v;
+    if (!Fr::from_bytes(rand32 + 32 * (*used)++, &v)) throw Panic("ipa create_proof: non-canonical rng scalar");
+    return v;
+  };
+}
+IpaDecidingKey ipa_dk_of(const uint8_t* svk_bytes, const uint8_t* g, size_t n_g) {
+  IpaDecidingKey dk;
+  dk.svk = parse_ipa_svk(svk_bytes);
+  dk.g.resize(n_g);
+  for (size_t i = 0; i < n_g; ++i) dk.g[i] = G1Affine::from_bytes(g + 64 * i);
+  return dk;
+}
+int ipa_put_proof(const Transcript& t, const IpaAccumulator& acc, uint8_t* proof_out, size_t cap, size_t* plen,
+                  uint8_t* acc_out) {
+  std::vector<uint8_t> st = transcript_stream(t);
+  *plen = st.size();
+  if (st.size() > cap) return -2;
+  memcpy(proof_out, st.data(), st.size());
+  put_ipa_acc(acc, acc_out);
+  return 1;
+}
+}  // namespace
+
+extern "C" int SNARKV_DRV(ipa_create_proof)(int tkind, const uint8_t* svk_bytes, const uint8_t* g, size_t n_g,
+                                            const uint8_t* p32, const uint8_t* z32, const uint8_t* omega32_or_null,
+                                            const uint8_t* rand32, size_t n_rand, uint8_t* proof_out, size_t cap,
+                                            size_t* plen, uint8_t* acc_out) {
+  return guarded([&] {
+    IpaDecidingKey dk = ipa_dk_of(svk_bytes, g, n_g);
+    std::vector<Fr> p(n_g);
+    for (size_t i = 0; i < n_g; ++i)
+      if (!Fr::from_bytes(p32 + 32 * i, &p[i])) return -3;
+    Fr z;
+    if (!Fr::from_bytes(z32, &z)) return -3;
+    std::optional<Fr> omega;
+    if (omega32_or_null) {
+      omega = Fr::zero();
+      if (!Fr::from_bytes(omega32_or_null, &*omega)) return -3;
+    }
+    size_t used = 0;
+    auto t = make_transcript(tkind, nullptr, 0);
+    auto acc = Ipa::create_proof(dk, std::move(p), z, omega, *t, ipa_rng_of(rand32, n_rand, &used));
+    if (!acc.ok()) return error_code(acc.err);
+    return ipa_put_proof(*t, *acc.value, proof_out, cap, plen, acc_out);
+  });
+}
+
+extern "C" int SNARKV_DRV(ipa_as_create_proof)(int tkind, const uint8_t* svk_bytes, const uint8_t* g, size_t n_g,
+                                               const uint8_t* accs, uint32_t m, const uint8_t* rand32, size_t n_rand,
+                                               uint8_t* proof_out, size_t cap, size_t* plen, uint8_t* acc_out) {
+  return guarded([&] {
+    IpaDecidingKey dk = ipa_dk_of(svk_bytes, g, n_g);
+    std::vector<IpaAccumulator> instances;
+    if (!parse_ipa_accs(accs, dk.svk.k, m, &instances)) return -3;
+    size_t used = 0;
+    auto t = make_transcript(tkind, nullptr, 0);
+    auto acc = IpaAs<>::create_proof(dk, instances, *t, ipa_rng_of(rand32, n_rand, &used));
+    if (!acc.ok()) return error_code(acc.err);
+    return ipa_put_proof(*t, *acc.value, proof_out, cap, plen, acc_out);
+  });
+}

@@ -864,6 +864,10 @@ std::unique_ptr<Transcript> make_transcript(int tkind, const uint8_t* proof, siz
   if (tkind == 0) return std::make_unique<EvmTranscript>(std::move(bytes));
   return std::make_unique<PoseidonTranscript>(std::move(bytes));
 }
+std::vector<uint8_t> transcript_stream(const Transcript& t) {  // what a writer of make_transcript's kinds holds
+  if (auto* e = dynamic_cast<const EvmTranscript*>(&t)) return e->stream();
+  return dynamic_cast<const PoseidonTranscript&>(t).stream();
+}
 }  // namespace
 #define SNARKV_DRV(name) hd_##name
 #include "ipa_driver.inc"

@@ -46,6 +46,7 @@ int guarded(const std::function<int()>& f) {
 std::unique_ptr<Transcript> make_transcript(int /*tkind: Blake2b only*/, const uint8_t* proof, size_t plen) {
   return std::make_unique<Blake2bTranscript>(std::vector<uint8_t>(proof, proof + plen));
 }
+std::vector<uint8_t> transcript_stream(const Transcript& t) { return dynamic_cast<const Blake2bTranscript&>(t).finalize(); }
 }  // namespace
 
 #define SNARKV_DRV(name) hp_##name

@@ -1,0 +1,56 @@
+"""CPU: the C ABI of the IPA prover (include/snarkv_ipa_prover.h): the header is strict C99, both
+libraries export every name it declares, the ctypes table of snark_verifier_amd.ipa_prover lists
+exactly those names (and none of snarkv_amd.h's), and null arguments are refused before any device
+work."""
+import ctypes
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HDR = os.path.join(ROOT, "include", "snarkv_ipa_prover.h")
+
+
+def _declared():
+    txt = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(snarkv_[a-z0-9_]+)\s*\(", txt)))
+
+
+def test_header_is_strict_c99():
+    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", HDR],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_both_libraries_export_every_declared_name():
+    import snark_verifier_amd as sv
+    from snark_verifier_amd import _lib, ipa_prover
+    from snark_verifier_amd import pallas as PL
+
+    declared = _declared()
+    assert len(declared) == 16
+    assert sorted(ipa_prover.SIGNATURES) == declared
+    assert not set(declared) & set(_lib._SIGNATURES)  # snarkv_amd.h's table stays as it is
+    bn, pa = sv.load_library(), PL.load_library()
+    for name in declared:
+        assert hasattr(bn if not name.startswith("snarkv_pallas_") else pa, name), name
+
+
+def test_null_arguments_are_refused_without_a_device():
+    import snark_verifier_amd as sv
+    from snark_verifier_amd import ipa_prover
+    from snark_verifier_amd import pallas as PL
+
+    for lib, prefix in ((sv.load_library(), "snarkv_"), (PL.load_library(), "snarkv_pallas_")):
+        api = ipa_prover._Api(lib, prefix, ipa_prover.R_BN254)
+        b32, b64 = b"\x00" * 32, b"\x00" * 64
+        out = ctypes.create_string_buffer(64)
+        h = ctypes.c_void_p()
+        assert api.ipa_prover_round(None, out, out) == sv.SNARKV_ERR_ARG
+        assert api.ipa_prover_fold(None, b32) == sv.SNARKV_ERR_ARG
+        assert api.ipa_prover_finish(None, out, out) == sv.SNARKV_ERR_ARG
+        api.ipa_prover_destroy(None)
+        assert api.ipa_prover_begin(None, None, b32, 1, b32, b64, b32, ctypes.byref(h)) == sv.SNARKV_ERR_ARG
+        assert api.ipa_prover_begin_dev(None, None, None, 1, b32, b64, b32, ctypes.byref(h)) == sv.SNARKV_ERR_ARG
+        assert api.ipa_commit(None, None, b32, 1, None, None, out) == sv.SNARKV_ERR_ARG
+        assert api.ipa_as_combine_dev(None, b32, 1, 1, b32, None, None) == sv.SNARKV_ERR_ARG
