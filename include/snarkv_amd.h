@@ -135,7 +135,7 @@ int snarkv_g1_msm_batched_dev(snarkv_ctx* ctx, const void* d_scalars32, const vo
  * msm.rs:308, is to the reference: the accumulation path issues one per `Msm::evaluate`): d_out64s[64 i ..] =
  * sum_j scalars_i[j] * points_i[j], the same bytes `snarkv_g1_msm_pippenger_dev` gives for each.  One call, one
  * context: the library pipelines the MSMs itself (sorts on high-priority streams, accumulations back to back, ONE
- * batched tail per round; csrc/capi.hip) -- 4-5 % faster than four single calls kept in flight for 8-20 MSMs of 2^20
+ * batched tail per round; csrc/msm_api.hip) -- 4-5 % faster than four single calls kept in flight for 8-20 MSMs of 2^20
  * points, level beyond.  Scratch: ~0.5 KiB per point and job; more than SNARKV_MANY_MAX_JOBS MSMs (or 48 GiB of
  * scratch) run as successive rounds; an MSM large enough for the chunk pipeline (3 * 2^20 points) makes the call
  * fall back to one MSM after the other.  Asynchronous on the context stream; n[i] = 0 is SNARKV_ERR_EMPTY. */
@@ -416,7 +416,7 @@ int snarkv_kzg_decide_batch_mgpu(snarkv_mgpu* mg, const uint8_t g1_64[64], const
  * launch sizes its lane groups by the share of the GPU it can count on); n >= 2: on, with n contexts in flight. */
 int snarkv_ctx_set_throughput_hint(snarkv_ctx* ctx, int enabled);
 /* points ONE launch of the Pippenger kernels processes for an n-point MSM: n itself, or the 2^20-point chunk of the
- * chunk pipeline large MSMs run as (csrc/capi.hip pippenger_maybe_split) -- what a per-launch roofline divides by */
+ * chunk pipeline large MSMs run as (csrc/msm_api.hip launch_msm_pippenger_auto) -- what a per-launch roofline divides by */
 int snarkv_g1_msm_launch_points(size_t n, size_t* per_launch);
 /* ... for a call that passes `window_bits` (an explicit window size keeps the single launch whatever n is) */
 int snarkv_g1_msm_launch_points_ex(size_t n, int window_bits, size_t* per_launch);

@@ -10,7 +10,7 @@ without the built library or without a HIP device raises.
 """
 # HIP multiplexes a process's streams onto a fixed number of hardware queues (the runtime's default is 4) and kernels of
 # streams that share a queue run one after the other.  The queue count is the runtime's and the host's setting: neither
-# the package nor the library changes it (csrc/capi.hip).
+# the package nor the library changes it (csrc/ctx.hip).
 
 from ._lib import (  # noqa: F401
     Context,

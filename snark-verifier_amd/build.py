@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsnarkv_amd.so")
-UNITS = ["capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "ipa_prover", "mgpu", "decompress"]
+UNITS = ["ctx", "msm_api", "capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "ipa_prover", "mgpu",
+         "decompress"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
@@ -66,18 +67,10 @@ def _link(lib, res, extra):
             raise RuntimeError("link failed: %s" % os.path.basename(lib))
 
 
-# The pasta build of the curve-generic units (csrc/pallas.hip explains the flags).
-PALLAS_UNITS = ["pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover"]
+# The pasta build of the curve-generic units (csrc/pallas.hip explains the flags, csrc/ctx.hpp the policy they select).
+PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
-
-
-def build_pallas(verbose=False):
-    os.makedirs(BUILD, exist_ok=True)
-    with ThreadPoolExecutor(max_workers=len(PALLAS_UNITS)) as ex:
-        res = list(ex.map(lambda u: _compile(u, verbose, PALLAS_FLAGS, "_pallas"), PALLAS_UNITS))
-    _link(PALLAS_LIB, res, ["-Wl,-Bsymbolic"])
-    return PALLAS_LIB
 
 
 HOST = os.path.join(HERE, "host")

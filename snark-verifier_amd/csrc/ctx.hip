@@ -1,6 +1,10 @@
-// Context object behind the C ABI: error string, grow-only scratch slots, create / destroy / sync.
-// Included by capi.hip (BN254: snarkv_*) and pallas.hip (the pasta build: snarkv_pallas_*); the entry
-// point names come from SNARKV_API (ctx.hpp).
+// Context object behind the C ABI: error string, grow-only scratch slots, create / destroy / sync, the staging
+// helpers of the entry points.  Built into both libraries (BN254: snarkv_*, the pasta build: snarkv_pallas_*); the
+// entry point names come from SNARKV_API (ctx.hpp).
+#include <stdarg.h>
+#include <string.h>
+#include "ctx.hpp"
+
 namespace snarkv {
 
 static thread_local char g_err[512] = "";
@@ -17,7 +21,7 @@ int ctx_reserve(snarkv_ctx* ctx, int slot, size_t bytes, void** out) {
   if (ctx->cap[slot] < bytes) {
     if (ctx->buf[slot]) {
       // earlier launches may still use the old buffer: on the context's stream -- or, for a lane / job context, on
-      // whichever stream of the owning scheduler its phases were enqueued on (capi.hip: the batch's sort and
+      // whichever stream of the owning scheduler its phases were enqueued on (msm_api.hip: the batch's sort and
       // accumulation streams never are the job's own), so a lane waits for the whole device
       if (ctx->is_lane) SNARKV_HIP(hipDeviceSynchronize());
       else SNARKV_HIP(hipStreamSynchronize(ctx->stream));
@@ -30,6 +34,29 @@ int ctx_reserve(snarkv_ctx* ctx, int slot, size_t bytes, void** out) {
     ctx->cap[slot] = cap;
   }
   *out = ctx->buf[slot];
+  return SNARKV_OK;
+}
+
+int stage_in(snarkv_ctx* ctx, int slot, const void* host, size_t bytes, void** d) {
+  SNARKV_TRY(ctx_reserve(ctx, slot, bytes, d));
+  SNARKV_HIP(hipMemcpyAsync(*d, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  return SNARKV_OK;
+}
+
+int fetch_out(snarkv_ctx* ctx, const void* d, void* host, size_t bytes) {
+  SNARKV_HIP(hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SNARKV_HIP(hipStreamSynchronize(ctx->stream));
+  return SNARKV_OK;
+}
+
+int check_validate(snarkv_ctx* ctx, const void* d_s, const void* d_p, size_t n, uint32_t flags) {
+  if (!((flags | ctx->flags) & SNARKV_FLAG_VALIDATE)) return SNARKV_OK;
+  int bad = 0;
+  SNARKV_TRY(launch_validate(ctx, d_s, d_p, n, &bad));
+  if (bad) {
+    set_last_error("%d of %zu inputs are non-canonical or off-curve", bad, n);
+    return SNARKV_ERR_ENCODING;
+  }
   return SNARKV_OK;
 }
 
@@ -154,6 +181,8 @@ namespace snarkv {
 // Four lanes for independent launches on one context: the caller's own stream + three private
 // sub-contexts (one HIP stream + scratch each).  Not four private ones: HIP multiplexes streams onto
 // 4 hardware queues by default, and a fifth busy stream would share a queue with one of the lanes.
+// (Streams sharing a queue serialise.  The queue count is a process-wide setting of the runtime and the
+// host: the library never touches it.)
 int ctx_lanes(snarkv_ctx* ctx) {
   if (!ctx->sub_ready) {
     for (int i = 0; i < 3; ++i) {

@@ -7,11 +7,20 @@
 #include "../../include/snarkv_amd.h"
 #include "curve_consts.h"
 
-// extern "C" names of the units shared between the BN254 library and the pasta build
+// extern "C" names of the units shared between the BN254 library and the pasta build, and where the two builds'
+// MSM entry points (msm_api.hip) differ:
+//   SNARKV_CHUNK_PIPELINE  large MSMs may run as the chunk pipeline (pip_chunk_pipeline); the pasta build keeps the
+//                          single launch at every size
+//   SNARKV_API_FLAGS       the bits of a call's `flags` the entry points honour; the pasta build takes
+//                          SNARKV_FLAG_VALIDATE only (include/snarkv_pallas.h)
 #if defined(SNARKV_CURVE_PALLAS)
 #define SNARKV_API(name) snarkv_pallas_##name
+#define SNARKV_CHUNK_PIPELINE 0
+#define SNARKV_API_FLAGS SNARKV_FLAG_VALIDATE
 #else
 #define SNARKV_API(name) snarkv_##name
+#define SNARKV_CHUNK_PIPELINE 1
+#define SNARKV_API_FLAGS (SNARKV_FLAG_VALIDATE | SNARKV_FLAG_MONTGOMERY)
 #endif
 
 namespace snarkv {
@@ -88,7 +97,7 @@ struct snarkv_ctx {
   float stage_ms[SNARKV_PIP_STAGES];
   hipEvent_t ev[SNARKV_PIP_STAGES + 1];
   bool ev_ready;
-  // large MSMs run as pipelined 2^20-point chunks on private sub-contexts (capi.hip)
+  // large MSMs run as pipelined 2^20-point chunks on private sub-contexts (msm_api.hip)
   snarkv_ctx* sub[4];
   hipEvent_t sub_ev[5];
   bool sub_ready;
@@ -158,7 +167,12 @@ struct WireFormScope {
 
 // Ensure slot capacity; returns device pointer through *out.
 int ctx_reserve(snarkv_ctx* ctx, int slot, size_t bytes, void** out);
-// four lanes (the context's stream + three private sub-contexts) for independent launches: ctx_impl.inc
+// staging of the host-resident entry points (ctx.hip): host bytes into a slot, a result back to the host (synchronous),
+// and the device check of SNARKV_FLAG_VALIDATE (the call's flags | the context's)
+int stage_in(snarkv_ctx* ctx, int slot, const void* host, size_t bytes, void** d);
+int fetch_out(snarkv_ctx* ctx, const void* d, void* host, size_t bytes);
+int check_validate(snarkv_ctx* ctx, const void* d_s, const void* d_p, size_t n, uint32_t flags);
+// four lanes (the context's stream + three private sub-contexts) for independent launches: ctx.hip
 int ctx_lanes(snarkv_ctx* ctx);
 int ctx_lanes_fork(snarkv_ctx* ctx);
 int ctx_lanes_join(snarkv_ctx* ctx);
@@ -177,16 +191,19 @@ int launch_msm_pippenger_phases(snarkv_ctx* ctx, hipStream_t st, int phases, con
                                 void* d_grid);
 int launch_buckets_reduce_many(snarkv_ctx* ctx, hipStream_t st, const void* d_grids, uint32_t c, uint32_t windows,
                                uint32_t jobs, void* d_out, bool partial_out);
-// `count` independent MSMs, phase-ordered over private job contexts (capi.hip)
+// `count` independent MSMs, phase-ordered over private job contexts (msm_api.hip)
 // `ready` (optional): one event per job -- its inputs are in place (uploads of a host-resident batch); a job's first kernel
 // waits for its event only, so the uploads of later jobs run under the kernels of earlier ones
 int launch_msm_pippenger_many(snarkv_ctx* ctx, size_t count, const void* const* d_scalars, const void* const* d_points,
                               const size_t* n, int window_bits, void* d_out, bool partial_out, hipEvent_t* ready = nullptr);
-// the product path of a large MSM: single launch, or the chunk pipeline over shared bucket grids (capi.hip)
+// the product path of a large MSM: single launch, or the chunk pipeline over shared bucket grids (msm_api.hip)
 int launch_msm_pippenger_auto(snarkv_ctx* ctx, const void* d_scalars, const void* d_points, size_t n, int window_bits,
                               void* d_out, bool partial_out);
-// does an n-point MSM run as the chunk pipeline over shared bucket grids? (the one rule: capi.hip)
+// does an n-point MSM run as the chunk pipeline over shared bucket grids? (the one rule: msm_api.hip)
 bool pip_chunk_pipeline(size_t n, int window_bits, bool is_lane, size_t* chunk);
+// the host-staged Pippenger behind snarkv_g1_msm_pippenger / snarkv_pallas_g1_msm_pippenger (msm_api.hip)
+int msm_pippenger_staged(snarkv_ctx* ctx, const uint8_t* scalars32, const uint8_t* points64, size_t n, uint32_t flags,
+                         uint8_t out64[64]);
 int pip_geometry(size_t n_total, int window_bits, uint32_t* c, uint32_t* windows, uint32_t* buckets_per_window);
 int launch_buckets_add(snarkv_ctx* ctx, void* d_dst, const void* d_src, size_t count);
 int launch_buckets_reduce(snarkv_ctx* ctx, const void* d_buckets, uint32_t c, uint32_t w0, uint32_t wcount, void* d_partial);

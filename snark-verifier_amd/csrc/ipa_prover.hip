@@ -230,11 +230,7 @@ static size_t naive_max() {
 }
 static int ipa_msm(snarkv_ctx* ctx, const void* d_s, const void* d_p, size_t n, const void* d_off01n, void* d_out) {
   if (n <= naive_max()) return launch_msm_batched(ctx, d_s, d_p, d_off01n, 1, n, d_out);
-#if defined(SNARKV_CURVE_PALLAS)
-  return launch_msm_pippenger(ctx, d_s, d_p, n, 0, d_out, false);  // the pasta build has no chunk pipeline (capi.hip)
-#else
   return launch_msm_pippenger_auto(ctx, d_s, d_p, n, 0, d_out, false);  // the product path of snarkv_g1_msm_pippenger_dev
-#endif
 }
 
 }  // namespace snarkv

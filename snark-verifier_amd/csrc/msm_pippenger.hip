@@ -1081,7 +1081,7 @@ int launch_msm_pippenger(snarkv_ctx* ctx, const void* d_scalars, const void* d_p
 }
 
 // The same launch cut into its three phases, each enqueued on a stream of the caller's choice (the batch scheduler of
-// capi.hip runs the phases of MANY MSMs in phase order):
+// msm_api.hip runs the phases of MANY MSMs in phase order):
 //   PIP_PHASE_SORT  P0-S5  prepare, scan, partition + sort, piece schedule  (reads the inputs, fills ctx's scratch)
 //   PIP_PHASE_ACC   P4-P5  bucket accumulation + fix-up                     (scratch -> bucket grid)
 //   PIP_PHASE_TAIL  P6-P9  bucket reduce, shift chains, final            (bucket grid -> d_out)

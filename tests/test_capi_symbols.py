@@ -70,6 +70,30 @@ def test_pallas_library_exports_every_declared_symbol():
         assert e.value.code == -4
 
 
+@pytest.mark.parametrize("lib_name", ["libsnarkv_amd.so", "libsnarkv_pallas.so"])
+def test_library_exports_nothing_undeclared(lib_name):
+    """The other direction: a device library exports no snarkv_* / bn254_* / pallas_* name that no header under include/
+    declares.  With the tests above, which check that every declared name is exported, both ABIs are pinned exactly."""
+    import subprocess
+
+    import snark_verifier_amd as sv
+    from snark_verifier_amd import pallas as PL
+
+    path = sv.load_library()._name if lib_name == "libsnarkv_amd.so" else PL.load_library()._name
+    assert os.path.basename(path) == lib_name
+    declared = set()
+    for h in os.listdir(os.path.join(ROOT, "include")):
+        if h.endswith(".h"):
+            txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", h)).read(), flags=re.S)
+            declared |= set(re.findall(r"\b((?:snarkv|bn254|pallas)_[a-z0-9_]+)\s*\(", txt))
+    r = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    exported = {f[-1] for f in (line.split() for line in r.stdout.splitlines()) if f}
+    exported = {s for s in exported if re.match(r"(snarkv|bn254|pallas)_", s)}
+    assert exported, lib_name
+    assert sorted(exported - declared) == []
+
+
 def test_headers_are_plain_c_and_a_c_program_links(tmp_path):
     """The drop-in boundary is a C ABI: every header under include/ compiles as strict C99 (no C++ types, no torch types in
     a signature), and a C program that names one entry point of each family links against the libraries with gcc alone."""

@@ -74,7 +74,7 @@ def test_pippenger_2p20_every_supported_window_size_same_bytes(gpu_ctx):
 
 def test_config4_2p24_bit_exact_vs_c_oracle(gpu_ctx):
     """BASELINE config 4 at ITS size, bit for bit: 2^24 points on the bench seeds through the default path -- the only
-    size that takes the 16-chunk pipeline over shared bucket grids (capi.hip launch_msm_pippenger_auto) -- against the
+    size that takes the 16-chunk pipeline over shared bucket grids (msm_api.hip launch_msm_pippenger_auto) -- against the
     threaded C restatement of util/msm.rs:308-343 on every host core (~20 s on the GPU box's 256 threads), and the same
     expected bytes for the config's multi-GPU shape: 8 ranks x 2^21 points through `snarkv_g1_msm_pippenger_mgpu_dev`
     (ranks emulated on device 0), point-sharded and bucket-sharded ("bucket-sum allreduce")."""

@@ -120,7 +120,7 @@ def test_mgpu_decide_all_1024_sharded(world):
 
 def test_mgpu_large_shards_take_the_chunk_pipeline(gpu_ctx, monkeypatch):
     """Shards of more than 3 x 2^20 points run as the chunk pipeline over shared bucket grids INSIDE each rank
-    (capi.hip launch_msm_pippenger_auto): two ranks x (3 x 2^20 + 5) points == one single-launch MSM over all of them."""
+    (msm_api.hip launch_msm_pippenger_auto): two ranks x (3 x 2^20 + 5) points == one single-launch MSM over all of them."""
     import torch
 
     import snark_verifier_amd as sv

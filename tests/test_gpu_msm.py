@@ -319,7 +319,7 @@ def test_batched_chunked_scalar_mul_all_chunkings(gpu_ctx, golden_msm, chunks, m
 
 def test_large_msm_chunk_pipelined_form_matches_unsplit(gpu_ctx, monkeypatch):
     """n > 2^21 runs as 2^20-point chunks on worker lanes that add their bucket sums into shared grids, with ONE
-    bucket reduce / shift / to_affine at the end (capi.hip pippenger_maybe_split): same bytes as the single-launch
+    bucket reduce / shift / to_affine at the end (msm_api.hip launch_msm_pippenger_auto): same bytes as the single-launch
     form, for an exact multiple and a ragged size, affine result and projective partial."""
     import torch
 

@@ -1,6 +1,6 @@
 """GPU parity of the batch entry point `snarkv_g1_msm_pippenger_many_dev` (include/snarkv_amd.h): MANY independent
 `util::msm::multi_scalar_multiplication` calls (reference snark-verifier/src/util/msm.rs:308-343) in one call, pipelined
-by the library (csrc/capi.hip launch_msm_pippenger_many).  Every job must give the bytes of the single-MSM entry point
+by the library (csrc/msm_api.hip launch_msm_pippenger_many).  Every job must give the bytes of the single-MSM entry point
 and of the C oracle: uniform batches (one batched tail over grids laid end to end), ragged batches (per-job tails),
 several rounds, the projective-partial form, the fall-backs, the error codes."""
 import os

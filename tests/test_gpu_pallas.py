@@ -186,6 +186,24 @@ def test_native_loader_msm_on_pallas(pctx):
         pctx.msm_naive(PA.fe_to_bytes(PA.R), PA.g1_to_bytes(pts[0]), flags=sv.SNARKV_FLAG_VALIDATE)  # scalar >= r
 
 
+def test_pasta_entry_points_take_only_the_validate_flag(pctx):
+    """The pasta entry points honour SNARKV_FLAG_VALIDATE only (include/snarkv_pallas.h): SNARKV_FLAG_MONTGOMERY on
+    `msm_batched` / `msm_naive` leaves the wire form in force, so canonical inputs give the bytes of flags = 0."""
+    import snark_verifier_amd as sv
+
+    rnd = random.Random(21)
+    pts = PA.sample_points(7, 48)
+    sc = [rnd.randrange(PA.R) for _ in pts]
+    s, p = _pack(sc, pts)
+    offs = [0, 5, 17, 48]
+    plain = pctx.msm_batched(s, p, offs)
+    assert plain == b"".join(PA.g1_to_bytes(PA.g1_msm_naive(sc[a:b], pts[a:b])) for a, b in zip(offs, offs[1:]))
+    mont = sv.SNARKV_FLAG_MONTGOMERY
+    assert pctx.msm_batched(s, p, offs, flags=mont) == plain
+    assert pctx.msm_batched(s, p, offs, flags=mont | sv.SNARKV_FLAG_VALIDATE) == plain
+    assert pctx.msm_naive(s, p, flags=mont) == pctx.msm_naive(s, p)
+
+
 def test_ipa_succinct_check_msms_on_the_device(pctx, on_pallas):
     """The two `Msm::evaluate(None)` of `Ipa::succinct_verify` (pcs/ipa.rs:172,177) as ONE segmented device
     launch on pallas, fed by the oracle's transcript + scalar algebra: C_k == c[U] + v'[H']."""
