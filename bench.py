@@ -11,10 +11,17 @@ its own input arrays); for N > 1 every rank computes K projective partials, ONE
 all-gather moves K x 144 B per rank over RCCL/xGMI and every rank folds them to
 the same K affine points.  value = N * 2^20 * steps / wall time
 (max over ranks) -> weak scaling.  `--inflight N` keeps N single-MSM calls in
-flight instead (the round-1 way, for comparison); `config.single_msm_latency_ms`
-gives the strictly sequential figure.
+flight instead (the round-1 way, for comparison).
 
-Launch:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the
+outputs of `--dump-outputs`, the line.  `--full` adds everything else the benchmark
+measures or checks, each in runs of its own after the timed region: the strictly
+sequential latency (`config.single_msm_latency_ms`) and stage times, the rooflines, the
+host-resident batch, config 4 (strong scaling), the CPU baselines, the second metric and
+the end-to-end legs, the one-GPU recompute of a sharded result and the single-process
+multi-GPU leg.
+
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 Prints ONE JSON line on rank 0.
 """
@@ -1194,6 +1201,10 @@ def main():
     ap.add_argument("--no-mgpu-leg", action="store_true", help="skip the single-process snarkv_mgpu_* leg")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="after the timed steps, write the results of the timed path's last step to DIR/*.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else: latency, rooflines, host-resident batch, config 4, CPU baselines, "
+                         "second metric, end-to-end legs, one-GPU recompute, single-process multi-GPU leg (the --no-* options "
+                         "still skip parts of it)")
     ap.add_argument("--mgpu-leg", action="store_true",
                     help="INTERNAL: run only the single-process multi-GPU leg over devices 0..gpus-1 and print its JSON")
     args = ap.parse_args()
@@ -1289,6 +1300,7 @@ def main():
     # The second metric keeps AGG_JOBS_IN_FLIGHT aggregation jobs in flight on contexts of their own.  Their streams are
     # created FIRST: the runtime hands its hardware queues to streams in creation order, and 16 streams created after
     # others can end up sharing queues (tools/aggregate_inflight.py --dummy-streams 5: 0.22 -> 0.34 ms per 64-proof job)
+    # They are created without --full too, idle: the timed streams then land on the same hardware queues in either run.
     agg_streams, agg_ctxs = [], []
     if not dry and not use_dist and not args.no_secondary:
         agg_streams = [make_stream() for _ in range(AGG_JOBS_IN_FLIGHT)]
@@ -1430,9 +1442,9 @@ def main():
         else:
             dump_outputs(args.dump_outputs, slot_results[(step_no[0] - 1) % inflight])
 
-    # single-MSM latency (strictly sequential), outside the timed region, for the record
+    # --full: single-MSM latency (strictly sequential), outside the timed region, for the record
     lat_ms, seq_stages = None, None
-    if not dry:  # (local single-MSM calls: also on every rank of a multi-GPU run, outside its timed region)
+    if args.full and not dry:  # (local single-MSM calls: also on every rank of a multi-GPU run, outside its timed region)
         dev_sync()
         lat_out = torch.zeros(64, dtype=torch.uint8, device=dev)  # (its own buffer: `out` holds the job's result)
         # one caller, one MSM at a time: no hint
@@ -1458,7 +1470,7 @@ def main():
         seq_stages = {k: v / 5 for k, v in seq_sum.items()}
 
     host_res = None
-    if not use_dist and not dry and batch and not args.no_host_resident:
+    if args.full and not use_dist and not dry and batch and not args.no_host_resident:
         host_res = host_resident_metrics(sv, torch, ctx, d_scalars_k, d_points_k, n, args.steps, slot_results, nsets)
     rccl_ranks_seen = None
     if use_dist:
@@ -1471,9 +1483,9 @@ def main():
         rccl_ranks_seen = int(ones.item())
     result_hex = bytes(out.cpu().numpy()).hex()
 
-    # BASELINE config 4 (2^24 points IN TOTAL, strong scaling) in the same run, on every world size
+    # --full: BASELINE config 4 (2^24 points IN TOTAL, strong scaling) in the same run, on every world size
     strong_res = None
-    if not strong and not args.no_strong and batch and (not dry or args.strong_total_log2n < 20):
+    if args.full and not strong and not args.no_strong and batch and (not dry or args.strong_total_log2n < 20):
         for c in ctxs[1:]:
             c.sync()
         strong_res = strong_leg(torch, dist, sv, ctx, streams[0], world, rank, args.strong_total_log2n, max(2, min(args.steps, 5)),
@@ -1482,15 +1494,7 @@ def main():
     line = None
     if rank == 0:
         stages = {k: v / stage_cnt for k, v in stage_sum.items()}
-        dom = max((k for k in stages if k != "total"), key=lambda k: stages[k])
-        dom_ms = stages[dom]
         launch_n = launch_points(n, args.window_bits)  # n, or the 2^20-point chunk large MSMs are pipelined in
-        # the dominant kernel's per-launch duration: ONE launch alone on the GPU (sequential single-MSM calls, HIP events on
-        # the context's stream).  In the timed batch ~1.5 launches of it are co-resident, so an in-batch launch lasts longer
-        # than ms_per_step -- that stretched figure is kept as `frac_in_batch`; it is not the kernel's speed.
-        dom_alone_ms = (seq_stages or {}).get(dom, 0.0) or dom_ms
-        achieved = BYTES_PER_POINT * launch_n / (dom_alone_ms * 1e-3) / 1e9
-        achieved_in_batch = BYTES_PER_POINT * launch_n / (dom_ms * 1e-3) / 1e9
         line = {
             "metric": "BN254 G1 MSM points/sec at 2^%d" % (args.total_log2n if strong else args.log2n),
             "value": world * n * args.steps / dt,
@@ -1538,7 +1542,18 @@ def main():
                     "rccl_env": {k: os.environ.get(k) for k in ("NCCL_SOCKET_IFNAME", "NCCL_IB_DISABLE", "HSA_ENABLE_IPC_MODE_LEGACY")}},
                 "result": result_hex,
             },
-            "roofline": {
+            "stages_ms": stages,
+        }
+        if args.full:  # everything beyond the headline, each in runs of its own
+            dom = max((k for k in stages if k != "total"), key=lambda k: stages[k])
+            dom_ms = stages[dom]
+            # the dominant kernel's per-launch duration: ONE launch alone on the GPU (sequential single-MSM calls, HIP events on
+            # the context's stream).  In the timed batch ~1.5 launches of it are co-resident, so an in-batch launch lasts longer
+            # than ms_per_step -- that stretched figure is kept as `frac_in_batch`; it is not the kernel's speed.
+            dom_alone_ms = (seq_stages or {}).get(dom, 0.0) or dom_ms
+            achieved = BYTES_PER_POINT * launch_n / (dom_alone_ms * 1e-3) / 1e9
+            achieved_in_batch = BYTES_PER_POINT * launch_n / (dom_ms * 1e-3) / 1e9
+            line["roofline"] = {
                 "bound": "hbm",
                 "kernel": "stage '%s'" % dom,
                 "achieved": achieved,
@@ -1558,154 +1573,152 @@ def main():
                         "launch on the GPU (`kernel_ms`, <= ms_per_step); `*_in_batch`: the same launch inside the timed region, "
                         "stretched by the %s launches of its kind that share the GPU there.  The path is integer-VALU-bound "
                         "(~160 Fq products per point), see DESIGN.md section 4" % (launch_n, "~1.5" if batch else str(inflight)),
-            },
-            "stages_ms": stages,
-        }
-        # HBM-side traffic of the dominant kernel: rocprofv3 PMC (tools/pmc_traffic.py: separate FETCH_SIZE / WRITE_SIZE
-        # passes, gfx950 correction 2 x FETCH + WRITE), quoted only from a record taken on the kernels of this tree
-        pmc, where = _profile_record("r*_pmc_hbm_traffic%s.json" % ("" if args.log2n == 20 else "_2p%d" % args.log2n))
-        kname = {"bucket_accumulate": "k_accumulate"}.get(dom)
-        if pmc and kname in pmc["kernels"]:
-            k = pmc["kernels"][kname]
-            line["roofline"]["traffic"] = k["bytes_corrected"]
-            line["roofline"]["traffic_as_counted"] = k["bytes_as_counted"]
-            line["roofline"]["traffic_fetch_factor"] = k.get("fetch_factor")
-            line["roofline"]["traffic_source"] = where + " (kernel_source_hash %s)" % pmc["kernel_source_hash"]
-            # the kernel's own byte accounting: one 64-byte point gather + one 8-byte entry per (half-scalar, window), the
-            # run partials and the bucket grid written once
-            Wn = -(-128 // 16) if not args.window_bits else -(-128 // args.window_bits)
-            entries = 2 * launch_n * Wn
-            model = entries * 72 + (entries // 96 + 1) * 288 + Wn * (1 << 15) * 144
-            line["roofline"]["traffic_model_bytes"] = model
-            line["roofline"]["traffic_over_algorithmic"] = k["bytes_corrected"] / (BYTES_PER_POINT * launch_n)
-            line["roofline"]["traffic_note"] = (
-                "per launch of k_accumulate, fabric side of L2 (Infinity-Cache hits included).  FETCH_SIZE on gfx950 tallies the "
-                "128-byte requests of wide coalesced reads at 64 B (x2, calibrated on k_prepare's 96 B/point stream: see the "
-                "record) but counts this kernel's 64-byte point gathers as they are (x1): the figure agrees with the byte "
-                "model (%d entries x (64 + 8) B + partials + grid = %.2f GB) within ~20 %%.  ~%.0fx the 96 B/point input: every "
-                "Montgomery point is gathered once per window -- inherent to bucket accumulation, not re-reads of the input"
-                % (entries, model / 1e9, k["bytes_corrected"] / (BYTES_PER_POINT * launch_n)))
-        else:
-            line["roofline"]["traffic_source"] = where if not pmc else "record has no %s" % kname
-        # the same kernel's average duration in the tracked rocprofv3 summary (tools/collect_profiles.sh writes the CSV and a
-        # sidecar with the kernel-source hash): `kernel_ms` above is THIS run's HIP events, `kernel_us_profile` the profile's
-        prof, pwhere = _profile_record("r*_kernel_stats_sequential.json")
-        if prof and kname in prof.get("kernels", {}):
-            pk = prof["kernels"][kname]
-            line["roofline"]["kernel_us_profile"] = pk["avg_us"]
-            line["roofline"]["kernel_us_profile_calls"] = pk.get("calls")
-            line["roofline"]["kernel_us_profile_source"] = "%s <- %s (kernel_source_hash %s)" % (pwhere, prof.get("csv"), prof["kernel_source_hash"])
-            line["roofline"]["frac_from_profile"] = BYTES_PER_POINT * launch_n / (pk["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBPS
-        else:
-            line["roofline"]["kernel_us_profile"] = None
-            line["roofline"]["kernel_us_profile_source"] = pwhere if not prof else "record has no %s" % kname
-        # issue roofline of the dominant kernel from its ISA (tools/isa_stats.py), same hash rule
-        isa, iwhere = _profile_record("r*_isa_k_accumulate.json")
-        if isa:
-            line["issue_roofline"] = {
-                "kernel": "k_accumulate", "mads_per_entry": isa["mads_per_entry"], "instr_per_entry": isa["instr_per_entry"],
-                "frac": isa["useful_issue_fraction"], "source": iwhere,
-                "note": "static ISA census of the accumulate loop: v_mad_i64_i32 (the 29 x 29-bit partial products) per issued "
-                        "instruction; on gfx950 every instruction of this mix costs one ~4.2-cycle issue slot "
-                        "(profiles/r02_ubench_issue.txt), so this is the fraction of issue slots doing arithmetic that the "
-                        "algorithm needs",
             }
-        else:
-            line["issue_roofline"] = {"kernel": "k_accumulate", "frac": None, "source": iwhere}
-        if not use_dist:
-            # Integer-VALU roofline (the binding constraint): the same
-            # mixed addition as k_accumulate in isolation, 4 waves/SIMD on every CU.
-            W = -(-128 // 16) if not args.window_bits else -(-128 // args.window_bits)
-            adds = 2.0 * launch_n * W  # one bucket addition per (half-scalar, window) of the points one launch covers
-            peak_madd = ctx.ubench_valu(1, 300)
-            peak_mul = ctx.ubench_valu(0, 2000)
-            acc_ms = (seq_stages or stages).get("bucket_accumulate", 0.0)
-            if acc_ms > 0:
-                line["valu_roofline"] = {
-                    "kernel": "k_accumulate", "unit": "G1 mixed additions/s",
-                    "achieved": adds / (acc_ms * 1e-3), "peak": peak_madd,
-                    "frac": adds / (acc_ms * 1e-3) / peak_madd,
-                    "peak_fq_mul_per_s": peak_mul,
-                    "note": "peak = xyzz29_madd_fast chains with no memory traffic, measured live "
-                            "(snarkv_ubench_valu); achieved uses the unshared (sequential) launch duration",
+            # HBM-side traffic of the dominant kernel: rocprofv3 PMC (tools/pmc_traffic.py: separate FETCH_SIZE / WRITE_SIZE
+            # passes, gfx950 correction 2 x FETCH + WRITE), quoted only from a record taken on the kernels of this tree
+            pmc, where = _profile_record("r*_pmc_hbm_traffic%s.json" % ("" if args.log2n == 20 else "_2p%d" % args.log2n))
+            kname = {"bucket_accumulate": "k_accumulate"}.get(dom)
+            if pmc and kname in pmc["kernels"]:
+                k = pmc["kernels"][kname]
+                line["roofline"]["traffic"] = k["bytes_corrected"]
+                line["roofline"]["traffic_as_counted"] = k["bytes_as_counted"]
+                line["roofline"]["traffic_fetch_factor"] = k.get("fetch_factor")
+                line["roofline"]["traffic_source"] = where + " (kernel_source_hash %s)" % pmc["kernel_source_hash"]
+                # the kernel's own byte accounting: one 64-byte point gather + one 8-byte entry per (half-scalar, window), the
+                # run partials and the bucket grid written once
+                Wn = -(-128 // 16) if not args.window_bits else -(-128 // args.window_bits)
+                entries = 2 * launch_n * Wn
+                model = entries * 72 + (entries // 96 + 1) * 288 + Wn * (1 << 15) * 144
+                line["roofline"]["traffic_model_bytes"] = model
+                line["roofline"]["traffic_over_algorithmic"] = k["bytes_corrected"] / (BYTES_PER_POINT * launch_n)
+                line["roofline"]["traffic_note"] = (
+                    "per launch of k_accumulate, fabric side of L2 (Infinity-Cache hits included).  FETCH_SIZE on gfx950 tallies the "
+                    "128-byte requests of wide coalesced reads at 64 B (x2, calibrated on k_prepare's 96 B/point stream: see the "
+                    "record) but counts this kernel's 64-byte point gathers as they are (x1): the figure agrees with the byte "
+                    "model (%d entries x (64 + 8) B + partials + grid = %.2f GB) within ~20 %%.  ~%.0fx the 96 B/point input: every "
+                    "Montgomery point is gathered once per window -- inherent to bucket accumulation, not re-reads of the input"
+                    % (entries, model / 1e9, k["bytes_corrected"] / (BYTES_PER_POINT * launch_n)))
+            else:
+                line["roofline"]["traffic_source"] = where if not pmc else "record has no %s" % kname
+            # the same kernel's average duration in the tracked rocprofv3 summary (tools/collect_profiles.sh writes the CSV and a
+            # sidecar with the kernel-source hash): `kernel_ms` above is THIS run's HIP events, `kernel_us_profile` the profile's
+            prof, pwhere = _profile_record("r*_kernel_stats_sequential.json")
+            if prof and kname in prof.get("kernels", {}):
+                pk = prof["kernels"][kname]
+                line["roofline"]["kernel_us_profile"] = pk["avg_us"]
+                line["roofline"]["kernel_us_profile_calls"] = pk.get("calls")
+                line["roofline"]["kernel_us_profile_source"] = "%s <- %s (kernel_source_hash %s)" % (pwhere, prof.get("csv"), prof["kernel_source_hash"])
+                line["roofline"]["frac_from_profile"] = BYTES_PER_POINT * launch_n / (pk["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBPS
+            else:
+                line["roofline"]["kernel_us_profile"] = None
+                line["roofline"]["kernel_us_profile_source"] = pwhere if not prof else "record has no %s" % kname
+            # issue roofline of the dominant kernel from its ISA (tools/isa_stats.py), same hash rule
+            isa, iwhere = _profile_record("r*_isa_k_accumulate.json")
+            if isa:
+                line["issue_roofline"] = {
+                    "kernel": "k_accumulate", "mads_per_entry": isa["mads_per_entry"], "instr_per_entry": isa["instr_per_entry"],
+                    "frac": isa["useful_issue_fraction"], "source": iwhere,
+                    "note": "static ISA census of the accumulate loop: v_mad_i64_i32 (the 29 x 29-bit partial products) per issued "
+                            "instruction; on gfx950 every instruction of this mix costs one ~4.2-cycle issue slot "
+                            "(profiles/r02_ubench_issue.txt), so this is the fraction of issue slots doing arithmetic that the "
+                            "algorithm needs",
                 }
-        if inflight > 1 and dom_ms > 0:
-            # launches of the dominant kernel overlap in the timed region (that overlap is what the in-flight mode is for), so a
-            # launch's duration stretches with the number of its kind resident at once: sum of launch durations / wall time
-            conc = dom_ms * args.steps / (dt * 1e3)
-            line["roofline"]["launches_resident_on_average"] = conc
-            line["roofline"]["overlap_note"] = (
-                "with %s %.2f launches of this kernel share the GPU on average in the timed region, so an in-batch launch lasts "
-                "%.2f ms (> ms_per_step) -- `frac_in_batch`; `frac` uses the launch alone (%.3f ms)"
-                % ("a batch's accumulations on three streams" if batch else "%d MSMs in flight" % inflight, conc, dom_ms, dom_alone_ms))
-        if seq_stages:
-            dseq = seq_stages.get(dom, 0.0)
-            line["stages_ms_sequential"] = seq_stages
-            if dseq > 0:  # (kept under the round-2 / round-3 names too: the same numbers as `achieved` / `frac`)
-                line["roofline"]["achieved_unshared"] = BYTES_PER_POINT * launch_n / (dseq * 1e-3) / 1e9
-                line["roofline"]["frac_unshared"] = line["roofline"]["achieved_unshared"] / HBM_PEAK_GBPS
-        if not args.no_cpu_baseline and world == 1:
-            cb, cpu_out, (s, p) = cpu_baseline(ctx, d_scalars, d_points, min(args.cpu_sample_log2 or args.log2n, args.log2n))
-            # the GPU must agree with the CPU restatement on that same sample
-            m = len(s) // 32
-            chk = torch.zeros(64, dtype=torch.uint8, device="cuda")
-            torch.cuda.synchronize()
-            ctx.msm_pippenger_dev(d_scalars.data_ptr(), d_points.data_ptr(), m, chk.data_ptr(), 0)
-            ctx.sync()
-            cb["gpu_matches_on_sample"] = bytes(chk.cpu().numpy()) == cpu_out
-            cb["sample_is_the_whole_workload"] = m == n
-            line["cpu_baseline"] = cb
-        if host_res:
-            line["host_resident"] = host_res
-        if not use_dist and not args.no_secondary:
-            line["secondary"] = secondary_metrics(sv, torch, agg_ctxs, cpu=not args.no_cpu_baseline)
-            line["secondary"]["aggregate_64_proofs_context_free_16_threads"] = context_free_metrics(sv)
-            line["secondary"]["aggregate_1024_proofs_context_free_16_threads"] = context_free_metrics(sv, nproofs=1024)
-            e2e = end_to_end_metrics()
-            if e2e:
-                line["secondary"].update(e2e)
-            # LAST key of the line (a log tail keeps it): the named BASELINE configs, ONE job at a time, then the others
-            sec = line["secondary"]
-            line["named_configs"] = {
-                "msm_2p%d_points_per_s" % args.log2n: line["value"],
-                "aggregate_64_proofs_one_job_ms": sec.get("aggregate_64_proofs", {}).get("ms"),
-                "aggregate_1024_proofs_one_job_ms": sec.get("aggregate_1024_proofs", {}).get("ms"),
-                "decide_all_1_ms": sec.get("decide_all_1", {}).get("ms"),
-                # config 5 (1 024 distinct proofs from proof bytes to the verdict, median of 25 calls): the reference example's own
-                # transcripts first (Poseidon for the snarks and the accumulation proof), the Keccak route beside it
-                "end_to_end_aggregate_1024_distinct_proofs_poseidon_ms": sec.get("end_to_end_aggregate_1024_distinct_proofs_poseidon", {}).get("ms"),
-                "end_to_end_aggregate_1024_distinct_proofs_keccak_ms": sec.get("end_to_end_aggregate_1024_distinct_proofs", {}).get("ms"),
-                "end_to_end_aggregate_64_proofs_bdfg21_poseidon_ms": sec.get("end_to_end_aggregate_64_proofs_bdfg21_poseidon", {}).get("ms"),
-                "host_resident_points_per_s": (host_res or {}).get("value"),
-                "NOT_one_job (16 jobs in flight / merged, proofs per s)": {
-                    "aggregate_64_proofs_pipelined": sec.get("aggregate_64_proofs_pipelined", {}).get("proofs_per_s"),
-                    "aggregate_64_proofs_context_free_16_threads": sec.get("aggregate_64_proofs_context_free_16_threads", {}).get("proofs_per_s"),
-                    "aggregate_64_proofs_merged": sec.get("aggregate_64_proofs_merged", {}).get("proofs_per_s"),
-                    "aggregate_1024_proofs_pipelined": sec.get("aggregate_1024_proofs_pipelined", {}).get("proofs_per_s"),
-                    "aggregate_1024_proofs_context_free_16_threads": sec.get("aggregate_1024_proofs_context_free_16_threads", {}).get("proofs_per_s"),
-                    "aggregate_1024_proofs_merged": sec.get("aggregate_1024_proofs_merged", {}).get("proofs_per_s")},
-            }
-        if use_dist and not dry and world > 1 and batch:
-            # the N-GPU result against ONE GPU: rank 0 samples job 0's points of ALL ranks ([0, N n) of the seeded streams)
-            # and reduces them alone
-            s_all = torch.empty(32 * n * world, dtype=torch.uint8, device=dev)
-            p_all = torch.empty(64 * n * world, dtype=torch.uint8, device=dev)
-            o_all = torch.zeros(64, dtype=torch.uint8, device=dev)
-            dev_sync()
-            ctx.sample_scalars_dev(0x5EED0001, n * world, s_all.data_ptr(), first=0)
-            ctx.sample_points_dev(0x5EED0002, n * world, p_all.data_ptr(), first=0)
-            ctx.msm_pippenger_dev(s_all.data_ptr(), p_all.data_ptr(), n * world, o_all.data_ptr(), args.window_bits)
-            ctx.sync()
-            line["config"]["result_matches_one_gpu_recompute"] = bytes(o_all.cpu().numpy()).hex() == result_hex
-            del s_all, p_all
-        if strong_res is not None:
-            line["config4_strong"] = strong_res
+            else:
+                line["issue_roofline"] = {"kernel": "k_accumulate", "frac": None, "source": iwhere}
+            if not use_dist:
+                # Integer-VALU roofline (the binding constraint): the same
+                # mixed addition as k_accumulate in isolation, 4 waves/SIMD on every CU.
+                W = -(-128 // 16) if not args.window_bits else -(-128 // args.window_bits)
+                adds = 2.0 * launch_n * W  # one bucket addition per (half-scalar, window) of the points one launch covers
+                peak_madd = ctx.ubench_valu(1, 300)
+                peak_mul = ctx.ubench_valu(0, 2000)
+                acc_ms = (seq_stages or stages).get("bucket_accumulate", 0.0)
+                if acc_ms > 0:
+                    line["valu_roofline"] = {
+                        "kernel": "k_accumulate", "unit": "G1 mixed additions/s",
+                        "achieved": adds / (acc_ms * 1e-3), "peak": peak_madd,
+                        "frac": adds / (acc_ms * 1e-3) / peak_madd,
+                        "peak_fq_mul_per_s": peak_mul,
+                        "note": "peak = xyzz29_madd_fast chains with no memory traffic, measured live "
+                                "(snarkv_ubench_valu); achieved uses the unshared (sequential) launch duration",
+                    }
+            if inflight > 1 and dom_ms > 0:
+                # launches of the dominant kernel overlap in the timed region (that overlap is what the in-flight mode is for), so a
+                # launch's duration stretches with the number of its kind resident at once: sum of launch durations / wall time
+                conc = dom_ms * args.steps / (dt * 1e3)
+                line["roofline"]["launches_resident_on_average"] = conc
+                line["roofline"]["overlap_note"] = (
+                    "with %s %.2f launches of this kernel share the GPU on average in the timed region, so an in-batch launch lasts "
+                    "%.2f ms (> ms_per_step) -- `frac_in_batch`; `frac` uses the launch alone (%.3f ms)"
+                    % ("a batch's accumulations on three streams" if batch else "%d MSMs in flight" % inflight, conc, dom_ms, dom_alone_ms))
+            if seq_stages:
+                dseq = seq_stages.get(dom, 0.0)
+                line["stages_ms_sequential"] = seq_stages
+                if dseq > 0:  # (kept under the round-2 / round-3 names too: the same numbers as `achieved` / `frac`)
+                    line["roofline"]["achieved_unshared"] = BYTES_PER_POINT * launch_n / (dseq * 1e-3) / 1e9
+                    line["roofline"]["frac_unshared"] = line["roofline"]["achieved_unshared"] / HBM_PEAK_GBPS
+            if not args.no_cpu_baseline and world == 1:
+                cb, cpu_out, (s, p) = cpu_baseline(ctx, d_scalars, d_points, min(args.cpu_sample_log2 or args.log2n, args.log2n))
+                # the GPU must agree with the CPU restatement on that same sample
+                m = len(s) // 32
+                chk = torch.zeros(64, dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()
+                ctx.msm_pippenger_dev(d_scalars.data_ptr(), d_points.data_ptr(), m, chk.data_ptr(), 0)
+                ctx.sync()
+                cb["gpu_matches_on_sample"] = bytes(chk.cpu().numpy()) == cpu_out
+                cb["sample_is_the_whole_workload"] = m == n
+                line["cpu_baseline"] = cb
+            if host_res:
+                line["host_resident"] = host_res
+            if not use_dist and not args.no_secondary:
+                line["secondary"] = secondary_metrics(sv, torch, agg_ctxs, cpu=not args.no_cpu_baseline)
+                line["secondary"]["aggregate_64_proofs_context_free_16_threads"] = context_free_metrics(sv)
+                line["secondary"]["aggregate_1024_proofs_context_free_16_threads"] = context_free_metrics(sv, nproofs=1024)
+                e2e = end_to_end_metrics()
+                if e2e:
+                    line["secondary"].update(e2e)
+                # LAST key of the line (a log tail keeps it): the named BASELINE configs, ONE job at a time, then the others
+                sec = line["secondary"]
+                line["named_configs"] = {
+                    "msm_2p%d_points_per_s" % args.log2n: line["value"],
+                    "aggregate_64_proofs_one_job_ms": sec.get("aggregate_64_proofs", {}).get("ms"),
+                    "aggregate_1024_proofs_one_job_ms": sec.get("aggregate_1024_proofs", {}).get("ms"),
+                    "decide_all_1_ms": sec.get("decide_all_1", {}).get("ms"),
+                    # config 5 (1 024 distinct proofs from proof bytes to the verdict, median of 25 calls): the reference example's own
+                    # transcripts first (Poseidon for the snarks and the accumulation proof), the Keccak route beside it
+                    "end_to_end_aggregate_1024_distinct_proofs_poseidon_ms": sec.get("end_to_end_aggregate_1024_distinct_proofs_poseidon", {}).get("ms"),
+                    "end_to_end_aggregate_1024_distinct_proofs_keccak_ms": sec.get("end_to_end_aggregate_1024_distinct_proofs", {}).get("ms"),
+                    "end_to_end_aggregate_64_proofs_bdfg21_poseidon_ms": sec.get("end_to_end_aggregate_64_proofs_bdfg21_poseidon", {}).get("ms"),
+                    "host_resident_points_per_s": (host_res or {}).get("value"),
+                    "NOT_one_job (16 jobs in flight / merged, proofs per s)": {
+                        "aggregate_64_proofs_pipelined": sec.get("aggregate_64_proofs_pipelined", {}).get("proofs_per_s"),
+                        "aggregate_64_proofs_context_free_16_threads": sec.get("aggregate_64_proofs_context_free_16_threads", {}).get("proofs_per_s"),
+                        "aggregate_64_proofs_merged": sec.get("aggregate_64_proofs_merged", {}).get("proofs_per_s"),
+                        "aggregate_1024_proofs_pipelined": sec.get("aggregate_1024_proofs_pipelined", {}).get("proofs_per_s"),
+                        "aggregate_1024_proofs_context_free_16_threads": sec.get("aggregate_1024_proofs_context_free_16_threads", {}).get("proofs_per_s"),
+                        "aggregate_1024_proofs_merged": sec.get("aggregate_1024_proofs_merged", {}).get("proofs_per_s")},
+                }
+            if use_dist and not dry and world > 1 and batch:
+                # the N-GPU result against ONE GPU: rank 0 samples job 0's points of ALL ranks ([0, N n) of the seeded streams)
+                # and reduces them alone
+                s_all = torch.empty(32 * n * world, dtype=torch.uint8, device=dev)
+                p_all = torch.empty(64 * n * world, dtype=torch.uint8, device=dev)
+                o_all = torch.zeros(64, dtype=torch.uint8, device=dev)
+                dev_sync()
+                ctx.sample_scalars_dev(0x5EED0001, n * world, s_all.data_ptr(), first=0)
+                ctx.sample_points_dev(0x5EED0002, n * world, p_all.data_ptr(), first=0)
+                ctx.msm_pippenger_dev(s_all.data_ptr(), p_all.data_ptr(), n * world, o_all.data_ptr(), args.window_bits)
+                ctx.sync()
+                line["config"]["result_matches_one_gpu_recompute"] = bytes(o_all.cpu().numpy()).hex() == result_hex
+                del s_all, p_all
+            if strong_res is not None:
+                line["config4_strong"] = strong_res
 
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if not dry and not args.no_mgpu_leg:
+        if args.full and not dry and not args.no_mgpu_leg:
             # the single-process form of the same batch (snarkv_mgpu_*), in a process of its own, after the ranks have left
             if use_dist:
                 time.sleep(2.0)  # the other ranks' processes release their GPUs

@@ -85,14 +85,26 @@ def test_plain_launch_without_torchrun_starts_the_ranks_itself():
 
 
 def test_config4_strong_leg_rides_in_the_same_run():
-    """the weak line and BASELINE config 4 (2^k points IN TOTAL over the ranks) come out of ONE run"""
-    d = _run(2, ["--steps", "2", "--warmup", "1", "--log2n", "7", "--strong-total-log2n", "9"], 39000 + os.getpid() % 1000)
+    """with --full, the weak line and BASELINE config 4 (2^k points IN TOTAL over the ranks) come out of ONE run"""
+    d = _run(2, ["--steps", "2", "--warmup", "1", "--log2n", "7", "--strong-total-log2n", "9", "--full"], 39000 + os.getpid() % 1000)
     assert d["scaling"] == "weak"
     c4 = d["config4_strong"]
     assert c4["scaling"] == "strong" and c4["n_gpus"] == 2 and c4["points_per_gpu"] == 256
     assert abs(c4["value"] - 512 * c4["steps"] / (c4["ms_per_step"] * c4["steps"] * 1e-3)) < 1e-6 * c4["value"]
     s, p = C.sample_scalars(0x5EED0011, 512), C.sample_points(0x5EED0012, 512)
     assert c4["result"] == C.msm_pippenger(s, p, 4).hex()
+
+
+def test_a_plain_run_is_the_headline_alone():
+    """without --full the run stops at the headline: no config 4 leg, no roofline, no latency -- the same weak line"""
+    log2n, steps = 7, 2
+    d = _run(2, ["--steps", str(steps), "--warmup", "1", "--log2n", str(log2n), "--strong-total-log2n", "9"], 39500 + os.getpid() % 1000)
+    assert d["scaling"] == "weak" and d["n_gpus"] == 2 and d["steps"] == steps
+    for k in ("config4_strong", "roofline", "issue_roofline", "stages_ms_sequential", "single_process_mgpu"):
+        assert k not in d and k not in d["_compact"], k
+    assert d["config"]["single_msm_latency_ms"] is None and "result_matches_one_gpu_recompute" not in d["config"]
+    s, p = C.sample_scalars(0x5EED0001, 2 << log2n), C.sample_points(0x5EED0002, 2 << log2n)
+    assert d["config"]["result"] == C.msm_pippenger(s, p, 4).hex()
 
 
 def test_rccl_probe_failure_makes_every_rank_fall_back_to_gloo():

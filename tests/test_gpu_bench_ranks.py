@@ -29,7 +29,7 @@ def test_plain_launch_n_ranks_one_device_measures_and_says_how(tmp_path, ranks):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["SNARKV_BENCH_RCCL_PROBE_TIMEOUT"] = "120"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", str(steps), "--warmup", "1", "--log2n", str(log2n),
-           "--strong-total-log2n", "16", "--no-cpu-baseline", "--no-secondary"]
+           "--strong-total-log2n", "16", "--no-cpu-baseline", "--no-secondary", "--full"]
     env["SNARKV_BENCH_DETAILS"] = os.path.join(str(tmp_path), "details.json")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -84,13 +84,13 @@ def test_rccl_data_plane_at_world_one_and_the_line_is_the_last_line(tmp_path):
 
 
 def test_the_default_line_keeps_the_drivers_contract(tmp_path):
-    """`python bench.py` (N = 1, small size here): ONE JSON line, the last of stdout, with every key the driver's contract
+    """`python bench.py --full` (N = 1, small size here): ONE JSON line, the last of stdout, with every key the driver's contract
     names -- metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype /
     data / config.workload (no model keys), `roofline` {bound, achieved, peak, unit, frac, traffic} and `cpu_baseline`
     {value, unit, cores, kind, sample} -- and the GPU agreeing with the CPU restatement on the whole workload."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--log2n", "14", "--no-secondary", "--no-host-resident",
-           "--strong-total-log2n", "16"]
+           "--strong-total-log2n", "16", "--full"]
     env["SNARKV_BENCH_DETAILS"] = os.path.join(str(tmp_path), "details.json")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -110,6 +110,34 @@ def test_the_default_line_keeps_the_drivers_contract(tmp_path):
     assert all(k in cb for k in ("value", "unit", "cores", "kind", "sample")) and cb["kind"] == "port"
     assert cb["gpu_matches_on_sample"] is True and cb["sample_is_the_whole_workload"] is True
     assert d["config4_strong"]["matches_one_gpu_single_call"] is True and d["single_process_mgpu"]["job0_matches_one_gpu_recompute"] is True
+
+
+def test_a_plain_run_is_the_headline_alone(tmp_path):
+    """`python bench.py` without --full: set-up, warm-up, the timed steps, --dump-outputs and the line -- nothing after
+    them (no latency, roofline, CPU baseline, config 4 or multi-GPU leg); the dumped batch agrees with the line's result
+    and job 0 with the C oracle."""
+    import numpy as np
+
+    log2n, steps = 14, 4
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["SNARKV_BENCH_DETAILS"] = os.path.join(str(tmp_path), "details.json")
+    dump = os.path.join(str(tmp_path), "dump")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--log2n", str(log2n),
+           "--strong-total-log2n", "16", "--dump-outputs", dump]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d, full = bench_line.parse(r.stdout)
+    assert d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == 1 and d["higher_is_better"] is True and d["unit"] == "points/s"
+    assert abs(d["value"] - (1 << log2n) * steps / (d["ms_per_step"] * steps * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "issue_roofline", "valu_roofline", "stages_ms_sequential", "cpu_baseline", "host_resident", "secondary",
+              "named_configs", "config4_strong", "single_process_mgpu"):
+        assert k not in full, k
+    assert full["config"]["single_msm_latency_ms"] is None and "stages_ms" in full
+    batch = np.load(os.path.join(dump, "msm_batch_results.npy")).astype(np.uint8)
+    last = np.load(os.path.join(dump, "msm_result.npy")).astype(np.uint8)
+    assert batch.shape == (steps, 64) and bytes(batch[-1]) == bytes(last) and bytes(batch[0]).hex() == full["config"]["result"]
+    n = 1 << log2n
+    assert full["config"]["result"] == C.msm_pippenger(C.sample_scalars(0x5EED0001, n), C.sample_points(0x5EED0002, n), 8).hex()
 
 
 def test_single_process_mgpu_leg_with_eight_emulated_ranks():

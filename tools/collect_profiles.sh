@@ -23,20 +23,20 @@ stats() {  # name, bench args...
   if [ -n "$db" ]; then python $R/tools/rocpd_top_kernels.py $db $O/${TAG}_rocprofv3_kernel_stats_$name.csv; else
     f=$(find /tmp/prof_$name -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${TAG}_rocprofv3_kernel_stats_$name.csv; fi
 }
-stats batch --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-host-resident --no-strong --no-mgpu-leg
-stats sequential --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --inflight 1 --no-strong --no-mgpu-leg
+stats batch --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary --no-host-resident --no-strong --no-mgpu-leg
+stats sequential --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary --inflight 1 --no-strong --no-mgpu-leg
 # the hash sidecar bench.py reads `kernel_us_profile` from (keyed to THESE sources), into profiles/ of this tree
 cp $O/${TAG}_rocprofv3_kernel_stats_sequential.csv $R/profiles/ && python $R/tools/stats_sidecar.py $R/profiles/${TAG}_rocprofv3_kernel_stats_sequential.csv \
   && cp $R/profiles/${TAG}_kernel_stats_sequential.json $O/
-stats with_secondary --steps 4 --warmup 1 --no-cpu-baseline --no-host-resident --no-strong --no-mgpu-leg
-stats 2p24_single --log2n 24 --inflight 1 --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --no-strong --no-mgpu-leg
+stats with_secondary --steps 4 --warmup 1 --full --no-cpu-baseline --no-host-resident --no-strong --no-mgpu-leg
+stats 2p24_single --log2n 24 --inflight 1 --steps 4 --warmup 1 --full --no-cpu-baseline --no-secondary --no-strong --no-mgpu-leg
 cd $R
 # (the line bench.py prints is the compact contract line; the full record goes to the file SNARKV_BENCH_DETAILS names)
-SNARKV_BENCH_DETAILS=$O/${TAG}_bench_details.json timeout 600 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+SNARKV_BENCH_DETAILS=$O/${TAG}_bench_details.json timeout 600 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 export SNARKV_BENCH_DETAILS=$O/${TAG}_bench_details_other.json
-timeout 300 python bench.py --steps 40 --warmup 4 --no-secondary --no-cpu-baseline --no-strong --no-mgpu-leg > $O/${TAG}_bench_40steps.json 2>/dev/null
-timeout 300 python bench.py --log2n 22 --inflight 1 --steps 10 --warmup 2 --no-secondary --cpu-sample-log2 18 --no-strong --no-mgpu-leg > $O/${TAG}_bench_2p22.json 2>/dev/null
-timeout 300 python bench.py --log2n 24 --inflight 1 --steps 6 --warmup 2 --no-secondary --cpu-sample-log2 18 --no-strong --no-mgpu-leg > $O/${TAG}_bench_2p24.json 2>/dev/null
+timeout 300 python bench.py --steps 40 --warmup 4 --full --no-secondary --no-cpu-baseline --no-strong --no-mgpu-leg > $O/${TAG}_bench_40steps.json 2>/dev/null
+timeout 300 python bench.py --log2n 22 --inflight 1 --steps 10 --warmup 2 --full --no-secondary --cpu-sample-log2 18 --no-strong --no-mgpu-leg > $O/${TAG}_bench_2p22.json 2>/dev/null
+timeout 300 python bench.py --log2n 24 --inflight 1 --steps 6 --warmup 2 --full --no-secondary --cpu-sample-log2 18 --no-strong --no-mgpu-leg > $O/${TAG}_bench_2p24.json 2>/dev/null
 # every keyed record the main line quotes must be of THESE sources: fail loudly otherwise
 TAGV=$TAG python - <<'PY' || { echo "STALE PROFILE RECORDS: see above" | tee $O/${TAG}_STALE.txt; }
 import json, os, sys

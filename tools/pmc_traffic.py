@@ -32,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def one_pass(counter, log2n, out):
     cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", out, "--",
-           sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+           sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--no-secondary", "--inflight", "1", "--log2n", str(log2n)]
     env = dict(os.environ, TMPDIR="/tmp")
     subprocess.run(cmd, check=True, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
@@ -87,7 +87,7 @@ def main():
     rec = {
         "kernel_source_hash": h.kernel_source_hash(), "log2n": a.log2n,
         "command": "rocprofv3 --kernel-trace --pmc {FETCH_SIZE | WRITE_SIZE} (two passes) -- python bench.py --steps 3 --warmup 1 "
-                   "--no-cpu-baseline --no-secondary --inflight 1 --log2n %d" % a.log2n,
+                   "--full --no-cpu-baseline --no-secondary --inflight 1 --log2n %d" % a.log2n,
         "unit": "KiB per dispatch as reported; bytes_corrected = (fetch_factor x FETCH_SIZE + WRITE_SIZE) x 1024: factor 2 for "
                 "wide coalesced reads (gfx950 counts their 128-byte requests as 64 B), 1 for k_accumulate's 64-byte gathers; "
                 "Infinity-Cache hits included",
