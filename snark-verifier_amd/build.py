@@ -50,8 +50,11 @@ def build(verbose=False):
     os.makedirs(BUILD, exist_ok=True)
     # every unit of both libraries in one pool (hipcc is single-threaded per unit)
     jobs = [(u, (), "") for u in UNITS] + [(u, tuple(PALLAS_FLAGS), "_pallas") for u in PALLAS_UNITS]
-    with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(jobs) + len(DEVTEST_FLAVOURS), os.cpu_count() or 4)) as ex:
+        devtest = [ex.submit(build_devtest, f) for f in DEVTEST_FLAVOURS]  # the test-only device units ride in the same pool
         res = list(ex.map(lambda j: _compile(j[0], verbose, j[1], j[2]), jobs))
+        for d in devtest:
+            d.result()
     _link(LIB, res[:len(UNITS)], [])
     _link(PALLAS_LIB, res[len(UNITS):], ["-Wl,-Bsymbolic"])  # its internals never bind by symbol lookup across libraries
     build_host_driver()
@@ -71,6 +74,35 @@ def _link(lib, res, extra):
 PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
+
+
+# Test-only device unit (tests/devtest/devtest.hip: one kernel per field / group operation, raw limbs in and out), in four
+# flavours: both curves, each with the asm multiplier bodies and with the plain-C ones.  Compiled and linked in one step
+# with the library's own FLAGS, next to its source, so that the artefacts travel with the tree like the libraries do.
+DEVTEST_DIR = os.path.join(HERE, "..", "tests", "devtest")
+DEVTEST_FLAVOURS = {"bn254_asm": [], "bn254_c": ["-DSNARKV_NO_SMAD_ASM"],
+                    "pallas_asm": PALLAS_FLAGS, "pallas_c": PALLAS_FLAGS + ["-DSNARKV_NO_SMAD_ASM"]}
+
+
+def devtest_sources():
+    return [os.path.join(DEVTEST_DIR, "devtest.hip"), os.path.join(DEVTEST_DIR, "..", "hosttest", "curve_ops.h")]
+
+
+def devtest_lib(flavour):
+    return os.path.join(DEVTEST_DIR, "libdevtest_%s.so" % flavour)
+
+
+def build_devtest(flavour):
+    out = devtest_lib(flavour)
+    newest = max([_deps()] + [os.path.getmtime(f) for f in devtest_sources()])
+    if os.path.exists(out) and os.path.getmtime(out) >= newest:
+        return out
+    cmd = [HIPCC] + FLAGS + DEVTEST_FLAVOURS[flavour] + ["-shared", "-Wl,-Bsymbolic", "-o", out, devtest_sources()[0]]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout + r.stderr)
+        raise RuntimeError("hipcc failed for devtest %s" % flavour)
+    return out
 
 
 HOST = os.path.join(HERE, "host")

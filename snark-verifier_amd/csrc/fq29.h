@@ -15,11 +15,21 @@
 // Contract ("lazy" values):
 //   * value = sum l_i 2^(29 i), any integer in (-8p, 8p) congruent to the field
 //     element; limb 8 carries the sign/overflow.
-//   * mul(a, b) needs  9 * max|a_i| * max|b_j| < 2^63 - 2^61.2, i.e.
-//     max|a_i| * max|b_j| < 2^59.6 (one operand carry-normalised (< 2^29), the
-//     other up to 2^30.6; or both < 2^29.8).  Its result has limbs 0..7 in
-//     [0, 2^29) and value in (-p/8, p + p/8) for operands within (-8p, 8p)... see
-//     the bound notes at each call site in g1_29.h.
+//   * mul(a, b) needs every COLUMN of the product scanning loop inside int64:
+//       sum_i |a_i| |b_(k-i)|  +  (2^29 - 1) * sum_j p_j  +  carry (< 2^35)  <  2^63.
+//     The operand classes that meet it: one operand with |limb| <= 2^29 and the
+//     other up to 2^30.6, or both up to 2^29.8 (max|a_i| * max|b_j| <= 2^59.6),
+//     with limb 8 as small as a value within (-8p, 8p) makes it -- a column then
+//     holds at most eight wide products; NINE products of 2^59.6 would not fit
+//     (2^62.77 against 2^63 - 2^61.2 = 2^62.51).  Peak seen by the model at
+//     the widest operands: about 2^62.7 on both curves.
+//     Its result has limbs 0..7 in [0, 2^29) and value in  a*b/2^261 + [0, p):
+//     the exact quotient plus m*p/2^261 with the nine reduction digits m < 2^261.
+//     For operands anywhere in (-8p, 8p) that is (-0.38p, 1.38p) for BN254
+//     (2^261/p = 168) and (-p/2, 3p/2) for pallas (2^261/p = 128); the call
+//     sites in g1_29.h feed narrower operands and stay inside (-p/4, 5p/4).
+//     tests/fq29_model.py asserts the budget, the shape and that range on raw
+//     limbs, for the host build and the device builds.
 //   * add/sub/neg are limb-wise and never carry; `fq29_norm` re-normalises the
 //     limbs (value unchanged) when the next product needs it.
 //   * zero/equality tests mod p need `fq29_is_zero_mod_p` (canonicalising).
@@ -247,7 +257,8 @@ SNARKV_HD Fq29 fq29_sqr(const Fq29& a) {
 
 // Unique representative in [0, p), carry-normalised.
 // canonical limbs of a value y in (-p, 2p) whose limbs 0..7 are already in [0, 2^29) -- in particular any OUTPUT of
-// fq29_mul / fq29_mul2 / fq29_sqr (value in (-p/8, p + p/8)): one conditional +p, one conditional -p, no product
+// fq29_mul / fq29_mul2 / fq29_sqr of operands within (-8p, 8p) (value in (-p/2, 3p/2)): one conditional +p, one
+// conditional -p, no product
 SNARKV_HD Fq29 fq29_canon_of_product(const Fq29& y) {
   Fq29 t;
   int32_t neg = y.v[8] >> 31;  // all ones if negative
@@ -271,7 +282,7 @@ SNARKV_HD Fq29 fq29_canon_of_product(const Fq29& y) {
 }
 
 // canonical limbs of ANY lazy value (the contract's (-8p, 8p)): one Montgomery product by 2^261 (i.e. by `one`) squeezes
-// the value into (-p/8, 9p/8) without changing the residue (x * R * R^-1), then at most one +p and one -p
+// the value into (-p/16, p + p/16) without changing the residue (x * R * R^-1), then at most one +p and one -p
 SNARKV_HD Fq29 fq29_canon_residue(const Fq29& x) { return fq29_canon_of_product(fq29_mul(fq29_norm(x), fq29_one())); }
 
 SNARKV_HD bool fq29_is_zero_mod_p(const Fq29& x) { return fq29_limbs_all_zero(fq29_canon_residue(x)); }

@@ -16,8 +16,20 @@
 //   acc.x   carry-normalised, value in (-4p, 2p)
 //   acc.y   lazy difference of two N: |limb| < 2^29, value in (-2p, 2p)
 //   acc.zz, acc.zzz   N
+// This set S is CLOSED under every adder and under xyzz29_double, for BN254 and
+// for pallas (2^261/p = 128, the tighter one: pp = sqr(pn) reaches 1.20p).
+// A Jacobian doubling chain (jac29_double ... jac29_to_xyzz, xyzz29_double_n)
+// leaves a wider record SJ: x carry-normalised in (-6p, 11p), y carry-normalised
+// in (-9.5p, 2p), zz and zzz N; inside the chain x, y keep those intervals and
+// z stays in (-p/2, 5p/2).  SJ is legal as EITHER operand of xyzz29_add_* (x and
+// y go straight into a product there) and the sum is in S again; it is not an
+// accumulator for xyzz29_madd_* (x3 could leave (-4p, 2p)).
+// tests/fq29_model.py derives the intervals; tests/test_curve_math_lazy_host.py
+// and tests/test_gpu_field_layer.py apply every formula once to every corner of
+// S and SJ and require the point, the set again and the limb budget of every
+// product inside the step.
 // Every product below has one carry-normalised operand (< 2^29) and one with
-// |limb| < 2^30, inside the 2^59.6 budget of fq29_mul.
+// |limb| < 2^30, inside the budget of fq29_mul (fq29.h).
 #pragma once
 #include "fq29.h"
 
@@ -172,9 +184,9 @@ SNARKV_HD G1Xyzz29 xyzz29_double(const G1Xyzz29& p) {
 // costs 2M + 5S against 6M + 3S for the XYZZ form.  (X, Y, ZZ, ZZZ) ->
 // Jacobian (X*ZZ, Y*ZZZ, ZZ) [x = X'/Z'^2 with Z' = ZZ, since ZZ^3 = ZZZ^2] and
 // back as (X', Y', Z'^2, Z'^3).  P non-identity.
-// Bounds: x, y, z stay carry-normalised; every value passes through a square
-// or product each round, so magnitudes stay below ~12p and every product
-// result below ~2p (|a*b| / 2^261 < 1.1 p for |a|,|b| < 14p).
+// Bounds: x, y, z stay carry-normalised, x in (-6p, 11p), y in (-9.5p, 2p), z in
+// (-p/2, 5p/2) (the set SJ of the header; a product of such values is below 2p:
+// |a*b| / 2^261 < 0.95 p for |a|, |b| < 11p on pallas, less on BN254).
 // one Jacobian doubling in place (dbl-2009-l, a = 0; 2M + 5S); x, y, z carry-normalised
 SNARKV_HD void jac29_double(Fq29& x, Fq29& y, Fq29& z) {
   Fq29 a = fq29_sqr(x);
@@ -333,7 +345,8 @@ SNARKV_HD G1Xyzz29 xyzz29_sanitize(const G1Xyzz29& p) {
   return p;
 }
 
-// `to_affine`: canonical Montgomery affine; identity -> (0,0)
+// `to_affine`: Montgomery affine; each coordinate is the OUTPUT of a product (carry-normalised, congruent to the
+// coordinate, within (-p/4, 5p/4)), not its canonical residue: callers canonicalise (g1a29_to_words).  identity -> (0,0)
 SNARKV_HD G1Affine29 xyzz29_to_affine(const G1Xyzz29& p) {
   G1Affine29 r;
   if (xyzz29_is_identity(p) || xyzz29_is_degenerate(p)) {

@@ -4,6 +4,7 @@
 #include "../../snark-verifier_amd/csrc/fr29.h"
 #include "../../snark-verifier_amd/csrc/g1_29.h"
 #include "../../snark-verifier_amd/csrc/glv.h"
+#include "curve_ops.h"
 
 using namespace snarkv;
 
@@ -72,4 +73,13 @@ void hc_glv_phi(const uint8_t* p, uint8_t* out) {
   a.x = fq29_mul(a.x, beta);
   stp(xyzz29_from_affine(a), out);
 }
+
+// raw-record entry points (curve_ops.h): n records in, n records out, limbs untouched on both sides
+#define HC_RAW(name, IN, OUT)                                               \
+  void hc_##name##_raw(const int32_t* in, int32_t* out, int n) {            \
+    for (int i = 0; i < n; ++i) rawops::op_##name(in + (long)i * IN, out + (long)i * OUT); \
+  }                                                                         \
+  int hc_##name##_raw_io() { return (IN << 16) | OUT; }
+SNARKV_RAW_OPS(HC_RAW)
+#undef HC_RAW
 }

@@ -1,7 +1,12 @@
 """CPU: the curve-generic device headers (fq29.h, fr29.h, g1_29.h, glv.h) compiled for the HOST
 with the BN254 and with the pallas constants (csrc/curve_consts.h) against the big-integer oracles: lazy
 9x29-bit field products at the edges of the range, the XYZZ adders, the Jacobian doubling chain, and the
-GLV split k = k1 + k2 lambda with |k_i| < 2^127 -- the packing the Pippenger relies on."""
+GLV split k = k1 + k2 lambda with |k_i| < 2^127 -- the packing the Pippenger relies on.
+
+Every entry point used here loads its operands from canonical bytes and stores canonical bytes, so the formulas only ever see
+freshly converted values in the middle of their allowed range.  The raw-limb tests at the edges of the lazy contract
+(negative values, values near +-8p, limbs above 2^29, accumulators at the corners of their set) are in
+tests/test_curve_math_lazy_host.py, and on the device in tests/test_gpu_field_layer.py."""
 import ctypes
 import os
 import random
