@@ -24,6 +24,7 @@ def _deps():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp", ".inc"))]
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_amd.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_pallas.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_pallas_decompress.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_prover.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
@@ -71,7 +72,7 @@ def _link(lib, res, extra):
 
 
 # The pasta build of the curve-generic units (csrc/pallas.hip explains the flags, csrc/ctx.hpp the policy they select).
-PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover"]
+PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover", "decompress_pallas"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
 
@@ -109,10 +110,13 @@ HOST = os.path.join(HERE, "host")
 HOST_LIB = os.path.join(HERE, "libsnarkv_host.so")                 # product: C API of the host mirror (host/capi.cpp)
 HOSTTEST_LIB = os.path.join(HERE, "libsnarkv_hosttest.so")         # test hooks only (host/test_driver.cpp)
 HOST_PALLAS_LIB = os.path.join(HERE, "libsnarkv_hosttest_pallas.so")  # pasta flavour of the mirror, test hooks
+HOST_PALLAS_API_LIB = os.path.join(HERE, "libsnarkv_host_pallas.so")  # pasta flavour, product C API (host/capi_pallas.cpp)
 
 
 def _host_stale(out, dev_lib):
-    srcs = [os.path.join(HOST, f) for f in os.listdir(HOST)] + [os.path.join(os.path.dirname(HERE), "include", "snarkv_host.h")]
+    inc = os.path.join(os.path.dirname(HERE), "include")
+    srcs = [os.path.join(HOST, f) for f in os.listdir(HOST)] + [os.path.join(inc, h) for h in (
+        "snarkv_host.h", "snarkv_host_pallas.h", "snarkv_pallas_decompress.h")]
     newest = max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(dev_lib)])
     return not os.path.exists(out) or os.path.getmtime(out) < newest
 
@@ -130,19 +134,22 @@ def _gxx(out, src, extra, dev):
 
 def build_host_driver():
     """C++ host mirror (host/*.hpp): its C API (host/capi.cpp -> libsnarkv_host.so, include/snarkv_host.h), the test
-    hooks (host/test_driver.cpp -> libsnarkv_hosttest.so) and the pasta flavour's test hooks, each linked against the
+    hooks (host/test_driver.cpp -> libsnarkv_hosttest.so), and the pasta flavour's test hooks and C API
+    (host/capi_pallas.cpp -> libsnarkv_host_pallas.so, include/snarkv_host_pallas.h), each linked against the
     device library next to it (rpath $ORIGIN).  Every target has its own staleness check."""
     jobs = []
     if _host_stale(HOST_LIB, LIB):
         jobs.append((HOST_LIB, "capi.cpp", [], "snarkv_amd"))
     if _host_stale(HOSTTEST_LIB, LIB):
         jobs.append((HOSTTEST_LIB, "test_driver.cpp", [], "snarkv_amd"))
+    # -Dsnarkv_host=...: its own C++ namespace -- the two flavours define the same inline functions and
+    # `static constexpr` members with different constants, and C++17 inline variables are STB_GNU_UNIQUE
+    # (bound process-wide even under RTLD_LOCAL) when both libraries sit in one process
+    pasta = ["-DSNARKV_HOST_PALLAS", "-Dsnarkv_host=snarkv_host_pallas", "-fno-gnu-unique"]
     if os.path.exists(PALLAS_LIB) and _host_stale(HOST_PALLAS_LIB, PALLAS_LIB):
-        # -Dsnarkv_host=...: its own C++ namespace -- the two flavours define the same inline functions and
-        # `static constexpr` members with different constants, and C++17 inline variables are STB_GNU_UNIQUE
-        # (bound process-wide even under RTLD_LOCAL) when both libraries sit in one process
-        jobs.append((HOST_PALLAS_LIB, "test_driver_pallas.cpp",
-                     ["-DSNARKV_HOST_PALLAS", "-Dsnarkv_host=snarkv_host_pallas", "-fno-gnu-unique"], "snarkv_pallas"))
+        jobs.append((HOST_PALLAS_LIB, "test_driver_pallas.cpp", pasta, "snarkv_pallas"))
+    if os.path.exists(PALLAS_LIB) and _host_stale(HOST_PALLAS_API_LIB, PALLAS_LIB):
+        jobs.append((HOST_PALLAS_API_LIB, "capi_pallas.cpp", pasta, "snarkv_pallas"))
     if jobs:
         with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
             list(ex.map(lambda j: _gxx(*j), jobs))
@@ -152,6 +159,11 @@ def build_host_driver():
 def build_host_driver_pallas():
     build_host_driver()
     return HOST_PALLAS_LIB
+
+
+def build_host_api_pallas():
+    build_host_driver()
+    return HOST_PALLAS_API_LIB
 
 
 if __name__ == "__main__":

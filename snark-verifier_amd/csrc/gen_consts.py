@@ -127,6 +127,34 @@ def glv_section(p, r, gen):
     print("#define SNARKV_GLV_G2 { %s }  // floor(2^288 |b1| / r), %d bits" % (words(g2, 6), g2.bit_length()))
 
 
+def sqrt_section(p, z):
+    """Square roots in a field of high 2-adicity (fq29_sqrt.h): p - 1 = 2^s t with t odd, z a non-residue, g = z^t a
+    generator of the 2^s-subgroup.  (t - 1) / 2 in 32-bit words, the table g^(-2^j), j < s, in 9x29 Montgomery limbs
+    (R = 2^261)."""
+    def lim29(v):
+        return ", ".join("0x%08x" % ((v >> (29 * i)) & ((1 << 29) - 1)) for i in range(9))
+
+    s, t = 0, p - 1
+    while t % 2 == 0:
+        s, t = s + 1, t // 2
+    assert pow(z, (p - 1) // 2, p) == p - 1  # Euler: z is not a square
+    g = pow(z, t, p)
+    assert pow(g, 1 << (s - 1), p) == p - 1
+    e = (t - 1) // 2
+    r29 = 1 << 261
+    print("// ---- square roots: p - 1 = 2^%d t, g = %d^t of order 2^%d (fq29_sqrt.h)" % (s, z, s))
+    print("#define SNARKV_FQ_TWO_ADICITY %d" % s)
+    print("#define SNARKV_FQ_SQRT_EXP_BITS %d  // bit length of (t - 1) / 2" % e.bit_length())
+    print("#define SNARKV_FQ_SQRT_EXP_LIMBS { %s }  // (t - 1) / 2" %
+          ", ".join("0x%08xu" % ((e >> (32 * i)) & 0xFFFFFFFF) for i in range(8)))
+    print("// g^(-2^j) * 2^261 mod p, j = 0 .. %d (the last one is -1)" % (s - 1))
+    print("#define SNARKV_FQ29_SQRT_GINV_POW { \\")
+    gi = pow(g, -1, p)
+    for j in range(s):
+        print("  { %s }, \\" % lim29(pow(gi, 1 << j, p) * r29 % p))
+    print("}")
+
+
 if len(sys.argv) > 1 and sys.argv[1] == "pallas":
     # pallas (pasta): y^2 = x^3 + 5 over Fp, group order q (= the base field of vesta); generator (-1, 2).
     PP = 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001
@@ -139,6 +167,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "pallas":
     print("#pragma once")
     generic_section(PP, PQ, 5, "pallas")
     glv_section(PP, PQ, (PP - 1, 2))
+    sqrt_section(PP, 5)
     sys.exit(0)
 
 

@@ -13,11 +13,12 @@
 // msm_naive.hip (the segmented small-MSM kernels behind `NativeLoader::multi_scalar_multiplication`,
 // loader/native.rs:61-71) comes along; pallas has the same kind of endomorphism as BN254 (j = 0), so
 // the GLV split stays on, with pallas' lattice.  There is no pairing, no KZG decider and no transcript.
-// This unit holds what has no BN254 twin: the exported host-staged Pippenger (no `flags` argument) and
-// the context-free pallas_* forms.
+// This unit holds what has no BN254 twin: the exported host-staged Pippenger (no `flags` argument), the
+// entry point of the batched point decompression (decompress_pallas.hip) and the context-free pallas_* forms.
 #include <mutex>
 #include "ctx.hpp"
 #include "../../include/snarkv_pallas.h"
+#include "../../include/snarkv_pallas_decompress.h"
 
 using namespace snarkv;
 
@@ -26,6 +27,29 @@ extern "C" {
 int snarkv_pallas_g1_msm_pippenger(snarkv_ctx* ctx, const uint8_t* scalars32, const uint8_t* points64, size_t n,
                                    uint8_t out64[64]) {
   return msm_pippenger_staged(ctx, scalars32, points64, n, 0, out64);
+}
+
+// `C::from_bytes` for a batch (include/snarkv_pallas_decompress.h; the kernel: decompress_pallas.hip), staged as
+// snarkv_g1_decompress stages its own
+int snarkv_pallas_g1_decompress(snarkv_ctx* ctx, const uint8_t* in32, size_t n, uint8_t* out64, uint8_t* ok) {
+  if (!ctx || (n && (!in32 || !out64 || !ok))) return SNARKV_ERR_ARG;
+  if (n == 0) return SNARKV_OK;
+  if (n > 0xFFFFFFFFull) return SNARKV_ERR_LENGTH;
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  void *d_in, *d_out;
+  SNARKV_TRY(stage_in(ctx, SLOT_IN_POINTS, in32, n * 32, &d_in));
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_OUT, n * 64 + n, &d_out));  // the points, then one validity byte each
+  SNARKV_TRY(launch_g1_decompress(ctx, d_in, n, d_out, (uint8_t*)d_out + n * 64));
+  SNARKV_HIP(hipMemcpyAsync(ok, (const uint8_t*)d_out + n * 64, n, hipMemcpyDeviceToHost, ctx->stream));
+  return fetch_out(ctx, d_out, out64, n * 64);
+}
+
+// snarkv_ctx_set_flags for a pasta context: the default flags of every call on it
+int snarkv_pallas_ctx_set_flags(snarkv_ctx* ctx, uint32_t flags) {
+  if (!ctx || (flags & ~(SNARKV_FLAG_VALIDATE | SNARKV_FLAG_MONTGOMERY))) return SNARKV_ERR_ARG;
+  ctx->flags = flags;
+  ctx->mont = (flags & SNARKV_FLAG_MONTGOMERY) != 0;
+  return SNARKV_OK;
 }
 
 // ---- context-free forms (what a `NativeLoader`-style unit struct binds: loader.rs:108 has no &self) ----
@@ -70,6 +94,10 @@ int pallas_ipa_dk_create(const uint8_t* g_points64, size_t n, snarkv_ipa_dk** ou
 int pallas_ipa_decide_batch(const snarkv_ipa_dk* dk, const uint8_t* xi32, const uint8_t* u64, size_t m, uint8_t* ok) {
   PALLAS_DEFAULT_CTX();
   return snarkv_pallas_ipa_decide_batch(c, dk, xi32, u64, m, ok);
+}
+int pallas_g1_decompress(const uint8_t* in32, size_t n, uint8_t* out64, uint8_t* ok) {
+  PALLAS_DEFAULT_CTX();
+  return snarkv_pallas_g1_decompress(c, in32, n, out64, ok);
 }
 
 }  // extern "C"

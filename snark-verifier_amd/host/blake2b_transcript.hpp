@@ -285,9 +285,17 @@ class Blake2bTranscript : public Transcript {
   Result<G1Affine> read_ec_point() override {
     using R = Result<G1Affine>;
     uint8_t b[32];
+    const size_t at = pos_;
     if (!take(b, 32)) return R::Err(Error{Error::Transcript, "failed to fill whole buffer"});
     const uint8_t sign = b[31] >> 7;
     b[31] &= 0x7F;
+    if (const uint8_t* h = hint_at(at, b, sign)) {  // decompressed for the whole batch by the device (pallas_g1_decompress)
+      G1Affine p = G1Affine::from_bytes(h);
+      Error e = common_ec_point(p);
+      if (!e.ok()) return R::Err(e);
+      ++hints_taken_;
+      return R::Ok(p);
+    }
     uint64_t xw[4];
     memcpy(xw, b, 32);
     const Error bad{Error::Transcript, "invalid point encoding in proof"};
@@ -332,8 +340,34 @@ class Blake2bTranscript : public Transcript {
     return {};
   }
   const std::vector<uint8_t>& finalize() const { return stream_; }
+  size_t remaining() const { return stream_.size() - pos_; }
+  // Candidate decodings of the stream's compressed points: hint i = the 64-byte point and validity flag the device
+  // answered for the 32 bytes at stream offset offs[i] (ascending).  Borrowed views of the batch's arrays: nothing is
+  // copied per proof.  A hint is used only if it IS the decoding of the bytes read (`hint_at`); everything else --
+  // a flag of 0, the identity, a read at another offset -- takes the square root above, whose verdicts and error
+  // texts therefore stay the only ones.
+  void set_point_hints(const uint32_t* offs, const uint8_t* pts64, const uint8_t* ok, size_t n) {
+    hint_offs_ = offs, hint_pts_ = pts64, hint_ok_ = ok, n_hints_ = n, next_hint_ = 0;
+  }
+  // how many points this transcript has decoded from a hint instead of a square root
+  size_t hints_taken() const { return hints_taken_; }
 
  private:
+  // a finite point whose x is the encoded x and whose y has the encoded parity (x < p and on the curve by
+  // construction: the device checks both before it answers 1)
+  const uint8_t* hint_at(size_t at, const uint8_t x_masked[32], uint8_t sign) {
+    while (next_hint_ < n_hints_ && hint_offs_[next_hint_] < at) ++next_hint_;
+    if (next_hint_ >= n_hints_ || hint_offs_[next_hint_] != at || !hint_ok_[next_hint_]) return nullptr;
+    const uint8_t* h = hint_pts_ + 64 * next_hint_;
+    bool zero = true;
+    for (int i = 0; i < 64 && zero; ++i) zero = h[i] == 0;
+    if (zero || memcmp(h, x_masked, 32) != 0 || (h[32] & 1) != sign) return nullptr;
+    return h;
+  }
+  const uint32_t* hint_offs_ = nullptr;
+  const uint8_t* hint_pts_ = nullptr;
+  const uint8_t* hint_ok_ = nullptr;
+  size_t n_hints_ = 0, next_hint_ = 0, hints_taken_ = 0;
   static Fr two_256() {
     static const Fr v = [] {
       Fr x = Fr::from_u64(1ull << 32);

@@ -16,6 +16,7 @@
 #include "blake2b_transcript.hpp"
 #include "ipa.hpp"
 #include "plonk.hpp"
+#include "plonk_ipa_batch.hpp"
 #include "wire.hpp"
 
 using namespace snarkv_host;
@@ -53,6 +54,34 @@ std::vector<uint8_t> transcript_stream(const Transcript& t) { return dynamic_cas
 #include "ipa_driver.inc"
 
 extern "C" {
+// the layout pass of the batch reader (plonk_ipa_batch.hpp): the byte offsets of the compressed points of one proof of
+// `protocol` under a key of size k, and the proof's length.  Returns the number of points; fills at most `cap` offsets.
+int hp_plonk_ipa_point_offsets(const uint8_t* protocol, size_t plen, uint32_t k, uint32_t* offsets_out, size_t cap,
+                               size_t* proof_len) {
+  return guarded([&] {
+    const IpaProofLayout l = plonk_ipa_proof_layout(parse_protocol(protocol, plen), k);
+    for (size_t i = 0; i < l.point_offsets.size() && i < cap; ++i) offsets_out[i] = l.point_offsets[i];
+    if (proof_len) *proof_len = l.len;
+    return (int)l.point_offsets.size();
+  });
+}
+// the batch reader alone (plonk_ipa_batch.hpp `plonk_ipa_read_batch`) under `route` (0 HOST, 1 DEVICE, 2 AUTO), batch
+// bytes as hp_plonk_ipa_verify_batch takes them.  Returns 1 or the first error's code; *hints_taken = the number of
+// compressed points of the batch whose decoding a transcript took from the device's answers.
+int hp_plonk_ipa_read_batch(const uint8_t* protocol, size_t plen, const uint8_t* instances, size_t ilen,
+                            const uint8_t* proofs, size_t prlen, uint32_t n, const uint8_t* svk_bytes, unsigned threads,
+                            int route, size_t* hints_taken) {
+  return guarded([&] {
+    const PlonkProtocol pr = parse_protocol(protocol, plen);
+    const IpaSuccinctVerifyingKey svk = parse_ipa_svk(svk_bytes);
+    std::vector<std::vector<std::vector<Fr>>> insts;
+    std::vector<std::vector<uint8_t>> pbytes;
+    wire::split_batch(instances, ilen, proofs, prlen, n, insts, pbytes);
+    std::vector<PlonkProof<Bgh19>> pfs;
+    Error e = plonk_ipa_read_batch(svk, pr, insts, pbytes, threads, (IpaDecompress)route, pfs, hints_taken);
+    return e.ok() ? 1 : error_code(e);
+  });
+}
 // Fr = pallas::Scalar self-test hooks
 void hp_fr_mul(const uint8_t* a, const uint8_t* b, uint8_t* out) {
   Fr x, y;

@@ -41,6 +41,10 @@ def load_library():
             "snarkv_pallas_ipa_dk_destroy": (None, [vp]),
             "snarkv_pallas_ipa_dk_k": (u32, [vp]),
             "snarkv_pallas_ipa_decide_batch": (ctypes.c_int, [vp, vp, vp, vp, sz, vp]),
+            # include/snarkv_pallas_decompress.h
+            "snarkv_pallas_ctx_set_flags": (ctypes.c_int, [vp, u32]),
+            "snarkv_pallas_g1_decompress": (ctypes.c_int, [vp, vp, sz, vp, vp]),
+            "pallas_g1_decompress": (ctypes.c_int, [vp, sz, vp, vp]),
         }.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
@@ -81,6 +85,11 @@ class PallasContext:
 
     def sync(self):
         _check(self._lib.snarkv_pallas_ctx_sync(self._h))
+
+    def set_flags(self, flags):
+        """Default flags of the context (`snarkv_pallas_ctx_set_flags`): SNARKV_FLAG_MONTGOMERY makes every call on it
+        speak halo2curves' in-memory form."""
+        _check(self._lib.snarkv_pallas_ctx_set_flags(self._h, int(flags)))
 
     def wait_stream(self, stream=None):
         """`snarkv_pallas_ctx_wait_stream`: the context's next work runs after everything queued on `stream` (a HIP stream
@@ -124,6 +133,18 @@ class PallasContext:
 
     def msm_pippenger_dev(self, d_scalars, d_points, n, d_out, window_bits=0):
         _check(self._lib.snarkv_pallas_g1_msm_pippenger_dev(self._h, d_scalars, d_points, n, window_bits, d_out))
+
+    def g1_decompress(self, compressed):
+        """`pallas::Affine::from_bytes` for a batch (`snarkv_pallas_g1_decompress`): 32-byte encodings (x little-endian,
+        bit 255 = parity of y) -> (64-byte affine points concatenated, list of validity flags).  An invalid encoding
+        gives 64 zero bytes and False; the all-zero encoding is the identity: 64 zero bytes and True."""
+        c = _as_bytes(compressed)
+        if len(c) % 32:
+            raise SnarkvError(-2, "compressed points are 32 bytes each")
+        n = len(c) // 32
+        out, ok = ctypes.create_string_buffer(64 * max(n, 1)), ctypes.create_string_buffer(max(n, 1))
+        _check(self._lib.snarkv_pallas_g1_decompress(self._h, c if n else b"\x00", n, out, ok))
+        return out.raw[:64 * n], [b != 0 for b in ok.raw[:n]]
 
     def ipa_dk_create(self, g):
         g = _as_bytes(g)
