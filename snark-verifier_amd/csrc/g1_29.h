@@ -394,15 +394,16 @@ SNARKV_HD G1Affine29 g1a29_neg(const G1Affine29& p) {
   return r;
 }
 
-// k*P, 256-step double-and-add (`*base * scalar`, reference native.rs:67).
+// k*P, double-and-add over the WORDS words of k, 256 steps by default (`*base * scalar`, reference native.rs:67); the
+// segmented MSM's careful redo of a 127-bit GLV half takes WORDS = 4.
 // Canonical scalars (< r) never meet an exceptional case after the first
 // addition; non-canonical ones are caught by the degenerate check + careful redo.
-template <bool CAREFUL>
-SNARKV_HD G1Xyzz29 g1_29_scalar_mul(const G1Affine29& p, const uint32_t k[8]) {
+template <bool CAREFUL, int WORDS = 8>
+SNARKV_HD G1Xyzz29 g1_29_scalar_mul(const G1Affine29& p, const uint32_t* k) {
   G1Xyzz29 acc = xyzz29_identity();
   if (g1a29_is_identity(p)) return acc;
   bool started = false;
-  for (int i = 7; i >= 0; --i) {
+  for (int i = WORDS - 1; i >= 0; --i) {
     uint32_t w = k[i];
     for (int b = 31; b >= 0; --b) {
       if (started) {

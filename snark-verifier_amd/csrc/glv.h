@@ -118,4 +118,20 @@ SNARKV_HD void glv_decompose(const uint32_t k[8], uint32_t out[8]) {
   }
 }
 
+// Signed 3-bit digits of a 127-bit magnitude: |k| = sum d_i 8^i, d_i in [-3, 4], i < kWinDigits.  A raw digit above 4
+// becomes d - 8 with a carry up, so the digits come low to high: `carry` starts at 0 and is handed from digit i to i + 1.
+constexpr int kWinDigits = 43;  // ceil(127 / 3) + the carry into the one-bit top digit
+
+// The magnitude comes as four values, not as a pointer: the selects below then pick among registers.  Through a pointer the
+// device compiler made them one indexed load, and a caller's array stayed in scratch memory for it.
+SNARKV_HD int glv_w3_digit(uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, int i, uint32_t& carry) {
+  const int bit = 3 * i, word = bit >> 5, sh = bit & 31;
+  uint32_t w0 = word == 0 ? k0 : word == 1 ? k1 : word == 2 ? k2 : word == 3 ? k3 : 0u;
+  uint32_t w1 = word == 0 ? k1 : word == 1 ? k2 : word == 2 ? k3 : 0u;
+  uint32_t raw = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh) & 7u;
+  raw += carry;
+  carry = raw > 4u ? 1u : 0u;
+  return (int)raw - (carry ? 8 : 0);
+}
+
 }  // namespace snarkv

@@ -5,16 +5,25 @@
 // The accumulation path produces MANY independent small MSMs (per proof a
 // ~21-term and a ~3-term one from Gwc19/Bdfg21::verify, then two (m+1)-term
 // ones from KzgAs::verify -- SURVEY.md section 0 item 6), so the launch unit
-// is a SEGMENTED MSM:
-//   K1  k_term_scalar_mul : one lane per (term, GLV half): k = k1 + k2*lambda
-//                           splits `*base * scalar` (native.rs:67) into two
-//                           independent 127-step double-and-add chains on P and
-//                           phi(P), on the lazy 9x29-bit field
-//   K2  k_segment_fold    : one wave per MSM folds its partials (`reduce(|a,v| a+v)`,
-//                           native.rs:68), then `to_affine()` (native.rs:70) and
-//                           canonical little-endian store.
-// A single small MSM is latency-bound by construction (one dependency chain);
-// the segmented launch is what fills the machine.
+// is a SEGMENTED MSM: a TERM stage leaves one XYZZ partial per (term, GLV half),
+//   k = k1 + k2*lambda with |k_i| < 2^127 (glv.h) splits `*base * scalar` (native.rs:67), a 254-step chain, into two
+//   independent 127-step chains on P and phi(P) = (beta x, y),
+// and a FOLD stage, k_segment_fold, folds every MSM's partials (`reduce(|a,v| a+v)`, native.rs:68), then `to_affine()`
+// (native.rs:70) and the canonical little-endian store.  A single small MSM is latency-bound by construction (one
+// dependency chain); the segmented launch is what fills the machine.
+//
+// Three regimes of the term stage, chosen by launch_msm_batched from the launch's size:
+//   chunked   k_term_chain / k_term_chain_quad + k_term_chunks: small launches, every half cut into J chunks
+//   two-lane  k_term_scalar_mul: one lane per (term, half), signed 3-bit fixed window
+//   group     k_term_scalar_mul_group (+ k_gmap_*): throughput-bound launches, up to four terms of a segment per lane
+// What they share is written once:
+//   glv_half      term t, half h -> the chain-ready base (phi applied, sign folded into y), |k_h|, "contributes nothing"
+//   glv_w3_digit  (glv.h) the signed 3-bit recoding, int8 digits for the two-lane form, biased nibbles for the group form
+//   col_put / col_get, xyzz_put / xyzz_get   limb-major columns of the per-lane table scratch
+//   table_2q_3q_4q  the window table's entries, handed to the caller's store
+//   careful_half  the redo of a half whose fast run met P = +-Q: g1_29.h's bit-serial g1_29_scalar_mul<true> on 4 words
+// A bit-serial FAST form of the two-lane kernel lost its A/B against the fixed window in round 3 and is no longer here:
+// commit 5e83a23 has its text behind -DSNARKV_NAIVE_WINDOW=0, profiles/r03_ab_naive_window.txt the record.
 #include "ctx.hpp"
 #include "g1.h"
 #include "g1_29.h"
@@ -53,86 +62,119 @@ __device__ __forceinline__ G1Affine29 load_term(const uint32_t* __restrict__ sca
   return g1a29_from_words(pw, mont != 0);
 }
 
-// |k| * Q for a 127-bit magnitude: left-to-right double-and-add on the lazy
-// 9x29-bit field.  FAST: branch-free adders, the caller checks the degenerate
-// flag; CAREFUL: explicit exceptional cases.
-template <bool CAREFUL>
-__device__ __forceinline__ G1Xyzz29 half_scalar_mul(const G1Affine29& q, const uint32_t k[4]) {
-  G1Xyzz29 acc = xyzz29_identity();
-  bool started = false;
-  for (int i = 3; i >= 0; --i) {
-    uint32_t w = k[i];
-    for (int b = 31; b >= 0; --b) {
-      if (started) {
-        if (!CAREFUL || !xyzz29_is_identity(acc)) acc = xyzz29_double(acc);
-      }
-      if ((w >> b) & 1u) {
-        if (!started) {
-          acc = xyzz29_from_affine(q);
-          started = true;
-        } else if (CAREFUL) {
-          xyzz29_madd_careful(acc, q);
-        } else {
-          xyzz29_madd_fast(acc, q);
-        }
-      }
-    }
-  }
-  return acc;
+__device__ __forceinline__ Fq29 glv_beta29() {
+  constexpr int32_t bl[9] = SNARKV_GLV_BETA29_LIMBS;
+  Fq29 beta;
+#pragma unroll
+  for (int j = 0; j < 9; ++j) beta.v[j] = bl[j];
+  return beta;
 }
+
+// half h of glv_decompose's output: the 127-bit magnitude into `mag`, the sign (1 = negative) returned.  Selects, not
+// halves[4 * h + w]: a lane-dependent index would put the array into scratch.
+__device__ __forceinline__ uint32_t glv_mag_sign(const uint32_t halves[8], uint32_t h, uint32_t (&mag)[4]) {
+#pragma unroll
+  for (int w = 0; w < 4; ++w) mag[w] = h ? halves[4 + w] : halves[w];
+  const uint32_t neg = mag[3] >> 31;
+  mag[3] &= 0x7FFFFFFFu;
+  return neg;
+}
+
+// GLV half h of term t, ready for a chain: the base is P (h = 0) or phi(P) = (beta x, y) with the half's sign folded into
+// y, so that the half contributes mag * q.  NORM_Y carry-normalises a negated y, as a Jacobian chain needs it.  `none`:
+// the half contributes nothing (identity base or zero magnitude); the magnitude of an identity base reads zero.
+// A caller that hands the magnitude on as an array COPIES it into a local one first: a pointer into the record kept the
+// whole record in scratch (96 B per lane), and so did filling `mag` through halves[4 * h + w].
+struct GlvHalf {
+  G1Affine29 q;
+  uint32_t mag[4];
+  bool none;
+};
+
+template <bool NORM_Y>
+__device__ __forceinline__ GlvHalf glv_half(const uint32_t* __restrict__ scalars, const uint32_t* __restrict__ points, size_t t,
+                                            uint32_t h, uint32_t mont) {
+  GlvHalf r;
+  uint32_t k[8], halves[8];
+  r.q = load_term(scalars, points, t, mont, k);
+  glv_decompose(k, halves);
+  const uint32_t neg = glv_mag_sign(halves, h, r.mag);
+  if (g1a29_is_identity(r.q)) r.mag[0] = r.mag[1] = r.mag[2] = r.mag[3] = 0;
+  r.none = (r.mag[0] | r.mag[1] | r.mag[2] | r.mag[3]) == 0;
+  if (h) r.q.x = fq29_canon_residue(fq29_mul(r.q.x, glv_beta29()));
+  if (neg) r.q.y = NORM_Y ? fq29_norm(fq29_neg(r.q.y)) : fq29_neg(r.q.y);
+  return r;
+}
+
+// mag * Q with every exceptional case spelled out (bit-serial, g1_29.h): the redo of a half whose fast run ended degenerate
+// -- P = +-Q met on the way, or a true identity.  A result that is degenerate but not the stored identity becomes it.
+__device__ __forceinline__ G1Xyzz29 careful_half(const G1Affine29& q, const uint32_t mag[4]) {
+  G1Xyzz29 r = g1_29_scalar_mul<true, 4>(q, mag);
+  if (!xyzz29_is_identity(r) && xyzz29_is_degenerate(r)) r = xyzz29_identity();
+  return r;
+}
+
+// The table scratch is limb-major per lane: an Fq29 is a column of 9 rows at [row0 .. row0 + 9)[lane], so that every
+// access of a wavefront is one segment; an XYZZ point is four such columns (x, y, zz, zzz) from row0.
+__device__ __forceinline__ void col_put(int32_t (*tab)[64], int row0, uint32_t lane, const Fq29& v) {
+#pragma unroll
+  for (int l = 0; l < 9; ++l) tab[row0 + l][lane] = v.v[l];
+}
+__device__ __forceinline__ Fq29 col_get(const int32_t (*tab)[64], int row0, uint32_t lane) {
+  Fq29 v;
+#pragma unroll
+  for (int l = 0; l < 9; ++l) v.v[l] = tab[row0 + l][lane];
+  return v;
+}
+__device__ __forceinline__ void xyzz_put(int32_t (*tab)[64], int row0, uint32_t lane, const G1Xyzz29& v) {
+  col_put(tab, row0, lane, v.x);
+  col_put(tab, row0 + 9, lane, v.y);
+  col_put(tab, row0 + 18, lane, v.zz);
+  col_put(tab, row0 + 27, lane, v.zzz);
+}
+__device__ __forceinline__ G1Xyzz29 xyzz_get(const int32_t (*tab)[64], int row0, uint32_t lane) {
+  G1Xyzz29 v;
+  v.x = col_get(tab, row0, lane);
+  v.y = col_get(tab, row0 + 9, lane);
+  v.zz = col_get(tab, row0 + 18, lane);
+  v.zzz = col_get(tab, row0 + 27, lane);
+  return v;
+}
+
+// the fixed window's table entries 2Q, 3Q, 4Q (XYZZ), handed in that order to put(0 .. 2, entry); Q itself stays with the caller
+template <class Put>
+__device__ __forceinline__ void table_2q_3q_4q(const G1Affine29& q, Put put) {
+  G1Xyzz29 t2 = xyzz29_double_affine(q), t3 = t2;
+  xyzz29_madd_fast(t3, q);
+  G1Xyzz29 t4 = xyzz29_double(t2);
+  put(0, t2);
+  put(1, t3);
+  put(2, t4);
+}
+
+#ifndef SNARKV_NAIVE_WAVES
+#define SNARKV_NAIVE_WAVES 2  // wavefronts per SIMD k_term_scalar_mul is compiled for (3: 168 VGPRs + 48 B of spills)
+#endif
 
 // |k| * Q with a FIXED 3-bit window and signed digits, every lane of the wavefront in the same step:
 //   table    2Q, 3Q, 4Q (XYZZ) in a global scratch, one column per lane (limb-major: every access one segment; it stays in
 //            L2) -- not in LDS: 27 KB per wavefront there capped a CU at five wavefronts, and with several launches in
 //            flight the kernel's throughput fell back to the bit-serial form's; Q itself stays in registers
-//   digits   |k| = sum d_i 8^i, d_i in [-3, 4] (a digit above 4 becomes d - 8 with a carry up), 43 of them for 127 bits,
-//            recoded low to high into LDS bytes, consumed high to low
+//   digits   glv_w3_digit: 43 of them for 127 bits, recoded low to high into LDS bytes, consumed high to low
 //   step     acc <- 8 acc (three doublings; the identity doubles to itself), then acc += sign * T[|d|] by the full XYZZ
 //            addition, the operand picked by a per-lane LDS read
-// The bit-serial form above costs a WAVEFRONT 127 doublings + 127 mixed additions (some lane's bit is always set, so
+// A bit-serial double-and-add costs a WAVEFRONT 127 doublings + 127 mixed additions (some lane's bit is always set, so
 // the addition is issued at every step): ~2 400 field products.  This one: 3 + 129 doublings + 43 additions ~ 1 800,
 // and no lane waits for another's branch.  A fast addition can only meet P = +-Q here while acc is still the identity
-// (8 x prefix >= 8 > |d|), which `started` covers; the degenerate check + careful bit-serial redo stay as the net.
-#ifndef SNARKV_NAIVE_WINDOW
-#define SNARKV_NAIVE_WINDOW 1  // 0: the bit-serial double-and-add (A/B: profiles/r03_ab_naive_window.txt)
-#endif
-#ifndef SNARKV_NAIVE_WAVES
-#define SNARKV_NAIVE_WAVES 2  // wavefronts per SIMD k_term_scalar_mul is compiled for (3: 168 VGPRs + 48 B of spills)
-#endif
-constexpr int kWinDigits = 43;  // ceil(127 / 3) + the carry into the one-bit top digit
-
+// (8 x prefix >= 8 > |d|), which `started` covers; the degenerate check + careful_half stay as the net.
 __device__ __forceinline__ G1Xyzz29 half_scalar_mul_w3(const G1Affine29& q, const uint32_t k[4], int32_t* __restrict__ tabg,
                                                        int8_t (*dig)[64]) {
   const uint32_t lane = threadIdx.x;
   // this wavefront's slice of the scratch: [entry 0..2][limb 0..35][lane]
   int32_t(*tab)[36][64] = reinterpret_cast<int32_t(*)[36][64]>(tabg + (size_t)blockIdx.x * 3 * 36 * 64);
-  // table: 2Q, 3Q, 4Q
-  G1Xyzz29 t2 = xyzz29_double_affine(q), t3 = t2;
-  xyzz29_madd_fast(t3, q);
-  G1Xyzz29 t4 = xyzz29_double(t2);
-  auto put = [&](int e, const G1Xyzz29& v) {
-#pragma unroll
-    for (int l = 0; l < 9; ++l) {
-      tab[e][l][lane] = v.x.v[l];
-      tab[e][9 + l][lane] = v.y.v[l];
-      tab[e][18 + l][lane] = v.zz.v[l];
-      tab[e][27 + l][lane] = v.zzz.v[l];
-    }
-  };
-  put(0, t2);
-  put(1, t3);
-  put(2, t4);
-  // signed digits, low to high
+  table_2q_3q_4q(q, [&](int e, const G1Xyzz29& v) { xyzz_put(tab[e], 0, lane, v); });
   uint32_t carry = 0;
-  for (int i = 0; i < kWinDigits; ++i) {
-    const int bit = 3 * i, word = bit >> 5, sh = bit & 31;
-    uint32_t w0 = word == 0 ? k[0] : word == 1 ? k[1] : word == 2 ? k[2] : word == 3 ? k[3] : 0u;
-    uint32_t w1 = word == 0 ? k[1] : word == 1 ? k[2] : word == 2 ? k[3] : 0u;
-    uint32_t raw = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh) & 7u;
-    raw += carry;
-    carry = raw > 4u ? 1u : 0u;
-    dig[i][lane] = (int8_t)((int)raw - (carry ? 8 : 0));
-  }
+  for (int i = 0; i < kWinDigits; ++i) dig[i][lane] = (int8_t)glv_w3_digit(k[0], k[1], k[2], k[3], i, carry);
   // (the lane reads back only what it wrote: no barrier; the compiler keeps LDS accesses of one lane in order)
   G1Xyzz29 acc = xyzz29_identity();
   bool started = false;
@@ -142,18 +184,7 @@ __device__ __forceinline__ G1Xyzz29 half_scalar_mul_w3(const G1Affine29& q, cons
     const int d = dig[i][lane];
     const int a = d < 0 ? -d : d;
     if (a != 0) {
-      G1Xyzz29 sel;
-      if (a == 1) {
-        sel = xyzz29_from_affine(q);
-      } else {
-#pragma unroll
-        for (int l = 0; l < 9; ++l) {
-          sel.x.v[l] = tab[a - 2][l][lane];
-          sel.y.v[l] = tab[a - 2][9 + l][lane];
-          sel.zz.v[l] = tab[a - 2][18 + l][lane];
-          sel.zzz.v[l] = tab[a - 2][27 + l][lane];
-        }
-      }
+      G1Xyzz29 sel = a == 1 ? xyzz29_from_affine(q) : xyzz_get(tab[a - 2], 0, lane);
       if (d < 0) sel.y = fq29_neg(sel.y);
       G1Xyzz29 sum = acc;
       xyzz29_add_fast(sum, sel);
@@ -164,45 +195,22 @@ __device__ __forceinline__ G1Xyzz29 half_scalar_mul_w3(const G1Affine29& q, cons
   return acc;
 }
 
-// K1: one lane per (term, GLV half).  k = k1 + k2*lambda with |k_i| < 2^127
-// (glv.h) turns `*base * scalar` (reference native.rs:67), a 254-step chain,
-// into two independent 127-step chains on P and phi(P) = (beta x, y).
+// K1, two-lane regime: one lane per (term, GLV half).
 __global__ void __launch_bounds__(64, SNARKV_NAIVE_WAVES) k_term_scalar_mul(const uint32_t* __restrict__ scalars,
                                                          const uint32_t* __restrict__ points,
                                                          G1Xyzz29* __restrict__ out, uint32_t n_terms,
                                                          int32_t* __restrict__ tabg, uint32_t mont) {
-#if SNARKV_NAIVE_WINDOW
   __shared__ int8_t dig[kWinDigits][64];
-#endif
   uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= 2 * n_terms) return;
-  uint32_t t = g >> 1, h = g & 1u;
-  uint32_t k[8], halves[8];
-  G1Affine29 q = load_term(scalars, points, t, mont, k);
-  glv_decompose(k, halves);
-  uint32_t mag[4] = {halves[4 * h], halves[4 * h + 1], halves[4 * h + 2], halves[4 * h + 3] & 0x7FFFFFFFu};
-  uint32_t neg = halves[4 * h + 3] >> 31;
-  if (g1a29_is_identity(q) || (mag[0] | mag[1] | mag[2] | mag[3]) == 0) {
+  const GlvHalf t = glv_half<false>(scalars, points, g >> 1, g & 1u, mont);
+  if (t.none) {
     out[g] = xyzz29_identity();
     return;
   }
-  if (h) {
-    constexpr int32_t bl[9] = SNARKV_GLV_BETA29_LIMBS;
-    Fq29 beta;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) beta.v[j] = bl[j];
-    q.x = fq29_canon_residue(fq29_mul(q.x, beta));
-  }
-  if (neg) q.y = fq29_neg(q.y);
-#if SNARKV_NAIVE_WINDOW
-  G1Xyzz29 r = half_scalar_mul_w3(q, mag, tabg, dig);
-#else
-  G1Xyzz29 r = half_scalar_mul<false>(q, mag);
-#endif
-  if (xyzz29_is_degenerate(r)) {  // P = +-Q met on the way (or a true identity): redo carefully
-    r = half_scalar_mul<true>(q, mag);
-    if (!xyzz29_is_identity(r) && xyzz29_is_degenerate(r)) r = xyzz29_identity();
-  }
+  const uint32_t mag[4] = {t.mag[0], t.mag[1], t.mag[2], t.mag[3]};
+  G1Xyzz29 r = half_scalar_mul_w3(t.q, mag, tabg, dig);
+  if (xyzz29_is_degenerate(r)) r = careful_half(t.q, mag);  // P = +-Q met on the way (or a true identity)
   out[g] = r;
 }
 
@@ -223,12 +231,13 @@ __global__ void __launch_bounds__(64, SNARKV_NAIVE_WAVES) k_term_scalar_mul(cons
 //             products each + an inversion worth ~55), which turns 14-product additions into 10-product ones
 //   digits    signed 3-bit, both halves, as NIBBLES in LDS (K x 2 x 22 bytes per lane)
 // Output: the group's sum in the slot of its first term, the identity in the group's other slots (the fold is unchanged).
-// A degenerate accumulator (P = +-Q met: e.g. a base listed twice in one group) sends every term of the group through the
-// careful bit-serial form.  A fast addition meets P = +-Q otherwise only if  sum_j (u_j + v_j lambda) P_j = +-d P_i  for
+// A degenerate accumulator (P = +-Q met: e.g. a base listed twice in one group) sends every term of the group through
+// careful_half.  A fast addition meets P = +-Q otherwise only if  sum_j (u_j + v_j lambda) P_j = +-d P_i  for
 // prefixes u, v of the lane's scalars: for independent bases never, for crafted ones the degenerate flag is the net.
 constexpr int kGroupMax = 4;
 constexpr int kGroupRows = 27 + 3 * 45 + 9;  // table rows per term: Q's x, y, beta x; 2Q, 3Q, 4Q with 45 rows each while they are
                                              // built (X, Y, ZZ, ZZZ, prefix product; x, y, beta x afterwards); the prefix before the term
+constexpr int kGroupPrefixRow = 27 + 3 * 45;
 
 __global__ void __launch_bounds__(256) k_gmap_count(const uint32_t* __restrict__ offsets, uint32_t n_msm, uint32_t* __restrict__ bsum) {
   __shared__ uint32_t sh[3][256];
@@ -347,10 +356,7 @@ __global__ void __launch_bounds__(64, SNARKV_NAIVE_WAVES)
   __shared__ uint8_t dig[kGroupMax][2][(kWinDigits + 1) / 2][64];
   const uint32_t lane = threadIdx.x, K = choice[0], T = choice[1];
   int32_t(*tab)[kGroupRows][64] = reinterpret_cast<int32_t(*)[kGroupRows][64]>(tabg + (size_t)blockIdx.x * kGroupMax * kGroupRows * 64);
-  constexpr int32_t bl[9] = SNARKV_GLV_BETA29_LIMBS;
-  Fq29 beta;
-#pragma unroll
-  for (int j = 0; j < 9; ++j) beta.v[j] = bl[j];
+  const Fq29 beta = glv_beta29();
 #pragma unroll 1
   for (uint32_t g0 = blockIdx.x * 64; g0 < T; g0 += gridDim.x * 64) {
     const uint32_t g = g0 + lane;
@@ -377,56 +383,31 @@ __global__ void __launch_bounds__(64, SNARKV_NAIVE_WAVES)
       if (has) {
         uint32_t k[8], halves[8];
         const G1Affine29 q = load_term(scalars, points, first + j, mont, k);
-        glv_decompose(k, halves);
+        glv_decompose(k, halves);  // ONE split for both halves of the term (glv_half would make it twice)
         uint32_t any = 0;
         for (int h = 0; h < 2; ++h) {
-          for (int w = 0; w < 4; ++w) mag[h][w] = halves[4 * h + w];
-          neg[h] = mag[h][3] >> 31;
-          mag[h][3] &= 0x7FFFFFFFu;
+          neg[h] = glv_mag_sign(halves, h, mag[h]);
           any |= mag[h][0] | mag[h][1] | mag[h][2] | mag[h][3];
         }
         if (g1a29_is_identity(q) || any == 0) {
           has = false;  // contributes nothing: all digits zero, table untouched
         } else {
           hasm |= 1u << j;
-          const Fq29 qbx = fq29_mul(q.x, beta);
-#pragma unroll
-          for (int l = 0; l < 9; ++l) {
-            tab[j][l][lane] = q.x.v[l];
-            tab[j][9 + l][lane] = q.y.v[l];
-            tab[j][18 + l][lane] = qbx.v[l];
-            tab[j][162 + l][lane] = running.v[l];  // the prefix product before this term's three elements
-          }
-          G1Xyzz29 t2 = xyzz29_double_affine(q), t3 = t2;
-          xyzz29_madd_fast(t3, q);
-          G1Xyzz29 t4 = xyzz29_double(t2);
-          auto put = [&](int e, const G1Xyzz29& v) {
+          col_put(tab[j], 0, lane, q.x);
+          col_put(tab[j], 9, lane, q.y);
+          col_put(tab[j], 18, lane, fq29_mul(q.x, beta));
+          col_put(tab[j], kGroupPrefixRow, lane, running);  // the prefix product before this term's three elements
+          table_2q_3q_4q(q, [&](int e, const G1Xyzz29& v) {
             running = fq29_mul(running, fq29_mul(v.zz, v.zzz));
-            const int r0 = 27 + 45 * e;
-#pragma unroll
-            for (int l = 0; l < 9; ++l) {
-              tab[j][r0 + l][lane] = v.x.v[l];
-              tab[j][r0 + 9 + l][lane] = v.y.v[l];
-              tab[j][r0 + 18 + l][lane] = v.zz.v[l];
-              tab[j][r0 + 27 + l][lane] = v.zzz.v[l];
-              tab[j][r0 + 36 + l][lane] = running.v[l];  // ... including this element
-            }
-          };
-          put(0, t2);
-          put(1, t3);
-          put(2, t4);
+            xyzz_put(tab[j], 27 + 45 * e, lane, v);
+            col_put(tab[j], 27 + 45 * e + 36, lane, running);  // ... including this element
+          });
         }
       }
       for (int h = 0; h < 2; ++h) {
         uint32_t carry = 0, pend = 0;
         for (int i = 0; i < kWinDigits; ++i) {
-          const int bit = 3 * i, word = bit >> 5, sh = bit & 31;
-          uint32_t w0 = word == 0 ? mag[h][0] : word == 1 ? mag[h][1] : word == 2 ? mag[h][2] : word == 3 ? mag[h][3] : 0u;
-          uint32_t w1 = word == 0 ? mag[h][1] : word == 1 ? mag[h][2] : word == 2 ? mag[h][3] : 0u;
-          uint32_t raw = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh) & 7u;
-          raw += carry;
-          carry = raw > 4u ? 1u : 0u;
-          int d = (int)raw - (carry ? 8 : 0);
+          int d = glv_w3_digit(mag[h][0], mag[h][1], mag[h][2], mag[h][3], i, carry);
           if (neg[h]) d = -d;
           const uint32_t enc = has ? (uint32_t)(d + 4) : 4u;  // 4 = the digit 0
           if (i & 1) dig[j][h][i >> 1][lane] = (uint8_t)(pend | (enc << 4));
@@ -443,27 +424,16 @@ __global__ void __launch_bounds__(64, SNARKV_NAIVE_WAVES)
         if (!((hasm >> j) & 1u)) continue;
 #pragma unroll 1
         for (int e = 2; e >= 0; --e) {
-          const int r0 = 27 + 45 * e, rp = e == 0 ? 162 : r0 - 45 + 36;  // where the prefix BEFORE this element lies
-          Fq29 X, Y, ZZ, ZZZ, prev;
-#pragma unroll
-          for (int l = 0; l < 9; ++l) {
-            X.v[l] = tab[j][r0 + l][lane];
-            Y.v[l] = tab[j][r0 + 9 + l][lane];
-            ZZ.v[l] = tab[j][r0 + 18 + l][lane];
-            ZZZ.v[l] = tab[j][r0 + 27 + l][lane];
-            prev.v[l] = tab[j][rp + l][lane];
-          }
-          const Fq29 izn = fq29_mul(inv, prev);   // 1 / (ZZ ZZZ) of this element
-          inv = fq29_mul(inv, fq29_mul(ZZ, ZZZ));  // ... and the inverse of the product up to the previous one
-          const Fq29 xa = fq29_mul(X, fq29_mul(izn, ZZZ));            // X / ZZ
-          const Fq29 ya = fq29_mul(fq29_norm(Y), fq29_mul(izn, ZZ));  // Y / ZZZ
-          const Fq29 bxa = fq29_mul(xa, beta);
-#pragma unroll
-          for (int l = 0; l < 9; ++l) {
-            tab[j][r0 + l][lane] = xa.v[l];
-            tab[j][r0 + 9 + l][lane] = ya.v[l];
-            tab[j][r0 + 18 + l][lane] = bxa.v[l];
-          }
+          const int r0 = 27 + 45 * e, rp = e == 0 ? kGroupPrefixRow : r0 - 45 + 36;  // where the prefix BEFORE this element lies
+          const G1Xyzz29 v = xyzz_get(tab[j], r0, lane);
+          const Fq29 prev = col_get(tab[j], rp, lane);
+          const Fq29 izn = fq29_mul(inv, prev);        // 1 / (ZZ ZZZ) of this element
+          inv = fq29_mul(inv, fq29_mul(v.zz, v.zzz));  // ... and the inverse of the product up to the previous one
+          const Fq29 xa = fq29_mul(v.x, fq29_mul(izn, v.zzz));            // X / ZZ
+          const Fq29 ya = fq29_mul(fq29_norm(v.y), fq29_mul(izn, v.zz));  // Y / ZZZ
+          col_put(tab[j], r0, lane, xa);
+          col_put(tab[j], r0 + 9, lane, ya);
+          col_put(tab[j], r0 + 18, lane, fq29_mul(xa, beta));
         }
       }
     }
@@ -481,11 +451,8 @@ __global__ void __launch_bounds__(64, SNARKV_NAIVE_WAVES)
         if (a != 0) {
           const int r0 = a == 1 ? 0 : 27 + 45 * (a - 2), xo = h ? 18 : 0;
           G1Affine29 sel;
-#pragma unroll
-          for (int l = 0; l < 9; ++l) {
-            sel.x.v[l] = tab[j][r0 + xo + l][lane];
-            sel.y.v[l] = tab[j][r0 + 9 + l][lane];
-          }
+          sel.x = col_get(tab[j], r0 + xo, lane);
+          sel.y = col_get(tab[j], r0 + 9, lane);
           if (d < 0) sel.y = fq29_neg(sel.y);
           G1Xyzz29 sum = acc;
           xyzz29_madd_fast(sum, sel);
@@ -495,28 +462,12 @@ __global__ void __launch_bounds__(64, SNARKV_NAIVE_WAVES)
       }
     }
     if (!live) continue;
-    if (started && xyzz29_is_degenerate(acc)) {  // an exceptional addition on the way: every term of the group, carefully
+    if (started && xyzz29_is_degenerate(acc)) {  // an exceptional addition on the way: every half of the group, carefully
 #pragma unroll 1
-      for (uint32_t j = 0; j < cnt; ++j) {
-        uint32_t k[8], halves[8], m0[4], m1[4];
-        const G1Affine29 q = load_term(scalars, points, first + j, mont, k);
-        glv_decompose(k, halves);
-        for (int w = 0; w < 4; ++w) m0[w] = halves[w], m1[w] = halves[4 + w];
-        const uint32_t n0 = m0[3] >> 31, n1 = m1[3] >> 31;
-        m0[3] &= 0x7FFFFFFFu, m1[3] &= 0x7FFFFFFFu;
-        G1Xyzz29 r1 = xyzz29_identity(), r2 = xyzz29_identity();
-        if (!g1a29_is_identity(q)) {
-          G1Affine29 q1 = q, q2 = q;
-          q2.x = fq29_canon_residue(fq29_mul(q.x, beta));
-          if (n0) q1.y = fq29_neg(q1.y);
-          if (n1) q2.y = fq29_neg(q2.y);
-          if ((m0[0] | m0[1] | m0[2] | m0[3]) != 0) r1 = half_scalar_mul<true>(q1, m0);
-          if (!xyzz29_is_identity(r1) && xyzz29_is_degenerate(r1)) r1 = xyzz29_identity();
-          if ((m1[0] | m1[1] | m1[2] | m1[3]) != 0) r2 = half_scalar_mul<true>(q2, m1);
-          if (!xyzz29_is_identity(r2) && xyzz29_is_degenerate(r2)) r2 = xyzz29_identity();
-        }
-        out[2 * (size_t)(first + j)] = r1;
-        out[2 * (size_t)(first + j) + 1] = r2;  // the fold adds them with the careful adder
+      for (uint32_t jh = 0; jh < 2 * cnt; ++jh) {
+        const GlvHalf t = glv_half<false>(scalars, points, first + (jh >> 1), jh & 1u, mont);
+        const uint32_t m[4] = {t.mag[0], t.mag[1], t.mag[2], t.mag[3]};
+        out[2 * (size_t)first + jh] = t.none ? xyzz29_identity() : careful_half(t.q, m);  // the fold adds them with the careful adder
       }
       continue;
     }
@@ -536,73 +487,45 @@ __global__ void __launch_bounds__(64, SNARKV_NAIVE_WAVES)
 //                       on Q_j, then a shuffle tree over the J adjacent lanes
 // Dependent field products per term: ~2400 -> ~900 + 23*bits.  Same partial
 // layout as K1 (one XYZZ per (term, half)), so K2 is unchanged.
+// K1a comes with ONE or (QUAD) FOUR lanes per (term, half): the same chain, every doubling by jac29_double_quad (3
+// dependent products instead of 7), lane 0 of the quad stores.  For small jobs -- an aggregation of 64 proofs is 1 666
+// terms -- the chain IS the launch's duration (120 doublings: 0.35 -> 0.19 ms); large jobs keep the one-lane form, whose
+// lanes all do useful work.  A quad never straddles a wavefront, and all four lanes take the same branches.
+template <bool QUAD>
+__device__ __forceinline__ void term_chain(const uint32_t* __restrict__ scalars, const uint32_t* __restrict__ points,
+                                           G1Xyzz29* __restrict__ chain, uint4* __restrict__ mags, uint32_t n_terms, uint32_t J,
+                                           uint32_t bits, uint32_t mont) {
+  const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t g = QUAD ? lane >> 2 : lane, q = QUAD ? lane & 3u : 0u;
+  if (g >= 2 * n_terms) return;
+  const GlvHalf t = glv_half<true>(scalars, points, g >> 1, g & 1u, mont);
+  if (q == 0) mags[g] = make_uint4(t.mag[0], t.mag[1], t.mag[2], t.mag[3]);  // all zero -> identity partial
+  G1Xyzz29* dst = chain + (size_t)g * J;
+  Fq29 x = t.q.x, y = t.q.y, z = fq29_one();
+  if (q == 0) dst[0] = jac29_to_xyzz(x, y, z);  // (x, y, 1, 1)
+  if (t.none) return;                           // bases never read
+  for (uint32_t j = 1; j < J; ++j) {
+    for (uint32_t i = 0; i < bits; ++i) {
+      if (QUAD) jac29_double_quad(x, y, z, q);
+      else jac29_double(x, y, z);
+    }
+    const G1Xyzz29 b = jac29_to_xyzz(x, y, z);
+    if (q == 0) dst[j] = b;
+  }
+}
+
 __global__ void __launch_bounds__(64) k_term_chain(const uint32_t* __restrict__ scalars,
                                                     const uint32_t* __restrict__ points,
                                                     G1Xyzz29* __restrict__ chain, uint4* __restrict__ mags,
                                                     uint32_t n_terms, uint32_t J, uint32_t bits, uint32_t mont) {
-  uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= 2 * n_terms) return;
-  uint32_t t = g >> 1, h = g & 1u;
-  uint32_t k[8], halves[8];
-  G1Affine29 q = load_term(scalars, points, t, mont, k);
-  glv_decompose(k, halves);
-  uint4 mag = make_uint4(halves[4 * h], halves[4 * h + 1], halves[4 * h + 2], halves[4 * h + 3] & 0x7FFFFFFFu);
-  uint32_t neg = halves[4 * h + 3] >> 31;
-  if (g1a29_is_identity(q)) mag = make_uint4(0, 0, 0, 0);  // all digits zero -> identity partial
-  mags[g] = mag;
-  if (h) {
-    constexpr int32_t bl[9] = SNARKV_GLV_BETA29_LIMBS;
-    Fq29 beta;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) beta.v[j] = bl[j];
-    q.x = fq29_canon_residue(fq29_mul(q.x, beta));
-  }
-  if (neg) q.y = fq29_norm(fq29_neg(q.y));
-  G1Xyzz29* dst = chain + (size_t)g * J;
-  Fq29 x = q.x, y = q.y, z = fq29_one();
-  dst[0] = jac29_to_xyzz(x, y, z);  // (x, y, 1, 1)
-  if ((mag.x | mag.y | mag.z | mag.w) == 0) return;  // bases never read
-  for (uint32_t j = 1; j < J; ++j) {
-    for (uint32_t i = 0; i < bits; ++i) jac29_double(x, y, z);
-    dst[j] = jac29_to_xyzz(x, y, z);
-  }
+  term_chain<false>(scalars, points, chain, mags, n_terms, J, bits, mont);
 }
 
-// K1a with FOUR lanes per (term, half): the same chain, every doubling by jac29_double_quad (3 dependent products
-// instead of 7).  For small jobs -- an aggregation of 64 proofs is 1 666 terms -- the chain IS the launch's duration
-// (120 doublings: 0.35 -> 0.19 ms); large jobs keep the one-lane form, whose lanes all do useful work.
 __global__ void __launch_bounds__(64) k_term_chain_quad(const uint32_t* __restrict__ scalars,
                                                          const uint32_t* __restrict__ points,
                                                          G1Xyzz29* __restrict__ chain, uint4* __restrict__ mags,
                                                          uint32_t n_terms, uint32_t J, uint32_t bits, uint32_t mont) {
-  uint32_t lane4 = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t g = lane4 >> 2, q = lane4 & 3u;  // a quad never straddles a wavefront; all four lanes take the same branches
-  if (g >= 2 * n_terms) return;
-  uint32_t t = g >> 1, h = g & 1u;
-  uint32_t k[8], halves[8];
-  G1Affine29 p = load_term(scalars, points, t, mont, k);
-  glv_decompose(k, halves);
-  uint4 mag = make_uint4(halves[4 * h], halves[4 * h + 1], halves[4 * h + 2], halves[4 * h + 3] & 0x7FFFFFFFu);
-  uint32_t neg = halves[4 * h + 3] >> 31;
-  if (g1a29_is_identity(p)) mag = make_uint4(0, 0, 0, 0);
-  if (q == 0) mags[g] = mag;
-  if (h) {
-    constexpr int32_t bl[9] = SNARKV_GLV_BETA29_LIMBS;
-    Fq29 beta;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) beta.v[j] = bl[j];
-    p.x = fq29_canon_residue(fq29_mul(p.x, beta));
-  }
-  if (neg) p.y = fq29_norm(fq29_neg(p.y));
-  G1Xyzz29* dst = chain + (size_t)g * J;
-  Fq29 x = p.x, y = p.y, z = fq29_one();
-  if (q == 0) dst[0] = jac29_to_xyzz(x, y, z);
-  if ((mag.x | mag.y | mag.z | mag.w) == 0) return;
-  for (uint32_t j = 1; j < J; ++j) {
-    for (uint32_t i = 0; i < bits; ++i) jac29_double_quad(x, y, z, q);
-    G1Xyzz29 b = jac29_to_xyzz(x, y, z);
-    if (q == 0) dst[j] = b;
-  }
+  term_chain<true>(scalars, points, chain, mags, n_terms, J, bits, mont);
 }
 
 __device__ __forceinline__ G1Xyzz29 xyzz29_shfl_xor(const G1Xyzz29& p, int mask) {
@@ -666,9 +589,8 @@ __global__ void __launch_bounds__(64) k_term_chunks(const G1Xyzz29* __restrict__
       G1Affine29 q;
       q.x = b0.x;
       q.y = b0.y;
-      uint32_t m4[4] = {mag.x, mag.y, mag.z, mag.w};
-      acc = half_scalar_mul<true>(q, m4);
-      if (!xyzz29_is_identity(acc) && xyzz29_is_degenerate(acc)) acc = xyzz29_identity();
+      const uint32_t m4[4] = {mag.x, mag.y, mag.z, mag.w};
+      acc = careful_half(q, m4);
     }
     out[g] = acc;
   }
@@ -762,10 +684,89 @@ static uint32_t chunks_for(size_t n_terms) {
   return 1;
 }
 
+// ---- term stage, group regime: several terms of a segment per lane on shared doublings; the lane -> segment map is built
+// on the device.  jmode 1: K chosen there; 2, 3, 4: K forced.
+static int launch_terms_group(snarkv_ctx* ctx, const uint32_t* d_scalars, const uint32_t* d_points, const uint32_t* d_offsets,
+                              size_t n_msm, size_t n_terms, G1Xyzz29* d_terms, int jmode, uint32_t mont) {
+  static int slots = 0;  // resident wavefronts of this kernel: 2 per SIMD
+  if (!slots) {
+    hipDeviceProp_t prop;
+    slots = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0 ? 8 * prop.multiProcessorCount : 2048;
+  }
+  const uint32_t nblk = (uint32_t)((n_msm + 1023) / 1024);
+  const size_t max_lanes = n_terms / 2 + n_msm + 1;
+  const uint32_t grid = (uint32_t)std::min<size_t>((size_t)slots, (max_lanes + 63) / 64);
+  void* d_map = nullptr;
+  void* d_tab = nullptr;  // the fixed-window tables, limb-major per lane
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_MAGS, ((size_t)3 * nblk + n_msm + 1 + 8) * 4, &d_map));
+  uint32_t* bsum = (uint32_t*)d_map;
+  uint32_t* choice = bsum + 3 * (size_t)nblk;
+  uint32_t* base = choice + 8;
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_CHAIN, (size_t)grid * kGroupMax * kGroupRows * 64 * 4, &d_tab));
+  hipLaunchKernelGGL(k_gmap_count, dim3(nblk), dim3(256), 0, ctx->stream, d_offsets, (uint32_t)n_msm, bsum);
+  // the slots THIS launch can count on: the whole machine when it runs alone; under the throughput hint other launches
+  // share it -- as many as the hint / the context pool says (16 when it does not: what bench.py keeps in flight) -- and
+  // the choice then goes by total work, as it should when the machine is full whatever this launch does
+  const int peers = ctx->throughput_peers > 1 ? ctx->throughput_peers : 16;
+  const uint32_t my_slots = ctx->throughput_mode ? (uint32_t)std::max(1, slots / peers) : (uint32_t)slots;
+  hipLaunchKernelGGL(k_gmap_choose, dim3(1), dim3(1024), 0, ctx->stream, bsum, nblk, choice, (uint32_t)(jmode >= 2 ? jmode : 0), my_slots);
+  hipLaunchKernelGGL(k_gmap_fill, dim3(nblk), dim3(256), 0, ctx->stream, d_offsets, (uint32_t)n_msm, (const uint32_t*)bsum,
+                     (const uint32_t*)choice, base);
+  hipLaunchKernelGGL(k_term_scalar_mul_group, dim3(grid), dim3(64), 0, ctx->stream, d_scalars, d_points, d_terms, d_offsets,
+                     (uint32_t)n_msm, (const uint32_t*)base, (const uint32_t*)choice, (int32_t*)d_tab, mont);
+  return SNARKV_OK;
+}
+
+// ---- term stage, two-lane regime: one lane per (term, half), a table slice per wavefront
+static int launch_terms_two_lane(snarkv_ctx* ctx, const uint32_t* d_scalars, const uint32_t* d_points, size_t n_terms,
+                                 G1Xyzz29* d_terms, uint32_t mont) {
+  void* d_tab = nullptr;
+  const uint32_t blocks = (uint32_t)((2 * n_terms + 63) / 64);
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_CHAIN, (size_t)blocks * 3 * 36 * 64 * 4, &d_tab));
+  hipLaunchKernelGGL(k_term_scalar_mul, dim3(blocks), dim3(64), 0, ctx->stream, d_scalars, d_points, d_terms, (uint32_t)n_terms,
+                     (int32_t*)d_tab, mont);
+  return SNARKV_OK;
+}
+
+// ---- term stage, chunked regime: J >= 2 chunk bases per half from one doubling chain, then one lane per chunk
+static int launch_terms_chunked(snarkv_ctx* ctx, const uint32_t* d_scalars, const uint32_t* d_points, size_t n_terms,
+                                G1Xyzz29* d_terms, uint32_t J, uint32_t mont) {
+  void* d_chain = nullptr;
+  void* d_mags = nullptr;
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_CHAIN, 2 * n_terms * J * sizeof(G1Xyzz29), &d_chain));
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_MAGS, 2 * n_terms * sizeof(uint4), &d_mags));
+  const uint32_t bits = 128 / J;
+  const char* eq = getenv("SNARKV_NAIVE_QUAD");  // 0 / 1 force the one-lane / four-lane chain (test knob)
+  const bool quad = eq ? atoi(eq) != 0 : 8 * n_terms <= 262144;  // four lanes per chain while they all fit the wave slots
+  if (quad)
+    hipLaunchKernelGGL(k_term_chain_quad, dim3((uint32_t)((8 * n_terms + 63) / 64)), dim3(64), 0, ctx->stream, d_scalars,
+                       d_points, (G1Xyzz29*)d_chain, (uint4*)d_mags, (uint32_t)n_terms, J, bits, mont);
+  else
+    hipLaunchKernelGGL(k_term_chain, dim3((uint32_t)((2 * n_terms + 63) / 64)), dim3(64), 0, ctx->stream, d_scalars, d_points,
+                       (G1Xyzz29*)d_chain, (uint4*)d_mags, (uint32_t)n_terms, J, bits, mont);
+  const uint32_t n_lanes = (uint32_t)(2 * n_terms * J);
+  hipLaunchKernelGGL(k_term_chunks, dim3((n_lanes + 63) / 64), dim3(64), 0, ctx->stream, (const G1Xyzz29*)d_chain,
+                     (const uint4*)d_mags, d_terms, n_lanes, J, bits);
+  return SNARKV_OK;
+}
+
+// ---- fold stage: lanes per MSM by the average segment length (k_segment_fold's comment)
+static void launch_fold(snarkv_ctx* ctx, const G1Xyzz29* d_terms, const uint32_t* d_offsets, size_t n_msm, size_t n_terms,
+                        uint32_t* d_out, uint32_t mont) {
+  const uint32_t nm = (uint32_t)n_msm;
+  if (n_terms >= 128 * n_msm)
+    hipLaunchKernelGGL((k_segment_fold<256, 256>), dim3(nm), dim3(256), 0, ctx->stream, d_terms, d_offsets, d_out, nm, mont);
+  else if (n_terms > 32 * n_msm)
+    hipLaunchKernelGGL((k_segment_fold<64, 64>), dim3(nm), dim3(64), 0, ctx->stream, d_terms, d_offsets, d_out, nm, mont);
+  else  // <= 64 partials per MSM on average: four MSMs per wavefront
+    hipLaunchKernelGGL((k_segment_fold<64, 16>), dim3((nm + 3) / 4), dim3(64), 0, ctx->stream, d_terms, d_offsets, d_out, nm, mont);
+}
+
 int launch_msm_batched(snarkv_ctx* ctx, const void* d_scalars, const void* d_points, const void* d_offsets,
                        size_t n_msm, size_t n_terms, void* d_out) {
   void* d_terms = nullptr;
   const uint32_t mont = ctx->mont ? 1u : 0u;  // SNARKV_FLAG_MONTGOMERY: terms in and points out in halo2curves' in-memory form
+  const uint32_t *sc = (const uint32_t*)d_scalars, *pt = (const uint32_t*)d_points, *of = (const uint32_t*)d_offsets;
   SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_PARTIALS, 2 * n_terms * sizeof(G1Xyzz29), &d_terms));
   const uint32_t J = chunks_for(n_terms);
   if (J == 1) {
@@ -773,71 +774,12 @@ int launch_msm_batched(snarkv_ctx* ctx, const void* d_scalars, const void* d_poi
     // throughput hint) take the grouped form: a third of the issued work on a chain K times as long
     const char* ej = getenv("SNARKV_NAIVE_JOINT");  // 0 two lanes per term / 1 groups (K chosen on the device) / 2, 3, 4: groups of that K (test / A-B knob)
     const int jmode = ej ? atoi(ej) : ((n_terms >= 49152 || ctx->throughput_mode) ? 1 : 0);
-    void* d_tab = nullptr;  // the fixed-window tables, limb-major per lane
-    if (jmode >= 1) {
-      // several terms of a segment per lane on shared doublings; the lane -> segment map is built on the device
-      static int slots = 0;  // resident wavefronts of this kernel: 2 per SIMD
-      if (!slots) {
-        hipDeviceProp_t prop;
-        slots = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0 ? 8 * prop.multiProcessorCount : 2048;
-      }
-      const uint32_t nblk = (uint32_t)((n_msm + 1023) / 1024);
-      const size_t max_lanes = n_terms / 2 + n_msm + 1;
-      const uint32_t grid = (uint32_t)std::min<size_t>((size_t)slots, (max_lanes + 63) / 64);
-      void* d_map = nullptr;
-      SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_MAGS, ((size_t)3 * nblk + n_msm + 1 + 8) * 4, &d_map));
-      uint32_t* bsum = (uint32_t*)d_map;
-      uint32_t* choice = bsum + 3 * (size_t)nblk;
-      uint32_t* base = choice + 8;
-      SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_CHAIN, (size_t)grid * kGroupMax * kGroupRows * 64 * 4, &d_tab));
-      hipLaunchKernelGGL(k_gmap_count, dim3(nblk), dim3(256), 0, ctx->stream, (const uint32_t*)d_offsets, (uint32_t)n_msm, bsum);
-      // the slots THIS launch can count on: the whole machine when it runs alone; under the throughput hint other launches
-      // share it -- as many as the hint / the context pool says (16 when it does not: what bench.py keeps in flight) -- and
-      // the choice then goes by total work, as it should when the machine is full whatever this launch does
-      const int peers = ctx->throughput_peers > 1 ? ctx->throughput_peers : 16;
-      const uint32_t my_slots = ctx->throughput_mode ? (uint32_t)std::max(1, slots / peers) : (uint32_t)slots;
-      hipLaunchKernelGGL(k_gmap_choose, dim3(1), dim3(1024), 0, ctx->stream, bsum, nblk, choice, (uint32_t)(jmode >= 2 ? jmode : 0), my_slots);
-      hipLaunchKernelGGL(k_gmap_fill, dim3(nblk), dim3(256), 0, ctx->stream, (const uint32_t*)d_offsets, (uint32_t)n_msm,
-                         (const uint32_t*)bsum, (const uint32_t*)choice, base);
-      hipLaunchKernelGGL(k_term_scalar_mul_group, dim3(grid), dim3(64), 0, ctx->stream, (const uint32_t*)d_scalars,
-                         (const uint32_t*)d_points, (G1Xyzz29*)d_terms, (const uint32_t*)d_offsets, (uint32_t)n_msm,
-                         (const uint32_t*)base, (const uint32_t*)choice, (int32_t*)d_tab, mont);
-    } else {
-      uint32_t blocks = (uint32_t)((2 * n_terms + 63) / 64);
-      SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_CHAIN, (size_t)blocks * 3 * 36 * 64 * 4, &d_tab));
-      hipLaunchKernelGGL(k_term_scalar_mul, dim3(blocks), dim3(64), 0, ctx->stream, (const uint32_t*)d_scalars,
-                         (const uint32_t*)d_points, (G1Xyzz29*)d_terms, (uint32_t)n_terms, (int32_t*)d_tab, mont);
-    }
+    if (jmode >= 1) SNARKV_TRY(launch_terms_group(ctx, sc, pt, of, n_msm, n_terms, (G1Xyzz29*)d_terms, jmode, mont));
+    else SNARKV_TRY(launch_terms_two_lane(ctx, sc, pt, n_terms, (G1Xyzz29*)d_terms, mont));
   } else {
-    void* d_chain = nullptr;
-    void* d_mags = nullptr;
-    SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_CHAIN, 2 * n_terms * J * sizeof(G1Xyzz29), &d_chain));
-    SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_MAGS, 2 * n_terms * sizeof(uint4), &d_mags));
-    const uint32_t bits = 128 / J;
-    uint32_t blocks_a = (uint32_t)((2 * n_terms + 63) / 64);
-    const char* eq = getenv("SNARKV_NAIVE_QUAD");  // 0 / 1 force the one-lane / four-lane chain (test knob)
-    const bool quad = eq ? atoi(eq) != 0 : 8 * n_terms <= 262144;  // four lanes per chain while they all fit the wave slots
-    if (quad)
-      hipLaunchKernelGGL(k_term_chain_quad, dim3((uint32_t)((8 * n_terms + 63) / 64)), dim3(64), 0, ctx->stream,
-                         (const uint32_t*)d_scalars, (const uint32_t*)d_points, (G1Xyzz29*)d_chain, (uint4*)d_mags,
-                         (uint32_t)n_terms, J, bits, mont);
-    else
-      hipLaunchKernelGGL(k_term_chain, dim3(blocks_a), dim3(64), 0, ctx->stream, (const uint32_t*)d_scalars,
-                         (const uint32_t*)d_points, (G1Xyzz29*)d_chain, (uint4*)d_mags, (uint32_t)n_terms, J, bits, mont);
-    uint32_t n_lanes = (uint32_t)(2 * n_terms * J);
-    hipLaunchKernelGGL(k_term_chunks, dim3((n_lanes + 63) / 64), dim3(64), 0, ctx->stream,
-                       (const G1Xyzz29*)d_chain, (const uint4*)d_mags, (G1Xyzz29*)d_terms, n_lanes, J, bits);
+    SNARKV_TRY(launch_terms_chunked(ctx, sc, pt, n_terms, (G1Xyzz29*)d_terms, J, mont));
   }
-  const uint32_t nm = (uint32_t)n_msm;
-  if (n_terms >= 128 * n_msm)
-    hipLaunchKernelGGL((k_segment_fold<256, 256>), dim3(nm), dim3(256), 0, ctx->stream, (const G1Xyzz29*)d_terms,
-                       (const uint32_t*)d_offsets, (uint32_t*)d_out, nm, mont);
-  else if (n_terms > 32 * n_msm)
-    hipLaunchKernelGGL((k_segment_fold<64, 64>), dim3(nm), dim3(64), 0, ctx->stream, (const G1Xyzz29*)d_terms,
-                       (const uint32_t*)d_offsets, (uint32_t*)d_out, nm, mont);
-  else  // <= 64 partials per MSM on average: four MSMs per wavefront
-    hipLaunchKernelGGL((k_segment_fold<64, 16>), dim3((nm + 3) / 4), dim3(64), 0, ctx->stream, (const G1Xyzz29*)d_terms,
-                       (const uint32_t*)d_offsets, (uint32_t*)d_out, nm, mont);
+  launch_fold(ctx, (const G1Xyzz29*)d_terms, of, n_msm, n_terms, (uint32_t*)d_out, mont);
   SNARKV_HIP(hipGetLastError());
   return SNARKV_OK;
 }

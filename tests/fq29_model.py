@@ -42,7 +42,7 @@ OPS = {
     "xyzz29_add_careful": (72, 36), "xyzz29_add_skipid_fast": (73, 37), "xyzz29_double": (36, 36),
     "jac29_double": (28, 27), "xyzz29_double_n": (37, 36), "jac29_to_xyzz": (27, 36), "xyzz29_is_degenerate": (36, 1),
     "xyzz29_to_affine": (36, 18), "g1_29_scalar_mul_fast": (26, 36), "g1_29_scalar_mul_careful": (26, 36),
-    "glv_decompose": (8, 8),
+    "glv_decompose": (8, 8), "glv_w3_digits": (4, 43),
 }
 
 
@@ -1090,6 +1090,32 @@ def glv_rows(C):
     ks += [x for lam in lams for x in (lam, R - lam, lam * 7 % R)]
     ks += [rnd.randrange(R) for _ in range(4000)]
     return _arr([words_i32(k) for k in ks]), ks
+
+
+W3_DIGITS = 43  # kWinDigits of csrc/glv.h
+
+
+def w3_rows():
+    """127-bit magnitudes for the signed 3-bit recoder: the edges (0, 1, 4 = the largest digit kept, 5 = the smallest that
+    carries, 2^127 - 1, every 3-bit field 0b100 resp. 0b101) and seeded random ones of every length"""
+    rnd = random.Random(43)
+    top = (1 << 127) - 1
+    all4 = sum(4 << (3 * i) for i in range(43)) & top
+    all5 = sum(5 << (3 * i) for i in range(43)) & top
+    ms = [0, 1, 4, 5, top, all4, all5, 3, 7, 8, 1 << 126, (1 << 96) - 1, 1 << 96, 0xFFFFFFFF, 1 << 32]
+    ms += [rnd.getrandbits(127) for _ in range(2000)]
+    ms += [rnd.getrandbits(rnd.randrange(1, 128)) for _ in range(2000)]
+    return _arr([words_i32(m)[:4] for m in ms]), ms
+
+
+def w3_suite(run):
+    """every digit within [-3, 4] and sum d_i 8^i the magnitude itself; returns (records in, records checked)"""
+    rows, ms = w3_rows()
+    out = np.asarray(run("glv_w3_digits", rows)).tolist()
+    for m, d in zip(ms, out):
+        assert len(d) == W3_DIGITS and all(-3 <= x <= 4 for x in d), "digit out of [-3, 4] for %#x: %r" % (m, d)
+        assert sum(x << (3 * i) for i, x in enumerate(d)) == m, "digits of %#x do not sum to it: %r" % (m, d)
+    return len(ms), len(out)
 
 
 def chain_suite(C, run, npts=256, model_long=8):

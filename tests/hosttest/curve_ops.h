@@ -180,6 +180,12 @@ SNARKV_HD void op_glv_decompose(const int32_t* in, int32_t* out) {
   glv_decompose(k, o);
   stw(o, out);
 }
+// in: a magnitude below 2^127 (4 words); out: its kWinDigits signed 3-bit digits, low to high
+SNARKV_HD void op_glv_w3_digits(const int32_t* in, int32_t* out) {
+  uint32_t carry = 0;
+  for (int i = 0; i < kWinDigits; ++i)
+    out[i] = glv_w3_digit((uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], (uint32_t)in[3], i, carry);
+}
 
 }  // namespace rawops
 }  // namespace snarkv
@@ -216,4 +222,5 @@ SNARKV_HD void op_glv_decompose(const int32_t* in, int32_t* out) {
   X(xyzz29_to_affine, 36, 18)            \
   X(g1_29_scalar_mul_fast, 26, 36)       \
   X(g1_29_scalar_mul_careful, 26, 36)    \
-  X(glv_decompose, 8, 8)
+  X(glv_decompose, 8, 8)                \
+  X(glv_w3_digits, 4, 43)

@@ -84,6 +84,14 @@ def test_glv_raw_entry_is_the_byte_entry(curve):
         assert buf.raw == row.astype("<i4").tobytes()
 
 
+@pytest.mark.parametrize("curve", CURVE_NAMES)
+def test_signed_3bit_recoder(curve):
+    """glv_w3_digit, the recoder of the segmented MSM's fixed window: digits in [-3, 4] that sum to the magnitude, at the
+    edge magnitudes (0, 1, 4, 5, 2^127 - 1, all-0b100, all-0b101) and seeded random ones"""
+    n, checked = M.w3_suite(M.host_runner(curve))
+    assert n == checked >= 4000
+
+
 def _kernel_mads(asm_text, kernel):
     lines = asm_text.split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^_ZN\w*7devtest\d+%sEPKiPii:" % kernel, l))

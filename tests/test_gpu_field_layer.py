@@ -116,3 +116,9 @@ def test_glv_split_on_the_device_is_the_hosts(builds):
     rows, ks = M.glv_rows(M.CURVES[builds.curve])
     out = builds("glv_decompose", rows)  # bit-equal across the three builds inside
     assert len(out) == len(ks) >= 4000
+
+
+def test_signed_3bit_recoder_on_the_device(builds):
+    """the cases of test_signed_3bit_recoder (tests/test_curve_math_lazy_host.py); bit-equal across the three builds inside"""
+    n, checked = M.w3_suite(builds)
+    assert n == checked >= 4000

@@ -1,6 +1,6 @@
 #!/bin/bash
 # dev tool (GPU box): interleaved A/B of library variants on the aggregation job (tools/aggregate_job.py), medians
-#   tools/ab_agg.sh <rounds> <proofs> default bitserial ...
+#   tools/ab_agg.sh <rounds> <proofs> default waves3 ...
 cd "$(dirname "$0")/.."
 ROUNDS=$1; PROOFS=$2; shift; shift
 for r in $(seq 1 $ROUNDS); do

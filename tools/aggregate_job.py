@@ -15,6 +15,7 @@ import snark_verifier_amd as sv
 ap = argparse.ArgumentParser()
 ap.add_argument("--proofs", type=int, default=64)
 ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--digest", action="store_true", help="print a sha256 over the MSM outputs and the accumulator after the last job")
 a = ap.parse_args()
 st = torch.cuda.Stream()
 ctx = sv.Context(0, stream=st.cuda_stream)
@@ -54,4 +55,8 @@ for _ in range(a.reps):
     job()
 torch.cuda.synchronize()
 print("aggregate_%d_proofs: %.4f ms per job" % (m, (time.perf_counter() - t0) / a.reps * 1e3))
+if a.digest:
+    import hashlib
+
+    print("digest_%d_proofs: %s" % (m, hashlib.sha256(out1.cpu().numpy().tobytes() + acc.cpu().numpy().tobytes()).hexdigest()))
 dk.close()

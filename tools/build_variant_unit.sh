@@ -1,7 +1,7 @@
 #!/bin/bash
 # dev tool: rebuild ONE unit (csrc/<unit>.hip) with extra flags and link it with the current objects of the other units
 # into tools/tmp/libsnarkv_<name>.so (the default build is left untouched)
-#   tools/build_variant_unit.sh msm_naive bitserial "-DSNARKV_NAIVE_WINDOW=0"
+#   tools/build_variant_unit.sh msm_naive waves3 "-DSNARKV_NAIVE_WAVES=3"
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p tools/tmp
