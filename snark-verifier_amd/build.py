@@ -53,6 +53,7 @@ def build(verbose=False):
     jobs = [(u, (), "") for u in UNITS] + [(u, tuple(PALLAS_FLAGS), "_pallas") for u in PALLAS_UNITS]
     with ThreadPoolExecutor(max_workers=min(len(jobs) + len(DEVTEST_FLAVOURS), os.cpu_count() or 4)) as ex:
         devtest = [ex.submit(build_devtest, f) for f in DEVTEST_FLAVOURS]  # the test-only device units ride in the same pool
+        devtest += [ex.submit(build_hosttest_curve, c) for c in ("bn254", "pallas")]
         res = list(ex.map(lambda j: _compile(j[0], verbose, j[1], j[2]), jobs))
         for d in devtest:
             d.result()
@@ -87,6 +88,24 @@ DEVTEST_FLAVOURS = {"bn254_asm": [], "bn254_c": ["-DSNARKV_NO_SMAD_ASM"],
 
 def devtest_sources():
     return [os.path.join(DEVTEST_DIR, "devtest.hip"), os.path.join(DEVTEST_DIR, "..", "hosttest", "curve_ops.h")]
+
+
+# The same operations for the host (tests/hosttest/hosttest_curve.cpp: the plain-C bodies, plus the lane-by-lane emulation of
+# the decider's rounds and the dumps of its generated programs), one library per curve, next to its source.
+HOSTTEST_DIR = os.path.join(HERE, "..", "tests", "hosttest")
+
+
+def build_hosttest_curve(curve):
+    out = os.path.join(HOSTTEST_DIR, "libhosttest_%s.so" % curve)
+    srcs = [os.path.join(HOSTTEST_DIR, f) for f in ("hosttest_curve.cpp", "curve_ops.h")]
+    if os.path.exists(out) and os.path.getmtime(out) >= max([_deps()] + [os.path.getmtime(f) for f in srcs]):
+        return out
+    flags = ["-DSNARKV_CURVE_PALLAS"] if curve == "pallas" else []
+    r = subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC"] + flags + ["-o", out, srcs[0]], capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout + r.stderr)
+        raise RuntimeError("host build failed: hosttest_curve.cpp (%s)" % curve)
+    return out
 
 
 def devtest_lib(flavour):

@@ -142,8 +142,9 @@ SNARKV_HD WtLaneC wt_lane_c(int half, int lane) {
 
 // The lane's contribution to its output coefficient: one fused two-product Montgomery step, or zero.
 //   e = 0:  a0 y0 - a1 y1      e = 1:  a0 y0 + a1 y1       with (y0, y1) = (b_e, b_(1-e)) of the chosen B coefficient
-// Every operand is carry-normalised (|limb| < 2^29): plain values within 1.5 p, xi copies within 15 p, so the sum of the
-// two products is below 45 p^2 and the step's output within (-0.3 p, 1.3 p).
+// Every operand has |limb| < 2^29: plain values (PLAIN_W: squeezed values, the single products of wt_eval_line and
+// wt_fq2inv, canonical constants) within 1.01 p, xi copies within 10.1 p (seen: 10.05 p), so the sum of the two products
+// is below 20.5 p^2 and the step's output inside (-p/8, 9p/8), the one range of pairing_coop29.h.
 SNARKV_HD Fq29 wt_task_c(const Fq29P* lds, const WtOp op, const WtLaneC& C) {
   const bool pw = op.kind == WT_PW;
   // the offset of the operation's addressing mode, picked with uniform masks (an indexed pick would put the lane's
@@ -170,12 +171,11 @@ SNARKV_HD Fq29 wt_task_c(const Fq29P* lds, const WtOp op, const WtLaneC& C) {
 SNARKV_HD Fq29 wt_task(const Fq29P* lds, const WtOp op, int half, int lane) { return wt_task_c(lds, op, wt_lane_c(half, lane)); }
 
 // s = limb-wise sum of <= 6 task outputs (limbs 0..7 read as unsigned: < 6 * 2^29; limb 8 signed).  Returns the
-// carry-normalised representative within 0.5 p (+ the estimate's slack: < 1.5 p) of the same residue: the quotient is
+// carry-normalised representative within (1/2 + 2^-13) p (seen: 0.500001 p) of the same residue: the quotient is
 // estimated from the top limb alone (the lower limbs carry at most 6 into it, against p >> 232 = 2^21.6).
 SNARKV_HD Fq29 wt_squeeze(const Fq29& s) {
   const float inv_ptop = 1.0f / (float)fq29_p(8);
-  const float qf = (float)s.v[8] * inv_ptop;
-  const int32_t q = (int32_t)(qf + (qf >= 0 ? 0.5f : -0.5f));
+  const int32_t q = (int32_t)__builtin_fmaf((float)s.v[8], inv_ptop, s.v[8] >= 0 ? 0.5f : -0.5f);  // one rounding: fq29_reduce_small
   Fq29 r;
   int64_t c = 0;
 #pragma unroll
@@ -189,7 +189,7 @@ SNARKV_HD Fq29 wt_squeeze(const Fq29& s) {
 }
 
 // component e of xi * (c0 + c1 u) = (9 c0 - c1) + (c0 + 9 c1) u, from own = c_e and other = c_(1-e); carry-normalised,
-// within 15 p for inputs within 1.5 p
+// the exact integer 9 own -/+ other: within 10.1 p for inputs within 1.01 p (seen: 10.05 p)
 SNARKV_HD Fq29 wt_xi(const Fq29& own, const Fq29& other, int e) {
   Fq29 r;
   int64_t c = 0;

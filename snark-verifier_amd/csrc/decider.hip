@@ -87,24 +87,6 @@ __shared__ Fq29 g_lines4[2][kLinesPerG2][4];
 
 static __device__ __forceinline__ void coop_store(int dst, int c, const Fq29& val) { g_sh.r[dst].v[c] = val; }
 
-// DPP lane exchange inside a 16-lane row (no LDS, no barrier)
-template <int CTRL>
-static __device__ __forceinline__ uint32_t dpp_u32(uint32_t x) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, true);
-}
-
-// every lane of an aligned 8-lane group gets the limb-wise sum over the group
-// (limbs as unsigned: <= 6 live terms of < 2^29 each)
-static __device__ __forceinline__ Fq29 group8_sum(Fq29 x) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) x.v[i] = (int32_t)((uint32_t)x.v[i] + dpp_u32<0xB1>((uint32_t)x.v[i]));   // quad_perm [1,0,3,2]
-#pragma unroll
-  for (int i = 0; i < 9; ++i) x.v[i] = (int32_t)((uint32_t)x.v[i] + dpp_u32<0x4E>((uint32_t)x.v[i]));   // quad_perm [2,3,0,1]
-#pragma unroll
-  for (int i = 0; i < 9; ++i) x.v[i] = (int32_t)((uint32_t)x.v[i] + dpp_u32<0x141>((uint32_t)x.v[i]));  // row_half_mirror
-  return x;
-}
-
 // dst = a * b, b a register (b_reg >= 0) or the sparse line (pair, idx): only
 // w^0, w^1, w^3 non-zero.  All lanes of the workgroup call it.
 static __device__ __forceinline__ void coop_mul_b(int dst, int a, int b_reg, int pair, int idx,
@@ -166,12 +148,6 @@ static __device__ __noinline__ void coop_conj(int dst, int a) {
   __syncthreads();
 }
 
-// dst_i = conj^cj(a_i) * (g0 + g1 u) for the Fq2 coefficients i >= first (others copied)
-static __device__ __forceinline__ Fq29 fq2_scale_lane(const Fq29& x, const Fq29& y, const Fq29& g0, const Fq29& g1, int e) {
-  // (x + y u)(g0 + g1 u) = (x g0 - y g1) + (x g1 + y g0) u ; every product N, so the lazy sum stays < 2^30
-  return e ? fq29_add(fq29_mul(x, g1), fq29_mul(y, g0)) : fq29_sub(fq29_mul(x, g0), fq29_mul(y, g1));
-}
-
 // dst = a^(p^k), k in {1,2,3}: g_i -> conj^k(g_i) * gamma_{k,i}
 static __device__ __noinline__ void coop_frob(int dst, int a, int k) {
   int tid = threadIdx.x;
@@ -181,12 +157,11 @@ static __device__ __noinline__ void coop_frob(int dst, int a, int k) {
     Fq29 x = g_sh.r[a].v[2 * i], y = g_sh.r[a].v[2 * i + 1];
     if (k & 1) y = fq29_neg(y);
     if (i == 0) {
-      out = e ? y : x;
+      out = fq29_norm(e ? y : x);
     } else {
       Fq2_29 g = frob29_gamma(k, i);
-      out = fq2_scale_lane(x, y, g.c0, g.c1, e);
+      out = fq2_scale_norm(x, y, g.c0, g.c1, e);
     }
-    out = fq29_norm(out);
   }
   __syncthreads();  // all reads of a done before dst (possibly == a) is written
   if (tid < 12) coop_store(dst, tid, out);
@@ -199,7 +174,7 @@ static __device__ __noinline__ void coop_scale(int dst, int a) {
   Fq29 out = fq29_zero();
   if (tid < 12) {
     int i = tid >> 1, e = tid & 1;
-    out = fq29_norm(fq2_scale_lane(g_sh.r[a].v[2 * i], g_sh.r[a].v[2 * i + 1], g_sh.scal[0], g_sh.scal[1], e));
+    out = fq2_scale_norm(g_sh.r[a].v[2 * i], g_sh.r[a].v[2 * i + 1], g_sh.scal[0], g_sh.scal[1], e);
   }
   __syncthreads();
   if (tid < 12) coop_store(dst, tid, out);

@@ -349,14 +349,16 @@ SNARKV_HD void fq29_to_words(const Fq29& a, uint32_t w[8], bool mont) {
 }
 SNARKV_HD void fq29_to_canonical(const Fq29& a, uint32_t w[8]) { fq29_to_words(a, w, false); }
 
-// x - round(x/p) p for |x| up to ~64p, x carry-normalised: the quotient is
-// estimated from the top limb (bits 232..), exact to +-1, so |result| < 1.5p.
+// x - round(x/p) p for |x| < 64p, x carry-normalised: the quotient is estimated
+// from the top limb (bits 232..), off by less than 4e-5 of a unit, so
+// |result| <= (1/2 + 2^-13) p (seen over +-64p: 0.50001 p).
 // Result carry-normalised.  (Cheap modular squeeze after a lazy sum of many
 // products; one float multiply, nine 64-bit mads.)
 SNARKV_HD Fq29 fq29_reduce_small(const Fq29& x) {
   const float inv_ptop = 1.0f / (float)fq29_p(8);  // p >> 232
-  float qf = (float)x.v[8] * inv_ptop;
-  int32_t q = (int32_t)(qf + (qf >= 0 ? 0.5f : -0.5f));
+  // ONE rounding, spelled as the fused multiply-add the device compiler made of `qf + 0.5f` anyway: left to contraction,
+  // the host build rounded the product first and picked the other quotient next to a half-integer
+  const int32_t q = (int32_t)__builtin_fmaf((float)x.v[8], inv_ptop, x.v[8] >= 0 ? 0.5f : -0.5f);
   Fq29 r;
   int64_t c = 0;
 #pragma unroll
@@ -369,7 +371,8 @@ SNARKV_HD Fq29 fq29_reduce_small(const Fq29& x) {
   return r;
 }
 
-// carry-normalised k*x for a small constant k (|k| < 2^20), x carry-normalised
+// carry-normalised k*x for a small constant k (|k| < 2^20), x carry-normalised; limb 8 of the result must fit int32:
+// |k| (|x| / 2^232 + 1) < 2^31, i.e. |k x| below about 600 p
 SNARKV_HD Fq29 fq29_mul_small_norm(const Fq29& x, int32_t k) {
   Fq29 r;
   int64_t c = 0;

@@ -20,7 +20,10 @@ struct Fq2_29P {  // one LDS slot: an Fq2 value, components carry-normalised (8-
 SNARKV_HD Fq29 g2w_get(const Fq2_29P* sl, int slot, int e) { return wt_load(sl[slot].c, e); }
 SNARKV_HD void g2w_put(Fq2_29P* sl, int slot, int e, const Fq29& x) { wt_store(sl[slot].c, e, x); }
 
-// sgn * sum_k coeff_k * slot_k (component e), carry-normalised; coefficients in -3 .. 3, values within ~1.5 p: the sum within ~9 p
+// sgn * sum_k coeff_k * slot_k (component e), carry-normalised; coefficients in -3 .. 3.  Over the 448 levels of
+// g2_prepare_prog.inc the largest |sum| is 3.04 p (interval arithmetic in tests/test_curve_math_lazy_host.py, which also
+// bounds the line values handed to fq29_canon_of_product to (-0.036 p, 1.024 p)); g2w_product is tested up to 3.25 p,
+// where its output stays inside (-0.08 p, 1.07 p).  A regenerated program must stay below 3.25 p or move that bound.
 SNARKV_HD Fq29 g2w_comb(const Fq2_29P* sl, const int8_t s[3], const int8_t c[3], int e, int32_t sgn) {
   Fq29 r = fq29_zero();
 #pragma unroll

@@ -6,11 +6,17 @@
 // writing a carry and the VALU consuming it -- the cheap-looking additions cost
 // as much as the products.  In the lazy form a sum is nine independent
 // `v_add_u32`, and one float-estimated quotient (`fq29_reduce_small`) squeezes
-// the up-to-22-term coefficient back below 1.5p.
+// the up-to-22-term coefficient back to within (1/2 + 2^-13) p.
 //
-// Invariant of a coefficient c held in LDS: carry-normalised, |c| < 1.5p, so both
-// operands of a product stay inside the multiplier budget (|limb| < 2^29) and every
-// fused two-product value inside (-p/16, 17p/16).
+// STORED: the invariant of a coefficient c held in LDS by k_decide: carry-normalised and
+// |c| < 2.05 p (proven).  coop3_finalize leaves |c| <= (1/2 + 2^-13) p (seen: 0.50001 p), but
+// coop_frob / coop_scale store fq2_scale_norm, an UNSQUEEZED sum or difference of two
+// single products, proven inside (-1.025 p, 2.025 p) (seen: -0.993 p .. 1.999 p), and coop_conj
+// negates such a value.  Both operands of a product stay inside the multiplier budget
+// (|limb| < 2^29), and every fused two-product value -- here and in decide_w.h, whose xi
+// copies reach 10.1 p -- inside (-p/8, 9p/8) (seen: -0.070 p .. 1.064 p): the ONE range
+// of a fused two-product output.  tests/fq29_model.py section 4 derives these sets from
+// the producers and checks every piece on raw limbs at their corners.
 #pragma once
 #include "fq29.h"
 
@@ -49,7 +55,7 @@ SNARKV_HD Fq2_29 frob29_gamma(int k, int i) {
 // group (DPP), the partner coefficient of xi V sits 8 lanes away (row_ror:8),
 // and lane j = 0 of each group applies   low + 9 hi_e -/+ hi_(1-e)   in one
 // 64-bit carry chain followed by the float-estimated squeeze.
-// Invariant of a stored coefficient: carry-normalised, |c| < 1.5p.
+// Invariant of a stored coefficient: STORED above.
 struct Coop3Lane {
   int k, e, i1, i2;
   bool active, high;
@@ -85,7 +91,8 @@ SNARKV_HD Fq29 coop3_product(int e, const Fq29& a0, const Fq29& a1, const Fq29& 
 // lo, hi, hp: limb-wise sums of <= 6 carry-normalised products (limbs 0..7
 // read as UNSIGNED: up to 6 * 2^29; limb 8 signed); hp = the high sum of the
 // other u-power.  Returns low + 9 hi - hp (e = 0) or low + 9 hi + hp (e = 1),
-// carry-normalised and squeezed below 1.5p.
+// carry-normalised and squeezed to within (1/2 + 2^-13) p (seen: 0.50001 p).  With k + 1 low
+// and 5 - k high terms in (-p/8, 9p/8) the sum lies in (-11.4 p, 57.4 p) (proven; seen: -11.375 p .. 57.375 p).
 SNARKV_HD Fq29 coop3_finalize(int e, const Fq29& lo, const Fq29& hi, const Fq29& hp) {
   Fq29 t;
   int64_t c = 0;
@@ -104,5 +111,36 @@ SNARKV_HD Fq29 coop3_finalize(int e, const Fq29& lo, const Fq29& hi, const Fq29&
   }
   return fq29_reduce_small(t);
 }
+
+// (x + y u)(g0 + g1 u) = (x g0 - y g1) + (x g1 + y g0) u, component e; every product N, so the lazy sum stays < 2^30
+SNARKV_HD Fq29 fq2_scale_lane(const Fq29& x, const Fq29& y, const Fq29& g0, const Fq29& g1, int e) {
+  return e ? fq29_add(fq29_mul(x, g1), fq29_mul(y, g0)) : fq29_sub(fq29_mul(x, g0), fq29_mul(y, g1));
+}
+// what coop_frob and coop_scale (decider.hip) store: the carry-normalised sum or difference of two single products, each
+// in a b / 2^261 + [0, p).  NOT squeezed: the sum (e = 1) reaches 2 p, the difference (e = 0) -p, see STORED above.
+SNARKV_HD Fq29 fq2_scale_norm(const Fq29& x, const Fq29& y, const Fq29& g0, const Fq29& g1, int e) {
+  return fq29_norm(fq2_scale_lane(x, y, g0, g1, e));
+}
+
+#if defined(__HIPCC__)
+// ---- device only: the lane exchanges of the rounds (decider.hip; tests/devtest/devtest.hip runs the same text) ----------
+// DPP lane exchange inside a 16-lane row (no LDS, no barrier)
+template <int CTRL>
+static __device__ __forceinline__ uint32_t dpp_u32(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, true);
+}
+
+// every lane of an aligned 8-lane group gets the limb-wise sum over the group
+// (limbs as unsigned: <= 6 live terms of < 2^29 each)
+static __device__ __forceinline__ Fq29 group8_sum(Fq29 x) {
+#pragma unroll
+  for (int i = 0; i < 9; ++i) x.v[i] = (int32_t)((uint32_t)x.v[i] + dpp_u32<0xB1>((uint32_t)x.v[i]));   // quad_perm [1,0,3,2]
+#pragma unroll
+  for (int i = 0; i < 9; ++i) x.v[i] = (int32_t)((uint32_t)x.v[i] + dpp_u32<0x4E>((uint32_t)x.v[i]));   // quad_perm [2,3,0,1]
+#pragma unroll
+  for (int i = 0; i < 9; ++i) x.v[i] = (int32_t)((uint32_t)x.v[i] + dpp_u32<0x141>((uint32_t)x.v[i]));  // row_half_mirror
+  return x;
+}
+#endif
 
 }  // namespace snarkv

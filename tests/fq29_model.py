@@ -1168,6 +1168,752 @@ def chain_suite(C, run, npts=256, model_long=8):
     return count
 
 
+# ---------------------------------------------------------------- section 4: the pairing decider's lane arithmetic (BN254)
+# The pieces of csrc/pairing_coop29.h, decide_w.h, g2_prepare_w.h and the two squeezes of fq29.h / decide_w.h as raw
+# records (tests/hosttest/curve_ops.h SNARKV_RAW_DECIDER_OPS), over the operand sets their PRODUCERS can emit.
+#
+# The sets, in units of p (rho = p / 2^261 = 1 / 169.3 for BN254; "product" = a b / 2^261 + [0, p)):
+#   SQUEEZED  what wt_squeeze / fq29_reduce_small (coop3_finalize) leave.  The quotient is round(v8 / p8) of the top limbs
+#             (p8 = p >> 232 = 2^21.6) in ONE rounding (a fused multiply-add).  x / p - v8 / p8 = L / p - (v8 / p8)(Lp / p)
+#             with L < 7 * 2^232 the lower limbs of a six-term sum and Lp < 2^232 those of p: below 71 * 2^-21.6 = 2.3e-5
+#             for |x| <= 64 p; the float path adds |q| 2^-23 + half an ulp of 64 = 1.2e-5.  So |result| <= (1/2 + 2^-13) p.
+#   PLAIN_W   a plain value of the program form (k_decide_w): SQUEEZED, the single products of wt_eval_line and wt_fq2inv
+#             (a value within 1.01 p times a canonical one: (-0.006 p, 1.006 p); seen for wt_fq2inv: 1.0031 p), the
+#             negated product of wt_fq2inv ((-1.006 p, 0.006 p)), canonical constants
+#             and key coefficients: inside (-1.01 p, 1.01 p), carry-normalised.
+#   XI_W      wt_xi of two PLAIN_W values: 9 own -/+ other, inside (-10.1 p, 10.1 p), carry-normalised.
+#   STORED    a coefficient of k_decide's registers: SQUEEZED (coop3_finalize), the canonical start values, and what
+#             coop_frob / coop_scale / coop_conj store WITHOUT a squeeze: fq2_scale_norm is a sum (e = 1) or difference
+#             (e = 0) of two single products of a STORED value by a value within 1.01 p, i.e. inside
+#             (-2.05 / 169.3 - 1, 2 + 2 * 2.05 / 169.3) = (-1.025 p, 2.025 p), and coop_conj negates that: inside
+#             (-2.05 p, 2.05 p), carry-normalised: the proven set (seen: -0.993 p .. 1.999 p).  (The headers used to say 1.5 p.)
+#   PRODUCT   the fused two-product step over any of these: k_decide multiplies STORED by STORED
+#             (2 * 2.05^2 / 169.3 = 0.050), k_decide_w PLAIN_W by PLAIN_W or XI_W (2 * 1.01 * 10.1 / 169.3 = 0.1205): inside
+#             (-p/8, 9p/8), carry-normalised.  Six of them sum to (-0.75 p, 6.75 p); low + 9 high +- high' of k + 1 and
+#             5 - k of them to (-11.4 p, 57.4 p) (-91/8 and 459/8 at k = 0; both ends are among the records): inside the +-64 p of the squeeze, top limb far inside int32.
+from fractions import Fraction
+
+DECIDER_OPS = {
+    "fq29_reduce_small": (9, 9), "fq29_mul_small_norm": (10, 9), "wt_squeeze": (9, 9), "wt_xi_e0": (18, 9), "wt_xi_e1": (18, 9),
+    "wt_cneg": (10, 9), "coop3_product_e0": (36, 9), "coop3_product_e1": (36, 9), "coop3_finalize_e0": (27, 9),
+    "coop3_finalize_e1": (27, 9), "g2w_product_e0": (36, 18), "g2w_product_e1": (36, 18), "fq2_scale_norm_e0": (36, 9),
+    "fq2_scale_norm_e1": (36, 9), "wt_fq2inv": (18, 18),
+}
+ROUND_OPS = {"wt_round": (48 * 9 + 2, 24 * 9), "coop3_round": (24 * 9 + 1, 12 * 9)}
+ALL_OPS = dict(OPS, **DECIDER_OPS, **ROUND_OPS)
+FLOAT_QUOTIENT_OPS = ("fq29_reduce_small", "wt_squeeze", "coop3_finalize_e0", "coop3_finalize_e1")
+
+SQUEEZED = Fraction(1, 2) + Fraction(1, 1 << 13)
+PLAIN_W = Fraction(101, 100)
+XI_W = 10 * PLAIN_W
+STORED = Fraction(205, 100)
+PROD_LO, PROD_HI = Fraction(-1, 8), Fraction(9, 8)
+REDUCE_DOMAIN = 64
+# the largest |g2w_comb| that interval arithmetic over g2_prepare_prog.inc proves (test_g2_prepare_program_stays_inside_its
+# contracts asserts it), rounded up; g2w_product is tested over operands up to it
+G2W_COMB_MAX = Fraction(13, 4)
+TOP = 1 << 232
+
+
+def _fr(F, fr):
+    """floor(fr * p) as an integer"""
+    return (fr.numerator * F.q) // fr.denominator
+
+
+def residue_classes(F, rnd, n_random):
+    q = F.q
+    p8 = q >> 232
+    edge = [0, 1, 2, q - 1, q - 2, (q - 1) // 2, (q + 1) // 2, TOP - 1, TOP, p8 << 232, ((p8 - 1) << 232) | (TOP - 1), F.one]
+    return edge + [rnd.randrange(q) for _ in range(n_random)]
+
+
+def reps(F, res, lo, hi):
+    """the smallest and the largest integer of the residue strictly inside (lo, hi), and the canonical one if it is inside"""
+    q = F.q
+    a = lo + 1 + ((res - lo - 1) % q)
+    b = hi - 1 - ((hi - 1 - res) % q)
+    return [v for v in (a, b, res) if lo < v < hi]
+
+
+def value_pool(F, seed, n, lo, hi):
+    """n integers strictly inside (lo, hi): every residue class at both ends of the interval and canonical, the ends
+    themselves, values whose limbs 0..7 are all ones / all zero at both ends, then seeded random ones"""
+    key = (F.q, "vpool", seed, n, lo, hi)
+    if key in _CACHE:
+        return _CACHE[key]
+    rnd = random.Random(seed)
+    out = [lo + 1, hi - 1]
+    for low in (TOP - 1, 0, (TOP - 1) // 3):
+        out += [((lo - low) // TOP + 1) * TOP + low, ((hi - low - 1) // TOP) * TOP + low]
+    for r in residue_classes(F, rnd, 12):
+        out += reps(F, r, lo, hi)
+    out = [v for v in out if lo < v < hi]
+    while len(out) < n:
+        out.append(rnd.randrange(lo + 1, hi))
+    rnd.shuffle(out)
+    assert all(lo < v < hi for v in out)
+    _CACHE[key] = out[:n]
+    return _CACHE[key]
+
+
+def _sym(F, fr):
+    b = _fr(F, fr)
+    return -b, b
+
+
+def _limb_rows(values):
+    return np.array([spell(v) for v in values], dtype=np.int64).astype(np.int32)
+
+
+def vals_u(a):
+    """(n, 9) int32 -> integers with limbs 0..7 read as UNSIGNED 32-bit words (a limb-wise sum of up to six), limb 8 signed"""
+    a = np.asarray(a)
+    out = a[:, 8].astype(object) << 232
+    for i in range(8):
+        out = out + ((a[:, i].astype(np.int64) & 0xFFFFFFFF).astype(object) << (29 * i))
+    return out
+
+
+def float_quotient(F, top):
+    """the quotient estimate of fq29_reduce_small / wt_squeeze: trunc(fma((float) v8, 1.0f / (float) p8, +-0.5f)), bit for
+    bit.  The product of two floats is exact in a double and so is its sum with 0.5 once |product| >= 2^-6 (below that the
+    result truncates to 0 whatever the rounding), so rounding the double once to float IS the fused operation."""
+    top = np.asarray(top, dtype=np.int32)
+    inv = np.float32(1.0) / np.float32(F.limbs[8])
+    t = top.astype(np.float32).astype(np.float64) * np.float64(inv) + np.where(top >= 0, 0.5, -0.5)
+    return t.astype(np.float32).astype(np.int64)
+
+
+def m_squeeze(F, values, tops):
+    """value - q p with the float quotient of the top limb, carry-normalised (limb 8 must fit int32)"""
+    return np.array([spell(int(v) - int(k) * F.q) for v, k in zip(values, float_quotient(F, tops))], dtype=np.int64).astype(np.int32)
+
+
+def _sum_limbs(terms):
+    """the limb-wise sum group8_sum leaves: limbs 0..7 below 6 * 2^29 as 32-bit words (int32 view), limb 8 signed"""
+    s = [0] * 9
+    for t in terms:
+        for i, x in enumerate(spell(t)):
+            s[i] += x
+    assert all(0 <= x < 1 << 32 for x in s[:8])
+    return [x - (1 << 32) if i < 8 and x >= I32 else x for i, x in enumerate(s)]
+
+
+def _split(rnd, total, n, lo, hi):
+    """n integers strictly inside (lo, hi) that sum to `total`, or None"""
+    if not n * lo + n <= total <= n * hi - n:
+        return None
+    for _ in range(20):
+        base = total // n
+        room = min(base - lo, hi - base) // 2
+        t = [base + (rnd.randrange(-room, room + 1) if room > 0 else 0) for _ in range(n - 1)]
+        t.append(total - sum(t))
+        if all(lo < v < hi for v in t):
+            return t
+    t = [total // n] * (n - 1)
+    t.append(total - sum(t))
+    return t if all(lo < v < hi for v in t) else None
+
+
+_HALF_DELTAS = [0, 1, -1, TOP >> 1, -(TOP >> 1), TOP, -TOP, 3 * TOP, -3 * TOP, 7 * TOP, -7 * TOP, 8 * TOP, -8 * TOP]
+
+
+def _term_extremes(F):
+    lo, hi = _fr(F, PROD_LO), _fr(F, PROD_HI) + 1
+    ext = [lo + 1, hi - 1]
+    for low in (TOP - 1, 0):
+        ext += [((lo - low) // TOP + 1) * TOP + low, ((hi - low - 1) // TOP) * TOP + low]
+    return lo, hi, ext
+
+
+def squeeze_cases(F, n):
+    """limb-wise sums of 1..6 fused-product outputs for wt_squeeze -> (rows, term lists)"""
+    rnd = random.Random(7001)
+    q = F.q
+    lo, hi, ext = _term_extremes(F)
+    pool = value_pool(F, 7002, 4000, lo, hi)
+    sums = []
+    for nt in range(1, 7):  # the corners: every term at the same extreme, and the extremes alternating
+        for e in ext:
+            sums.append([e] * nt)
+        for e in ext:
+            for f in ext:
+                sums.append([e if i % 2 == 0 else f for i in range(nt)])
+    for res in residue_classes(F, rnd, 40):  # every residue class with the other terms at an extreme
+        for nt in range(1, 7):
+            for e in ext:
+                r = (res - (nt - 1) * e) % q
+                for last in (r, r + q, r - q):
+                    if lo < last < hi:
+                        sums.append([e] * (nt - 1) + [last])
+    for k in range(-1, 7):  # totals next to (k + 1/2) p, on both sides
+        for d in _HALF_DELTAS + [q >> 18, -(q >> 18), q >> 21, -(q >> 21)]:
+            total = ((2 * k + 1) * q) // 2 + d
+            for nt in range(1, 7):
+                for _ in range(3):
+                    t = _split(rnd, total, nt, lo, hi)
+                    if t:
+                        sums.append(t)
+    while len(sums) < n:
+        nt = rnd.randrange(1, 7)
+        sums.append([rnd.choice(pool) if rnd.random() < 0.7 else rnd.choice(ext) for _ in range(nt)])
+    rows = np.array([_sum_limbs(t) for t in sums], dtype=np.int64).astype(np.int32)
+    assert (rows[:, :8] < 0).any(), "no limb reached 2^31: the unsigned reading is not exercised"
+    assert rows[:, :8].astype(np.int64).__and__(0xFFFFFFFF).max() >= 6 * MASK - 8
+    assert rows[:, 8].min() < 0 and rows[:, 8].max() >= 6 * ((hi - 1) >> 232) - 1
+    return rows
+
+
+def finalize_cases(F, n, e):
+    """(lo, hi, hp) for coop3_finalize: sums of k + 1, 5 - k and 5 - k fused-product outputs, k = 0..5"""
+    rnd = random.Random(7100 + e)
+    q = F.q
+    lo, hi, ext = _term_extremes(F)
+    pool = value_pool(F, 7002, 4000, lo, hi)
+    recs = []
+    sg = 1 if e else -1
+    for k in range(6):
+        nl, nh = k + 1, 5 - k
+        for a in ext:  # every combination of extremes: this holds the maximum and the minimum of lo + 9 hi +- hp
+            for b in ext:
+                for c in ext:
+                    recs.append(([a] * nl, [b] * nh, [c] * nh))
+        for res in residue_classes(F, rnd, 12):  # every residue class at both ends
+            for b, c in ((ext[1], ext[1] if e else ext[0]), (ext[0], ext[0] if e else ext[1]), (ext[3], ext[2]), (ext[5], ext[4])):
+                for a in (ext[0], ext[1]):
+                    r = (res - (nl - 1) * a - 9 * nh * b - sg * nh * c) % q
+                    for last in (r, r + q, r - q):
+                        if lo < last < hi:
+                            recs.append(([a] * (nl - 1) + [last], [b] * nh, [c] * nh))
+        for d in _HALF_DELTAS + [q >> 18, -(q >> 18)]:  # lo + 9 hi +- hp next to a half-integer multiple of p
+            for _ in range(12):
+                th = [rnd.choice(pool) if rnd.random() < 0.6 else rnd.choice(ext) for _ in range(nh)]
+                tp = [rnd.choice(pool) if rnd.random() < 0.6 else rnd.choice(ext) for _ in range(nh)]
+                base = 9 * sum(th) + sg * sum(tp)
+                # integers m with  (m + 1/2) p + d - base  a feasible sum of nl terms
+                mlo = -((-(2 * (base + nl * lo - d) + q)) // (2 * q)) + 1
+                mhi = (2 * (base + nl * hi - d) - q) // (2 * q) - 1
+                if mlo > mhi:
+                    continue
+                m = rnd.randrange(mlo, mhi + 1)
+                tl = _split(rnd, ((2 * m + 1) * q) // 2 + d - base, nl, lo, hi)
+                if tl:
+                    recs.append((tl, th, tp))
+    while len(recs) < n:
+        k = rnd.randrange(6)
+        pick = lambda m: [rnd.choice(pool) if rnd.random() < 0.7 else rnd.choice(ext) for _ in range(m)]  # noqa: E731
+        recs.append((pick(k + 1), pick(5 - k), pick(5 - k)))
+    rows = np.array([_sum_limbs(a) + _sum_limbs(b) + _sum_limbs(c) for a, b, c in recs], dtype=np.int64).astype(np.int32)
+    top = (hi - 1) >> 232
+    for j, nt in ((0, 6), (1, 5), (2, 5)):  # the low block sums up to six terms, the two high blocks up to five
+        blk = rows[:, 9 * j:9 * j + 9]
+        assert (blk[:, :8] < 0).any(), "block %d: no limb reached 2^31: the unsigned reading is not exercised" % j
+        assert blk[:, :8].astype(np.int64).__and__(0xFFFFFFFF).max() >= nt * MASK - 8, j
+        assert blk[:, 8].min() < 0 and blk[:, 8].max() >= nt * top - 1, j
+    return rows
+
+
+def reduce_small_cases(F, n):
+    """carry-normalised x inside (-64 p, 64 p): every residue class at every multiple of p, and top limbs next to
+    (k + 1/2) p8 with the lower limbs all zero, all ones and random"""
+    rnd = random.Random(7200)
+    q = F.q
+    p8 = q >> 232
+    vs = []
+    res = residue_classes(F, rnd, 8)
+    for r in res:
+        for k in range(-REDUCE_DOMAIN, REDUCE_DOMAIN):
+            vs.append(r + k * q)
+    for k in range(-REDUCE_DOMAIN, REDUCE_DOMAIN - 1):
+        half = ((2 * k + 1) * q) // 2
+        for d in _HALF_DELTAS + [q >> 18, -(q >> 18)]:
+            vs.append(half + d)
+        t8 = ((2 * k + 1) * p8) // 2
+        for d8 in range(-3, 4):
+            for low in (0, TOP - 1, rnd.randrange(TOP)):
+                vs.append(((t8 + d8) << 232) + low)
+    vs = [v for v in vs if -REDUCE_DOMAIN * q < v < REDUCE_DOMAIN * q]
+    while len(vs) < n:
+        vs.append(rnd.randrange(-REDUCE_DOMAIN * q + 1, REDUCE_DOMAIN * q))
+    return _limb_rows(vs)
+
+
+def _pick(rnd, *pools):
+    return rnd.choice(rnd.choice(pools))
+
+
+def decider_cases(F, n=20000):
+    """op -> (>= n, words in) int32 records, every one inside the domain its producers can emit (asserted)"""
+    key = (F.q, "decider", n)
+    if key in _CACHE:
+        return _CACHE[key]
+    rnd = random.Random(7300)
+    q = F.q
+    cases = {}
+    plain = value_pool(F, 7301, n, *_sym(F, PLAIN_W))
+    plain2 = value_pool(F, 7302, n, *_sym(F, PLAIN_W))
+    xi = value_pool(F, 7303, n, *_sym(F, XI_W))
+    xi2 = value_pool(F, 7304, n, *_sym(F, XI_W))
+    st = [value_pool(F, 7310 + i, n, *_sym(F, STORED)) for i in range(4)]
+    canon = value_pool(F, 7320, n, -1, q)
+    canon2 = value_pool(F, 7321, n, -1, q)
+    comb = [value_pool(F, 7330 + i, n, *_sym(F, G2W_COMB_MAX)) for i in range(4)]
+    cases["fq29_reduce_small"] = reduce_small_cases(F, n)
+    cases["wt_squeeze"] = squeeze_cases(F, n)
+    cases["coop3_finalize_e0"] = finalize_cases(F, n, 0)
+    cases["coop3_finalize_e1"] = finalize_cases(F, n, 1)
+    two = np.concatenate([_limb_rows(plain), _limb_rows(plain2)], axis=1)
+    cases["wt_xi_e0"] = two
+    cases["wt_xi_e1"] = two
+    m = np.array([[0 if i % 2 else -1] for i in range(n)], dtype=np.int32)
+    cn = _limb_rows(plain)
+    lazy = _pool(F, 3, n, "lazy")  # any |limb| <= 2^29 works limb-wise
+    cases["wt_cneg"] = np.concatenate([np.concatenate([cn[:n // 2], lazy[n // 2:n]]), m], axis=1)
+    # fused products: STORED x STORED (k_decide), PLAIN_W x (PLAIN_W | XI_W) (k_decide_w)
+    h = n // 2
+    a0 = _limb_rows(st[0][:h] + plain[h:])
+    a1 = _limb_rows(st[1][:h] + plain2[h:])
+    y0 = _limb_rows(st[2][:h] + xi[h:])
+    y1 = _limb_rows(st[3][:h] + xi2[h:])
+    cases["coop3_product_e0"] = np.concatenate([a0, a1, y0, y1], axis=1)
+    cases["coop3_product_e1"] = cases["coop3_product_e0"]
+    g = np.concatenate([_limb_rows(c) for c in comb], axis=1)
+    cases["g2w_product_e0"] = g
+    cases["g2w_product_e1"] = g
+    # coop_frob: (stored, stored, gamma, gamma), gamma canonical, and for odd k the y it passes is fq29_neg of the stored
+    # one, NOT normalised (limbs in (-2^29, 0], top limb negated): every fourth record, across both kinds of g1; coop_scale: the scalar 1 / d of coop_inv: scal[0] a single
+    # product of a squeezed value by a canonical one, scal[1] the limb-wise negation of one (limbs <= 0)
+    s0 = value_pool(F, 7340, n, -q // 128, q + q // 128)
+    s1 = np.concatenate([_limb_rows(canon2[:h]), -_limb_rows(value_pool(F, 7341, n, -q // 128, q + q // 128)[h:])])
+    g0 = _limb_rows(canon[:h] + s0[h:])
+    y = _limb_rows(st[1])
+    y[1::4] = -y[1::4]
+    assert (y[1::4, :8] <= 0).all() and (y[1::4, :8] < 0).any() and (np.abs(y.astype(np.int64)) < (1 << 29)).all()
+    cases["fq2_scale_norm_e0"] = np.concatenate([_limb_rows(st[0]), y, g0, s1], axis=1)
+    cases["fq2_scale_norm_e1"] = cases["fq2_scale_norm_e0"]
+    # wt_fq2inv: d = coefficient 0 of a register a round wrote (SQUEEZED; tested over all of PLAIN_W), d = 0 included
+    d = np.concatenate([_limb_rows(plain2), _limb_rows(plain)], axis=1)
+    d[0] = 0
+    cases["wt_fq2inv"] = d
+    # k x: limb 8 of the result must fit int32, i.e. |k| (|x| / 2^232 + 1) < 2^31
+    wide = value_pool(F, 7350, n, -8 * q, 8 * q)
+    rows = []
+    for i in range(n):
+        v = wide[i] if i % 3 else plain[i]
+        if i % 7 == 0:
+            v = rnd.choice([0, 1, -1, TOP - 1, -TOP])
+        kmax = min((1 << 20) - 1, (I32 - 1) // ((abs(v) >> 232) + 2))
+        k = rnd.choice([kmax, -kmax, 1, -1, 0, 9, -9, rnd.randrange(-kmax, kmax + 1)])
+        rows.append(spell(v) + [k])
+    cases["fq29_mul_small_norm"] = np.array(rows, dtype=np.int64).astype(np.int32)
+    for name, arr in cases.items():
+        assert arr.shape[1] == DECIDER_OPS[name][0] and len(arr) >= n, name
+    _CACHE[key] = cases
+    return cases
+
+
+def _span(mx, name, values, q):
+    lo, hi = min(values), max(values)
+    old = mx.get(name, (0.0, 0.0))
+    mx[name] = (min(old[0], float(Fraction(int(lo), q))), max(old[1], float(Fraction(int(hi), q))))
+
+
+def _assert_norm(out, what):
+    out = np.asarray(out)
+    assert ((out[:, :8] >= 0) & (out[:, :8] <= MASK)).all(), what + ": a limb 0..7 outside [0, 2^29)"
+
+
+def _assert_within(values, lo, hi, q, what):
+    bad = [i for i, v in enumerate(values) if not lo <= v <= hi]
+    assert not bad, "%s: %d values outside [%.4f p, %.4f p], first at %d: %.6f p" % (
+        what, len(bad), lo / q, hi / q, bad[0], values[bad[0]] / q)
+
+
+def decider_suite(F, run, n=20000):
+    """Every decider piece over `decider_cases` through `run(op, in) -> out`; each record against exact integers: residue,
+    limbs 0..7 in [0, 2^29), the set the consumers rely on, and (where the model fixes them) the nine limbs.
+    Returns ({op: records checked}, {bound name: (smallest, largest value / p seen)})."""
+    q = F.q
+    cases = decider_cases(F, n)
+    outs = {name: np.asarray(run(name, inp)) for name, inp in cases.items()}
+    checked, mx = {}, {}
+    sq = _fr(F, SQUEEZED)
+    # ---- the two float-quotient squeezes and the finalisation built on one
+    inp = cases["fq29_reduce_small"]
+    assert ((inp[:, :8] >= 0) & (inp[:, :8] <= MASK)).all()
+    x = vals(inp)
+    for name, x, top in (("fq29_reduce_small", x, inp[:, 8]), ("wt_squeeze", vals_u(cases["wt_squeeze"]), cases["wt_squeeze"][:, 8])):
+        o = outs[name]
+        _assert_norm(o, name)
+        v = vals(o)
+        assert all((a - b) % q == 0 for a, b in zip(v, x)), name + ": residue changed"
+        _assert_within(v, -sq, sq, q, name)
+        checked[name] = _eq(o, m_squeeze(F, x, top), name + " against the model's quotient")
+        _span(mx, name, v, q)
+    for e in (0, 1):
+        name = "coop3_finalize_e%d" % e
+        inp = cases[name]
+        lo, hi, hp = vals_u(inp[:, :9]), vals_u(inp[:, 9:18]), vals_u(inp[:, 18:])
+        t = lo + 9 * hi + (hp if e else -hp)
+        assert all(-REDUCE_DOMAIN * q < v < REDUCE_DOMAIN * q for v in t)
+        _span(mx, "coop3_finalize input", t, q)
+        o = outs[name]
+        _assert_norm(o, name)
+        v = vals(o)
+        assert all((a - b) % q == 0 for a, b in zip(v, t)), name + ": residue is not lo + 9 hi +- hp"
+        _assert_within(v, -sq, sq, q, name)
+        tops = np.array([spell(int(z))[8] for z in t], dtype=np.int64).astype(np.int32)
+        checked[name] = _eq(o, m_squeeze(F, t, tops), name + " against the model's quotient")
+        _span(mx, "coop3_finalize", v, q)
+    # ---- xi copies: the exact integer 9 own -/+ other, inside the bound the products need
+    xb = _fr(F, XI_W)
+    for e in (0, 1):
+        name = "wt_xi_e%d" % e
+        inp = cases[name]
+        own, other = vals(inp[:, :9]), vals(inp[:, 9:])
+        want = 9 * own + (other if e else -other)
+        o = outs[name]
+        _assert_norm(o, name)
+        assert (vals(o) == want).all(), name + ": not the integer 9 own %s other" % ("+" if e else "-")
+        _assert_within(want, -xb, xb, q, name)
+        checked[name] = len(o)
+        _span(mx, "wt_xi", want, q)
+    inp = cases["wt_cneg"]
+    want = np.where(inp[:, 9:10] != 0, -inp[:, :9], inp[:, :9])
+    checked["wt_cneg"] = _eq(outs["wt_cneg"], want, "wt_cneg")
+    # ---- fused two-product steps
+    plo, phi = _fr(F, PROD_LO), _fr(F, PROD_HI)
+    for e in (0, 1):
+        name = "coop3_product_e%d" % e
+        inp = cases[name]
+        assert (np.abs(inp.astype(np.int64)) < (1 << 29)).all()
+        a0, a1, y0, y1 = (vals(inp[:, 9 * j:9 * j + 9]) for j in range(4))
+        t = a0 * y0 + (a1 * y1 if e else -(a1 * y1))
+        checked[name] = check_product(F, outs[name], t, name)
+        exp = np.array([spell((z + ((z * F.nqinv) % F.R) * q) >> RBITS) for z in t], dtype=np.int64).astype(np.int32)
+        _eq(outs[name], exp, name + " against the closed form")
+        v = vals(outs[name])
+        _assert_within(v, plo + 1, phi, q, name)
+        _span(mx, "fused product", v, q)
+        name = "g2w_product_e%d" % e
+        inp = cases[name]
+        am, bm, ap, bp = (vals(inp[:, 9 * j:9 * j + 9]) for j in range(4))
+        t = ap * bm + am * bp if e else am * bm - ap * bp
+        o = outs[name]
+        checked[name] = check_product(F, o[:, :9], t, name)
+        v = vals(o[:, :9])
+        _assert_within(v, -q + 1, 2 * q - 1, q, name + " (the contract of fq29_canon_of_product)")
+        _span(mx, "g2w product", v, q)
+        _eq(o[:, 9:], _canon_expect(F, o[:, :9]), name + ": the line coefficient is not the canonical representative")
+    # ---- what coop_frob / coop_scale store
+    sb = _fr(F, STORED)
+    for e in (0, 1):
+        name = "fq2_scale_norm_e%d" % e
+        inp = cases[name].tolist()
+        exp = []
+        for r in inp:
+            x, y, g0, g1 = r[:9], r[9:18], r[18:27], r[27:]
+            exp.append(l_norm(l_add(m_mul(F, x, g1), m_mul(F, y, g0)) if e else l_sub(m_mul(F, x, g0), m_mul(F, y, g1))))
+        o = outs[name]
+        _assert_norm(o, name)
+        checked[name] = _eq(o, np.array(exp, dtype=np.int64).astype(np.int32), name + " against the model")
+        v = vals(o)
+        x, y, g0, g1 = (vals(cases[name][:, 9 * j:9 * j + 9]) for j in range(4))
+        t = x * g1 + y * g0 if e else x * g0 - y * g1
+        assert all((a * F.R - b) % q == 0 for a, b in zip(v, t)), name + ": residue"
+        _assert_within(v, -sb, sb, q, name + " (the stored-coefficient set)")
+        _span(mx, "fq2_scale_norm", v, q)
+    # ---- WT_FQ2INV's lane: (d0 - d1 u) / (d0^2 + d1^2) in the Montgomery form, both values PLAIN_W
+    inp = cases["wt_fq2inv"]
+    o = outs["wt_fq2inv"]
+    d0, d1 = vals(inp[:, :9]), vals(inp[:, 9:])
+    v0, v1 = vals(o[:, :9]), vals(o[:, 9:])
+    _assert_norm(o[:, :9], "wt_fq2inv")
+    _assert_norm(o[:, 9:], "wt_fq2inv")
+    r2 = F.R * F.R % q
+    for a0, a1, b0, b1 in zip(d0, d1, v0, v1):
+        nn = (a0 * a0 + a1 * a1) % q
+        assert (b0 * nn - a0 * r2) % q == 0 and (b1 * nn + a1 * r2) % q == 0, "wt_fq2inv: not conj(d) / norm(d)"
+        assert nn or (b0 % q == 0 and b1 % q == 0)
+    pw = _fr(F, PLAIN_W)
+    _assert_within(list(v0) + list(v1), -pw, pw, q, "wt_fq2inv (a plain value of the program form)")
+    checked["wt_fq2inv"] = len(o)
+    _span(mx, "wt_fq2inv", list(v0) + list(v1), q)
+    inp = cases["fq29_mul_small_norm"]
+    want = vals(inp[:, :9]) * inp[:, 9].astype(object)
+    o = outs["fq29_mul_small_norm"]
+    _assert_norm(o, "fq29_mul_small_norm")
+    assert (vals(o) == want).all(), "fq29_mul_small_norm: not k x"
+    checked["fq29_mul_small_norm"] = len(o)
+    for name in cases:
+        assert checked[name] == len(cases[name]) >= n, name
+    return checked, mx
+
+
+# ---------------------------------------------------------------- section 4b: whole rounds on raw records
+WT_MUL, WT_PW, WT_FQ2INV = 1, 2, 3
+WT_A_LINE, WT_B_LINE, WT_A_CONJ, WT_B_CONJ, WT_A_UCONJ, WT_B_BCAST = 1, 2, 4, 8, 16, 32
+# every (kind, flags) wt_build_program() emits (the host hook hc_wt_variants lists them; the test compares); WT_FQ2INV is
+# one lane's wt_fq2inv, not a round of the duo: the raw operation wt_fq2inv of section 4 covers it
+WT_VARIANTS = [(WT_MUL, 0), (WT_MUL, WT_A_LINE | WT_B_LINE), (WT_MUL, WT_A_CONJ), (WT_MUL, WT_B_CONJ),
+               (WT_PW, 0), (WT_PW, WT_A_UCONJ), (WT_PW, WT_B_BCAST)]
+_PATTERNS = ("max", "min", "alt_e", "alt_k", "alt_ek", "canon", "rand")
+_POISON = [MASK] * 8 + [0x5A5A5A]  # an operand slot the operation must not read
+
+
+def fq12_operand(F, rnd, bound, pattern):
+    """12 integers strictly inside (-bound, bound), coefficient c = 2 k + e <-> u^e w^k: residues from the corner classes,
+    each at the end of the interval the sign pattern asks for"""
+    res = residue_classes(F, rnd, 6)
+    out = []
+    for c in range(12):
+        r = rnd.choice(res)
+        rp = reps(F, r, -bound, bound)
+        small, large = rp[0], rp[1]
+        k, e = c >> 1, c & 1
+        up = {"max": True, "min": False, "alt_e": e == 0, "alt_k": k % 2 == 0, "alt_ek": (k + e) % 2 == 0,
+              "canon": None, "rand": rnd.random() < 0.5}[pattern]
+        out.append(r if up is None else large if up else small)
+    return out
+
+
+def _fq12_of(coef):
+    O = BN
+    f = [O.Fq2(coef[2 * i], coef[2 * i + 1]) for i in range(6)]
+    return O.Fq12(O.Fq6(f[0], f[2], f[4]), O.Fq6(f[1], f[3], f[5]))
+
+
+def _flat_of(x):
+    c6 = [x.c0.c0, x.c1.c0, x.c0.c1, x.c1.c1, x.c0.c2, x.c1.c2]  # w^0 .. w^5
+    return [v for f in c6 for v in (f.a, f.b)]
+
+
+def _conj_flat(coef):
+    return [-v if (c >> 1) & 1 else v for c, v in enumerate(coef)]
+
+
+def _with_xi(coef):
+    """plain coefficients followed by their xi copies (component e of xi * (c0 + c1 u))"""
+    out = list(coef)
+    for i in range(len(coef) // 2):
+        c0, c1 = coef[2 * i], coef[2 * i + 1]
+        out += [9 * c0 - c1, c0 + 9 * c1]
+    return out
+
+
+def wt_round_cases(F, per_variant=2000):
+    """records of k_wt_round for every variant -> (rows, [(kind, flags, expected 12 residues times 2^261)])"""
+    key = (F.q, "wt_round", per_variant)
+    if key in _CACHE:
+        return _CACHE[key]
+    rnd = random.Random(7400)
+    q = F.q
+    bound = _fr(F, PLAIN_W)
+    rows, meta = [], []
+    for kind, flags in WT_VARIANTS:
+        for i in range(per_variant):
+            pa, pb = _PATTERNS[i % 7], _PATTERNS[(i // 7) % 7]
+            A = fq12_operand(F, rnd, bound, pa)
+            B = A if (i % 11 == 0 and not flags & (WT_A_LINE | WT_B_LINE | WT_B_BCAST)) else fq12_operand(F, rnd, bound, pb)
+            if i % 13 == 0:  # a sparse B
+                B = [v if (c >> 1) in (0, 1, 3) else 0 for c, v in enumerate(B)]
+            la = [0, 1, 2, 3, 6, 7]  # the coefficients of w^0, w^1, w^3
+            if kind == WT_MUL:
+                if flags & WT_A_LINE:
+                    A = [v if c in la else 0 for c, v in enumerate(A)]
+                    areg = [spell(A[c]) for c in la] + [_POISON] * 18
+                else:
+                    areg = [spell(v) for v in _with_xi(A)]
+                if flags & WT_B_LINE:
+                    B = [v if c in la else 0 for c, v in enumerate(B)]
+                    breg = [spell(v) for v in _with_xi([B[c] for c in la])] + [_POISON] * 12
+                else:
+                    breg = [spell(v) for v in _with_xi(B)]
+                ea = _conj_flat(A) if flags & WT_A_CONJ else A
+                eb = _conj_flat(B) if flags & WT_B_CONJ else B
+                exp = _flat_of(_fq12_of(ea) * _fq12_of(eb))
+            else:
+                areg = [spell(v) for v in _with_xi(A)]
+                if flags & WT_B_BCAST:
+                    breg = [spell(B[0]), spell(B[1])] + [_POISON] * 22
+                else:
+                    breg = [spell(v) for v in B] + [_POISON] * 12
+                exp = []
+                for k in range(6):
+                    a = BN.Fq2(A[2 * k], A[2 * k + 1])
+                    if flags & WT_A_UCONJ:
+                        a = a.conj()
+                    if (flags & WT_A_CONJ) and k & 1:
+                        a = -a
+                    j = 0 if flags & WT_B_BCAST else k
+                    r = a * BN.Fq2(B[2 * j], B[2 * j + 1])
+                    exp += [r.a, r.b]
+            rows.append(flat(areg, breg) + [kind, flags])
+            meta.append((kind, flags, exp))
+    out = (np.array(rows, dtype=np.int64).astype(np.int32), meta)
+    _CACHE[key] = out
+    return out
+
+
+def check_wt_round(F, out, meta):
+    """a round's 24 stored values: the product's residues, the stored-coefficient invariant, the exact xi copies"""
+    q = F.q
+    sq = _fr(F, SQUEEZED)
+    out = np.asarray(out)
+    assert out.shape == (len(meta), 24 * 9)
+    _assert_norm(out.reshape(-1, 9), "wt_round")
+    v = vals(out.reshape(-1, 9)).reshape(len(meta), 24)
+    count = {}
+    for i, (kind, flags, exp) in enumerate(meta):
+        row = v[i]
+        for c in range(12):
+            assert (row[c] * F.R - exp[c]) % q == 0, "wt_round record %d (kind %d flags %d): coefficient %d" % (i, kind, flags, c)
+            assert -sq <= row[c] <= sq, "wt_round record %d: coefficient %d at %.5f p" % (i, c, row[c] / q)
+        for k in range(6):
+            c0, c1 = row[2 * k], row[2 * k + 1]
+            assert row[12 + 2 * k] == 9 * c0 - c1 and row[13 + 2 * k] == c0 + 9 * c1, "wt_round record %d: xi copy of w^%d" % (i, k)
+        count[(kind, flags)] = count.get((kind, flags), 0) + 1
+    return count, (float(Fraction(int(v[:, :12].min()), q)), float(Fraction(int(v[:, :12].max()), q)))
+
+
+def coop3_round_cases(F, n=2000):
+    """records of k_coop3_round: dense B, sparse / line-shaped B (mode 1, the unread coefficients poisoned), A == B"""
+    key = (F.q, "coop3_round", n)
+    if key in _CACHE:
+        return _CACHE[key]
+    rnd = random.Random(7500)
+    bound = _fr(F, STORED)
+    rows, meta = [], []
+    for mode in (0, 1):
+        for i in range(n):
+            A = fq12_operand(F, rnd, bound, _PATTERNS[i % 7])
+            B = A if (mode == 0 and i % 11 == 0) else fq12_operand(F, rnd, bound, _PATTERNS[(i // 7) % 7])
+            if mode == 1 or i % 13 == 0:
+                B = [v if (c >> 1) in (0, 1, 3) else 0 for c, v in enumerate(B)]
+            exp = _flat_of(_fq12_of(A) * _fq12_of(B))
+            bl = [spell(v) if (mode == 0 or (c >> 1) in (0, 1, 3)) else _POISON for c, v in enumerate(B)]
+            rows.append(flat([spell(v) for v in A], bl) + [mode])
+            meta.append((mode, 0, exp))
+    out = (np.array(rows, dtype=np.int64).astype(np.int32), meta)
+    _CACHE[key] = out
+    return out
+
+
+def check_coop3_round(F, out, meta):
+    q = F.q
+    sq = _fr(F, SQUEEZED)
+    out = np.asarray(out)
+    assert out.shape == (len(meta), 12 * 9)
+    _assert_norm(out.reshape(-1, 9), "coop3_round")
+    v = vals(out.reshape(-1, 9)).reshape(len(meta), 12)
+    for i, (mode, _, exp) in enumerate(meta):
+        for c in range(12):
+            assert (v[i][c] * F.R - exp[c]) % q == 0, "coop3_round record %d (mode %d): coefficient %d" % (i, mode, c)
+            assert -sq <= v[i][c] <= sq, "coop3_round record %d: coefficient %d at %.5f p" % (i, c, v[i][c] / q)
+    return len(meta), (float(Fraction(int(v.min()), q)), float(Fraction(int(v.max()), q)))
+
+
+# ---------------------------------------------------------------- section 4c: the level program of k_g2_prepare_w
+def g2w_program(lib):
+    """kG2wProg as the host build holds it: (levels, tasks, start slots, [[task dict] per level]); the start slots are
+    the program's own constants (hc_g2w_slot): ([canonical at the start], [zero at the start])"""
+    import ctypes
+
+    levels, tasks, nslots = (lib.hc_g2w_dims(i) for i in range(3))
+    named = [lib.hc_g2w_slot(i) for i in range(12)]  # ONE B3 G12 G13 G22 G23, QX QY, TX TZ TYA, TYB
+    assert lib.hc_g2w_slot(12) == -1 and len(set(named)) == 12 and all(0 <= s < nslots for s in named)
+    slots = (named[:11], named[11:])  # k_g2_prepare_w starts T at (QX, 1, QY) with TYB = 0
+    buf = (ctypes.c_int32 * (16 * levels * tasks))()
+    assert lib.hc_g2w_prog(buf, levels * tasks) == levels * tasks
+    prog = []
+    for lv in range(levels):
+        row = []
+        for t in range(tasks):
+            o = list(buf[16 * (lv * tasks + t):16 * (lv * tasks + t) + 16])
+            row.append({"dst": o[0], "out": o[1], "as": o[2:5], "ac": o[5:8], "bs": o[8:11], "bc": o[11:14], "conj": o[14], "used": o[15]})
+        prog.append(row)
+    return levels, tasks, slots, prog
+
+
+_IV = 1 << 48  # intervals are integers in units of p / 2^48, rounded outward at every product
+
+
+def _imul(a, b):
+    c = [a[0] * b[0], a[0] * b[1], a[1] * b[0], a[1] * b[1]]
+    return min(c), max(c)
+
+
+def g2w_intervals(F, prog, slots):
+    """Intervals in units of p through every level (outward-rounded fixed point).  slots = (the constants, Q and the start
+    state of T: canonical, [0, 1); the slot that starts at zero), from g2w_program; a combination is sum coeff * slot; a fused-product output is (a b + c d) p / 2^261 + [0, 1).
+    Returns (largest |combination|, (smallest, largest) value handed to fq29_canon_of_product, problems found)."""
+    zero, canon = (0, 0), (0, _IV)
+    sl = {s: [canon, canon] for s in slots[0]}
+    sl.update({s: [zero, zero] for s in slots[1]})
+    comb_max, line_lo, line_hi, bad = 0, 0, 0, []
+
+    def comb(ss, cs, e, sgn, where):
+        lo = hi = 0
+        pos = neg = 0
+        for s, c in zip(ss, cs):
+            c *= sgn
+            if c == 0:
+                continue
+            if s not in sl:
+                bad.append("%s reads slot %d before anything wrote it" % (where, s))
+                continue
+            a, b = sl[s][e]
+            lo += min(c * a, c * b)
+            hi += max(c * a, c * b)
+            pos += max(c, 0)
+            neg += max(-c, 0)
+        # fq29_norm of the limb-wise sum: every limb of the sum, plus the carry of the one below, must fit int32
+        if max(pos, neg) * MASK + 8 >= I32:
+            bad.append("%s: a limb of the combination can leave int32" % where)
+        return lo, hi
+
+    def scale(lo, hi):  # (units^2 of p^2) -> units of p: times p / 2^261, floor / ceiling, plus [0, 1)
+        d = _IV * F.R
+        return (lo * F.q) // d, -((-hi * F.q) // d) + _IV
+
+    for lv, row in enumerate(prog):
+        written = {t["dst"] for t in row if t["used"] and t["dst"] >= 0}
+        new = {}
+        for ti, t in enumerate(row):
+            if not t["used"]:
+                continue
+            where = "level %d task %d" % (lv, ti)
+            read = {s for s, c in zip(t["as"] + t["bs"], t["ac"] + t["bc"]) if c}
+            if read & written:
+                bad.append("%s reads slot(s) %s that the same level writes" % (where, sorted(read & written)))
+            A = [comb(t["as"], t["ac"], e, -1 if (t["conj"] and e) else 1, where) for e in (0, 1)]
+            B = [comb(t["bs"], t["bc"], e, 1, where) for e in (0, 1)]
+            for iv in A + B:
+                comb_max = max(comb_max, -iv[0], iv[1])
+            m00, m11, m01, m10 = _imul(A[0], B[0]), _imul(A[1], B[1]), _imul(A[0], B[1]), _imul(A[1], B[0])
+            v0 = scale(m00[0] - m11[1], m00[1] - m11[0])
+            v1 = scale(m01[0] + m10[0], m01[1] + m10[1])
+            if t["dst"] >= 0:
+                new[t["dst"]] = [v0, v1]
+            else:
+                line_lo, line_hi = min(line_lo, v0[0], v1[0]), max(line_hi, v0[1], v1[1])
+        sl.update(new)
+    return Fraction(comb_max, _IV), (Fraction(line_lo, _IV), Fraction(line_hi, _IV)), bad
+
+
+def mul2_column_peak(F, top_units):
+    """the largest column sum of fq29_mul2 over carry-normalised operands (or their limb-wise negations) within
+    top_units * p: limbs 0..7 at 2^29 - 1, limb 8 at the value's own top, plus the reduction products and the carry"""
+    l = [MASK] * 8 + [int(top_units * F.q) >> 232]
+    peak = 0
+    for k in range(17):
+        lo, hi = max(0, k - 8), min(k, 8)
+        s = 2 * sum(l[i] * l[k - i] for i in range(lo, hi + 1))
+        red = MASK * sum(F.limbs[k - i] for i in range(lo, hi + 1))
+        peak = max(peak, s + red + (1 << 35))
+    return peak
+
+
 # ---------------------------------------------------------------- the builds
 def _newest(paths):
     return max(os.path.getmtime(p) for p in paths)
@@ -1175,7 +1921,7 @@ def _newest(paths):
 
 def _csrc_files():
     d = os.path.join(ROOT, "snark-verifier_amd", "csrc")
-    return [os.path.join(d, f) for f in os.listdir(d) if f.endswith((".h", ".inc"))]
+    return [os.path.join(d, f) for f in os.listdir(d) if f.endswith((".h", ".hpp", ".inc"))]
 
 
 def host_lib(curve):
@@ -1199,13 +1945,14 @@ def host_runner(curve):
     import ctypes
 
     lib = host_lib(curve)
-    for op, (wi, wo) in OPS.items():
+    table = ALL_OPS if curve == "bn254" else OPS  # the decider's pieces and rounds exist for BN254 only
+    for op, (wi, wo) in table.items():
         assert getattr(lib, "hc_%s_raw_io" % op)() == (wi << 16) | wo, op  # the table above is the header's
 
     def run(op, a):
         a = np.ascontiguousarray(a, dtype=np.int32)
-        assert a.ndim == 2 and a.shape[1] == OPS[op][0], op
-        out = np.zeros((len(a), OPS[op][1]), dtype=np.int32)
+        assert a.ndim == 2 and a.shape[1] == table[op][0], op
+        out = np.zeros((len(a), table[op][1]), dtype=np.int32)
         getattr(lib, "hc_%s_raw" % op)(a.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p), len(a))
         return out
 

@@ -9,6 +9,9 @@
 #include "../../snark-verifier_amd/csrc/fr29.h"
 #include "../../snark-verifier_amd/csrc/g1_29.h"
 #include "../../snark-verifier_amd/csrc/glv.h"
+#if !defined(SNARKV_CURVE_PALLAS)
+#include "../../snark-verifier_amd/csrc/g2_prepare_w.h"  // the pairing decider's lane pieces (BN254 only): decide_w.h, pairing_coop29.h
+#endif
 
 namespace snarkv {
 namespace rawops {
@@ -187,6 +190,62 @@ SNARKV_HD void op_glv_w3_digits(const int32_t* in, int32_t* out) {
     out[i] = glv_w3_digit((uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], (uint32_t)in[3], i, carry);
 }
 
+
+#if !defined(SNARKV_CURVE_PALLAS)
+// ---- the lane arithmetic of the pairing decider (fq29.h, pairing_coop29.h, decide_w.h, g2_prepare_w.h) ----
+SNARKV_HD void op_fq29_reduce_small(const int32_t* in, int32_t* out) { stq(fq29_reduce_small(ldq(in)), out); }
+// in: x, k (1 word)
+SNARKV_HD void op_fq29_mul_small_norm(const int32_t* in, int32_t* out) { stq(fq29_mul_small_norm(ldq(in), in[9]), out); }
+SNARKV_HD void op_wt_squeeze(const int32_t* in, int32_t* out) { stq(wt_squeeze(ldq(in)), out); }
+SNARKV_HD void op_wt_xi_e0(const int32_t* in, int32_t* out) { stq(wt_xi(ldq(in), ldq(in + 9), 0), out); }
+SNARKV_HD void op_wt_xi_e1(const int32_t* in, int32_t* out) { stq(wt_xi(ldq(in), ldq(in + 9), 1), out); }
+// in: x, m (1 word: 0 / -1)
+SNARKV_HD void op_wt_cneg(const int32_t* in, int32_t* out) { stq(wt_cneg(ldq(in), in[9]), out); }
+// in: a0, a1, y0, y1
+SNARKV_HD void op_coop3_product_e0(const int32_t* in, int32_t* out) {
+  stq(coop3_product(0, ldq(in), ldq(in + 9), ldq(in + 18), ldq(in + 27)), out);
+}
+SNARKV_HD void op_coop3_product_e1(const int32_t* in, int32_t* out) {
+  stq(coop3_product(1, ldq(in), ldq(in + 9), ldq(in + 18), ldq(in + 27)), out);
+}
+// in: lo, hi, hp
+SNARKV_HD void op_coop3_finalize_e0(const int32_t* in, int32_t* out) {
+  stq(coop3_finalize(0, ldq(in), ldq(in + 9), ldq(in + 18)), out);
+}
+SNARKV_HD void op_coop3_finalize_e1(const int32_t* in, int32_t* out) {
+  stq(coop3_finalize(1, ldq(in), ldq(in + 9), ldq(in + 18)), out);
+}
+// in: am, bm, ap, bp; out: the fused product, then what k_g2_prepare_w writes into the line table
+SNARKV_HD void op_g2w_product_e0(const int32_t* in, int32_t* out) {
+  const Fq29 v = g2w_product(ldq(in), ldq(in + 9), ldq(in + 18), ldq(in + 27), 0);
+  stq(v, out);
+  stq(fq29_canon_of_product(v), out + 9);
+}
+SNARKV_HD void op_g2w_product_e1(const int32_t* in, int32_t* out) {
+  const Fq29 v = g2w_product(ldq(in), ldq(in + 9), ldq(in + 18), ldq(in + 27), 1);
+  stq(v, out);
+  stq(fq29_canon_of_product(v), out + 9);
+}
+// in: x, y, g0, g1: the step coop_frob / coop_scale store
+SNARKV_HD void op_fq2_scale_norm_e0(const int32_t* in, int32_t* out) {
+  stq(fq2_scale_norm(ldq(in), ldq(in + 9), ldq(in + 18), ldq(in + 27), 0), out);
+}
+SNARKV_HD void op_fq2_scale_norm_e1(const int32_t* in, int32_t* out) {
+  stq(fq2_scale_norm(ldq(in), ldq(in + 9), ldq(in + 18), ldq(in + 27), 1), out);
+}
+// in: d0, d1 (coefficient 0 of the operand register); out: the two values WT_FQ2INV's one lane leaves in the scalar register
+SNARKV_HD void op_wt_fq2inv(const int32_t* in, int32_t* out) {
+  Fq29P lds[4];
+  wt_store(lds, 0, ldq(in));
+  wt_store(lds, 1, ldq(in + 9));
+  WtOp op{};
+  op.a = 0, op.dst = 2, op.kind = WT_FQ2INV;
+  wt_fq2inv(lds, op);
+  stq(wt_load(lds, 2), out);
+  stq(wt_load(lds, 3), out + 9);
+}
+#endif
+
 }  // namespace rawops
 }  // namespace snarkv
 
@@ -224,3 +283,30 @@ SNARKV_HD void op_glv_w3_digits(const int32_t* in, int32_t* out) {
   X(g1_29_scalar_mul_careful, 26, 36)    \
   X(glv_decompose, 8, 8)                \
   X(glv_w3_digits, 4, 43)
+
+// the pairing decider's pieces (BN254 only); tests/fq29_model.py keeps the same table as DECIDER_OPS
+#if !defined(SNARKV_CURVE_PALLAS)
+#define SNARKV_RAW_DECIDER_OPS(X) \
+  X(fq29_reduce_small, 9, 9)      \
+  X(fq29_mul_small_norm, 10, 9)   \
+  X(wt_squeeze, 9, 9)             \
+  X(wt_xi_e0, 18, 9)              \
+  X(wt_xi_e1, 18, 9)              \
+  X(wt_cneg, 10, 9)               \
+  X(coop3_product_e0, 36, 9)      \
+  X(coop3_product_e1, 36, 9)      \
+  X(coop3_finalize_e0, 27, 9)     \
+  X(coop3_finalize_e1, 27, 9)     \
+  X(g2w_product_e0, 36, 18)       \
+  X(g2w_product_e1, 36, 18)       \
+  X(fq2_scale_norm_e0, 36, 9)     \
+  X(fq2_scale_norm_e1, 36, 9)     \
+  X(wt_fq2inv, 18, 18)
+// records of the two whole rounds (device: k_wt_round / k_coop3_round of tests/devtest/devtest.hip, one workgroup per record;
+// host: round_emul.h), in words.  wt_round: A and B as 24 values each, kind, flags -> the 24 values of dst.
+// coop3_round: A and B as 12 coefficients each, mode -> 12 coefficients.
+constexpr int kWtRoundIn = 48 * 9 + 2, kWtRoundOut = 24 * 9;
+constexpr int kCoop3RoundIn = 24 * 9 + 1, kCoop3RoundOut = 12 * 9;
+#else
+#define SNARKV_RAW_DECIDER_OPS(X)
+#endif

@@ -11,6 +11,7 @@
 #include "../../snark-verifier_amd/csrc/fr29.h"
 #include "../../snark-verifier_amd/csrc/decide_sched.hpp"
 #include "../../snark-verifier_amd/csrc/g2_prepare_w.h"
+#include "../../snark-verifier_amd/csrc/round_emul.h"
 #include <vector>
 
 using namespace snarkv;
@@ -226,28 +227,7 @@ void ht29_double_n(const uint8_t* p, int n, uint8_t* out) {
 // the round k_decide runs (pairing_coop29.h "coop3"): 96 lanes emulated one by
 // one, butterflies replaced by explicit sums.  mode 0: f <- f*b each round;
 // mode 1: f <- f*f, then f <- f*b (the Miller-loop pattern, both operands lazy).
-static void coop3_round(const Fq29* fa, const Fq29* fb, Fq29* fc) {
-  Fq29 prod[96];
-  Coop3Lane L[96];
-  for (int l = 0; l < 96; ++l) {
-    L[l] = coop3_lane(l);
-    prod[l] = L[l].active ? coop3_product(L[l].e, fa[2 * L[l].i1], fa[2 * L[l].i1 + 1], fb[2 * L[l].i2 + L[l].e],
-                                          fb[2 * L[l].i2 + 1 - L[l].e])
-                          : fq29_zero();
-  }
-  Fq29 lo[12], hi[12];
-  for (int g = 0; g < 12; ++g) {
-    lo[g] = fq29_zero();
-    hi[g] = fq29_zero();
-    for (int j = 0; j < 8; ++j) {
-      int l = 8 * g + j;  // g = 2k + e
-      if (!L[l].active) continue;
-      Fq29& dst = L[l].high ? hi[g] : lo[g];
-      for (int i = 0; i < 9; ++i) dst.v[i] = (int32_t)((uint32_t)dst.v[i] + (uint32_t)prod[l].v[i]);
-    }
-  }
-  for (int g = 0; g < 12; ++g) fc[g] = coop3_finalize(g & 1, lo[g], hi[g], hi[g ^ 1]);
-}
+static void coop3_round(const Fq29* fa, const Fq29* fb, Fq29* fc) { coop3_round_emul(fa, fb, fc); }  // round_emul.h
 void ht_coop3_fq12_mul_iter(const uint8_t* a, const uint8_t* b, int rounds, int mode, uint8_t* out) {
   Fq fa8[12], fb8[12];
   coop_flat_from_tower(load_fq12(a), fa8);
@@ -332,18 +312,7 @@ int ht_decide_w(const uint8_t* q2, const uint8_t* acc, uint8_t* out, int* info) 
         wt_fq2inv(next.data(), op);  // reads a's coefficient 0 (unchanged in `next`: nothing else wrote it), writes the scalar register
         continue;
       }
-      for (int half = 0; half < 2; ++half) {
-        Fq29 own[8];
-        for (int g = 0; g < 8; ++g) {
-          Fq29 s = fq29_zero();
-          for (int jj = 0; jj < 8; ++jj) {
-            const Fq29 v = wt_task(lds.data(), op, half, 8 * g + jj);
-            for (int q = 0; q < 9; ++q) s.v[q] = (int32_t)((uint32_t)s.v[q] + (uint32_t)v.v[q]);
-          }
-          own[g] = wt_squeeze(s);
-        }
-        for (int g = 0; g < 8; ++g) wt_write(next.data(), op, half, 8 * g, own[g], own[g ^ 1]);
-      }
+      wt_round_emul(lds.data(), next.data(), op);  // round_emul.h
     }
     lds.swap(next);
   }

@@ -92,6 +92,66 @@ def test_signed_3bit_recoder(curve):
     assert n == checked >= 4000
 
 
+# ---- the pairing decider's lane arithmetic (BN254 only): tests/fq29_model.py sections 4, 4b, 4c
+def test_decider_pieces_at_their_lazy_bounds():
+    """every piece of SNARKV_RAW_DECIDER_OPS over the operand sets its producers can emit, >= 20 000 records each: residue,
+    limb shape, the set the consumers rely on, the model's limbs"""
+    checked, mx = M.decider_suite(M.CURVES["bn254"].fq, M.host_runner("bn254"), n=20000)
+    assert set(checked) == set(M.DECIDER_OPS) and min(checked.values()) >= 20000
+    for name, span in sorted(mx.items()):
+        print("%-24s value / p in [%.7f, %.7f]" % ((name,) + span))
+
+
+def _wt_variants():
+    import ctypes
+
+    buf = (ctypes.c_int32 * 128)()
+    n = M.host_lib("bn254").hc_wt_variants(buf, 64)
+    return [(buf[2 * i], buf[2 * i + 1]) for i in range(n)]
+
+
+def test_round_variant_table_is_the_programs():
+    """the (kind, flags) table of the round tests is exactly what wt_build_program() emits (WT_FQ2INV is one lane's
+    wt_fq2inv, not a round)"""
+    assert sorted(M.WT_VARIANTS + [(M.WT_FQ2INV, 0)]) == _wt_variants()
+
+
+def test_program_round_lane_by_lane_on_corner_operands():
+    """one round of k_decide_w emulated lane by lane (csrc/round_emul.h) on every variant, >= 2 000 records each:
+    the exact Fq12 / pointwise product, the stored-coefficient invariant, the exact xi copies"""
+    F = M.CURVES["bn254"].fq
+    rows, meta = M.wt_round_cases(F, 2000)
+    count, span = M.check_wt_round(F, M.host_runner("bn254")("wt_round", rows), meta)
+    print("stored coefficient / p in [%.7f, %.7f]" % span)
+    assert set(count) == set(M.WT_VARIANTS) and min(count.values()) >= 2000
+
+
+def test_team_round_lane_by_lane_on_corner_operands():
+    """one round of k_decide (coop_mul_b) emulated lane by lane: dense, sparse, line-shaped B and squarings"""
+    F = M.CURVES["bn254"].fq
+    rows, meta = M.coop3_round_cases(F, 2000)
+    n, span = M.check_coop3_round(F, M.host_runner("bn254")("coop3_round", rows), meta)
+    print("stored coefficient / p in [%.7f, %.7f]" % span)
+    assert n >= 4000
+
+
+def test_g2_prepare_program_stays_inside_its_contracts():
+    """integer intervals (units of p) through all levels of g2_prepare_prog.inc, read through the host build: every
+    combination fits the fq29_mul2 operand contract, every line coefficient reaches fq29_canon_of_product inside (-p, 2p),
+    no level reads a slot that it writes"""
+    F = M.CURVES["bn254"].fq
+    levels, tasks, slots, prog = M.g2w_program(M.host_lib("bn254"))
+    assert (levels, tasks) == (448, 7) and sum(1 for row in prog for t in row if t["used"] and t["dst"] < 0) == 102 * 3
+    comb_max, (lo, hi), bad = M.g2w_intervals(F, prog, slots)
+    print("largest |combination| = %.4f p; line values in (%.4f p, %.4f p)" % (comb_max, lo, hi))
+    assert not bad, bad[:5]
+    assert comb_max <= M.G2W_COMB_MAX, "a combination reaches %.3f p: above what g2w_product is tested to" % comb_max
+    assert -1 < lo and hi < 2
+    # carry-normalised operands within G2W_COMB_MAX p: |limb| < 2^29 and every column of the fused product inside int64
+    assert (int(M.G2W_COMB_MAX * F.q) >> 232) + 1 < 1 << 29
+    assert M.mul2_column_peak(F, M.G2W_COMB_MAX) < 1 << 63
+
+
 def _kernel_mads(asm_text, kernel):
     lines = asm_text.split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^_ZN\w*7devtest\d+%sEPKiPii:" % kernel, l))
