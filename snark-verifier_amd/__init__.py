@@ -38,11 +38,13 @@ from . import host_api  # noqa: F401,E402  (C API of the C++ host mirror: includ
 from . import host_api_pallas  # noqa: F401,E402  (the pasta flavour of the host mirror: include/snarkv_host_pallas.h)
 from . import ipa_prover  # noqa: F401,E402  (the IPA prover on the device: include/snarkv_ipa_prover.h)
 from .ipa_prover import IpaProver  # noqa: F401,E402
+from . import ipa_batch  # noqa: F401,E402  (many vectors against one resident IPA key: include/snarkv_ipa_batch.h)
 
 __all__ = [
     "host_api",
     "host_api_pallas",
     "ipa_prover",
+    "ipa_batch",
     "IpaProver",
     "Context",
     "DecidingKey",

@@ -333,6 +333,21 @@ class IpaDecidingKey:
             _check(self._lib.snarkv_ipa_dk_create_shard(ctx._h, g if g else b"\x00", len(g) // 64, k, first,
                                                         ctypes.byref(self._h)))
         self.k = self._lib.snarkv_ipa_dk_k(self._h)
+        self._ctx = ctx
+
+    def prepare(self, ctx=None):
+        """Build the key's window table now (`snarkv_ipa_dk_prepare`; include/snarkv_ipa_batch.h) on `ctx` (default: the
+        context the key was made on).  A no-op if it is built, or for a shard or a key over the cap."""
+        from . import ipa_batch
+
+        ipa_batch.dk_prepare(ctx or self._ctx, self)
+
+    @property
+    def table_bytes(self):
+        """Bytes of the window table: 0 until it is built, then 32 * 2^k * 64."""
+        from . import ipa_batch
+
+        return ipa_batch.dk_table_bytes(self, False)
 
     def close(self):
         if self._h:
@@ -631,6 +646,18 @@ class Context:
         ok = ctypes.create_string_buffer(max(m, 1))
         _check(self._lib.snarkv_ipa_decide_batch(self._h, dk._h, xi if xi else b"\x00", u if u else b"\x00", m, ok))
         return [b != 0 for b in ok.raw[:m]]
+
+    def ipa_commit_batch(self, dk, polys, n):
+        """m commitments `sum_j polys[a][j] G[j]` against the resident key in one call (`snarkv_ipa_commit_batch`):
+        `polys` = m x n scalars (32 bytes LE each) -> m points (64 bytes each), concatenated."""
+        from . import ipa_batch
+
+        return ipa_batch.commit_batch(self, dk, polys, n)
+
+    def ipa_commit_batch_dev(self, dk, d_polys, n, m, d_out, slices=0):
+        from . import ipa_batch
+
+        ipa_batch.commit_batch_dev(self, dk, d_polys, n, m, d_out, slices)
 
     def ipa_commit_partial_dev(self, dk, xi, d_partial):
         """This shard's part of commit(G, h(xi)) as a projective partial at device address `d_partial`."""

@@ -12,6 +12,7 @@
 #include <vector>
 #include <stdlib.h>
 #include "ctx.hpp"
+#include "../../include/snarkv_ipa_batch.h"
 
 namespace snarkv {
 
@@ -769,6 +770,11 @@ int bn254_ipa_dk_create(const uint8_t* g_points64, size_t n, snarkv_ipa_dk** out
 int bn254_ipa_decide_batch(const snarkv_ipa_dk* dk, const uint8_t* xi32, const uint8_t* u64, size_t m, uint8_t* ok) {
   SNARKV_DEFAULT_LEASE(c);
   return snarkv_ipa_decide_batch(c, dk, xi32, u64, m, ok);
+}
+
+int bn254_ipa_commit_batch(const snarkv_ipa_dk* dk, const uint8_t* polys32, size_t n, size_t m, uint8_t* out64s) {
+  SNARKV_DEFAULT_LEASE(c);
+  return snarkv_ipa_commit_batch(c, dk, polys32, n, m, out64s);
 }
 
 int bn254_poseidon_transcript_batch(const snarkv_poseidon* ps, const uint8_t* elems, size_t n, size_t L,

@@ -1,6 +1,7 @@
 // Internal: context object behind the C ABI (include/snarkv_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <mutex>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -134,6 +135,13 @@ struct snarkv_ipa_dk {
   void* d_points;  // the points held: 64 B canonical affine each, as the Pippenger entry point takes them
   size_t first;    // index of the first point held in the 2^k-point key (0 unless a multi-GPU shard)
   size_t count;    // points held (2^k unless a shard)
+  // the window table of the shared-key MSM (msm_shared.hip): T[w][j] = 2^(8 w) G[j], packed Montgomery affine.  Built at most
+  // once per key, under `table_mu` (handles are shared between host threads), by the first batched call or by
+  // snarkv_ipa_dk_prepare; freed with the key.  The fields are mutable: every call takes the key as const.
+  mutable std::mutex table_mu;
+  mutable int table_state;     // 0 not tried, 1 built, 2 declined (a shard, or over kSharedTableCap)
+  mutable void* d_table;
+  mutable size_t table_bytes;  // 0 until built
 };
 
 namespace snarkv {
@@ -209,6 +217,16 @@ int launch_buckets_add(snarkv_ctx* ctx, void* d_dst, const void* d_src, size_t c
 int launch_buckets_reduce(snarkv_ctx* ctx, const void* d_buckets, uint32_t c, uint32_t w0, uint32_t wcount, void* d_partial);
 int launch_fold_partials(snarkv_ctx* ctx, const void* d_partials, size_t count, void* d_out64, bool partial_out = false);
 int launch_fold_partials_many(snarkv_ctx* ctx, const void* d_partials, size_t count, size_t jobs, void* d_out64s);
+// the shared-key MSM (msm_shared.hip): many scalar vectors against the window table of one resident key
+constexpr size_t kSharedTableCap = (size_t)256 << 20;  // largest table built (2 KiB per base: keys up to 2^17)
+// can this key have a table at all? (whole key, table within the cap)
+bool ipa_dk_table_fits(const snarkv_ipa_dk* dk);
+// build the table if it is not there and fits; *have = the table can be used.  Synchronises ctx->stream when it builds.
+int ipa_dk_table_prepare(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, bool* have);
+// out[a] = sum_{j < n} s[a][j] G[j], a < m: d_scalars = m x n canonical scalars, d_out64s = m affine points in the call's
+// encoding.  The table must be built.  slices = 0: chosen so that m x slices workgroups fill the machine.
+int launch_msm_shared(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_scalars, size_t n, size_t m, uint32_t slices,
+                      void* d_out64s);
 int launch_validate(snarkv_ctx* ctx, const void* d_scalars, const void* d_points, size_t n, int* bad_host);
 int launch_g2_prepare(snarkv_ctx* ctx, const void* d_g2x2_256, void* d_prep);
 int launch_decide(snarkv_ctx* ctx, const void* d_prep, const void* d_accs, size_t m, void* d_ok, void* d_gt);

@@ -4,21 +4,28 @@
 // reference re-reads it from memory on every decide, a PCIe copy of 64 * 2^k bytes here --
 // and the 2^k coefficients of h(X) = prod_i (1 + xi_{k-1-i} X^(2^i)) (pcs/ipa.rs:405-421)
 // are produced by a kernel straight into the scalar buffer of the Pippenger, so a decide
-// moves k scalars in and 64 bytes out.
+// moves k scalars in and 64 bytes out.  A batch of accumulators runs as ONE shared-key MSM over the key's window table
+// (msm_shared.hip) from the thresholds below on, one Pippenger per accumulator otherwise.
+#include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <vector>
 #include "ctx.hpp"
 #include "fr29.h"
+#include "../../include/snarkv_ipa_batch.h"
 
 namespace snarkv {
 
 // coeff[j] = prod over the set bits i of j of xi[k-1-i]   (h_coeffs with scalar = 1: the
 // doubling loop `coeffs[len + j] = coeffs[j] * xi` unrolled per index).  One lane per
-// coefficient, <= k products; canonical little-endian out.
+// coefficient, <= k products; canonical little-endian out.  blockIdx.y = the accumulator: its k challenges, its `count`
+// coefficients (one vector of the shared-key MSM's batch; a single accumulator launches one row).
 __global__ void __launch_bounds__(256)
     k_h_coeffs(const uint32_t* __restrict__ xi_canon, uint32_t k, uint32_t first, uint32_t count,
                uint32_t* __restrict__ out) {
   __shared__ Fr29 sx[32];
+  xi_canon += 8 * (size_t)blockIdx.y * k;
+  out += 8 * (size_t)blockIdx.y * count;
   if (threadIdx.x < k) sx[threadIdx.x] = fr29_from_canonical(xi_canon + 8 * (size_t)(k - 1 - threadIdx.x));
   __syncthreads();
   uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -33,6 +40,31 @@ __global__ void __launch_bounds__(256)
   uint4* o = reinterpret_cast<uint4*>(out + 8 * (size_t)t);
   o[0] = make_uint4(w[0], w[1], w[2], w[3]);
   o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+
+// SNARKV_IPA_SHARED, read once: 0 = never the shared-key MSM, 1 = whenever the table fits, unset = by the thresholds
+static int shared_mode() {
+  static const int v = [] {
+    const char* e = getenv("SNARKV_IPA_SHARED");
+    return e && *e ? (atoi(e) ? 1 : 0) : -1;
+  }();
+  return v;
+}
+
+// When decide_batch takes the shared-key MSM, from profiles/ipa_batch_bench.txt (both curves alike):
+//   k <= 14   the table route wins at every m measured, m = 1 included (k = 8: 0.37 against 0.83 ms, k = 14: 0.71 against
+//             1.12); a lone accumulator does not BUILD the table, though -- the build costs one to three calls, and a caller
+//             that makes a key for one decide would pay it every time -- it uses the table once a batch or prepare() built it
+//   k >  14   at k = 16 a lone accumulator loses on the table (1.25 against 1.10 ms), m = 4 ties within the parent's spread
+//             and m = 64 wins by 15 %: the table serves batches of kSharedMinMLargeKey or more, between the tie and the win
+constexpr uint32_t kSharedSmallKeyMaxK = 14;
+constexpr size_t kSharedBuildMinM = 2;      // k <= kSharedSmallKeyMaxK: smallest batch that builds the table
+constexpr size_t kSharedMinMLargeKey = 8;   // above: smallest batch on the table route
+constexpr size_t kDecideHCap = (size_t)64 << 20;  // coefficient vectors of one group of accumulators
+// does a batch of m accumulators take the table route without the override? (`built`: the key has its table already)
+static bool shared_by_threshold(uint32_t k, size_t m, bool built) {
+  if (k > kSharedSmallKeyMaxK) return m >= kSharedMinMLargeKey;
+  return built || m >= kSharedBuildMinM;
 }
 
 }  // namespace snarkv
@@ -50,6 +82,9 @@ static int ipa_dk_make(snarkv_ctx* ctx, const uint8_t* g_points64, uint32_t k, s
   dk->first = first;
   dk->count = count;
   dk->d_points = nullptr;
+  dk->table_state = 0;
+  dk->d_table = nullptr;
+  dk->table_bytes = 0;
   if (hipMalloc(&dk->d_points, count * 64) != hipSuccess) {
     delete dk;
     set_last_error("ipa_dk_create: hipMalloc of %zu bytes failed", count * 64);
@@ -101,7 +136,22 @@ void SNARKV_API(ipa_dk_destroy)(snarkv_ipa_dk* dk) {
   if (!dk) return;
   (void)hipSetDevice(dk->device);
   if (dk->d_points) (void)hipFree(dk->d_points);
+  if (dk->d_table) (void)hipFree(dk->d_table);
   delete dk;
+}
+
+int SNARKV_API(ipa_dk_prepare)(snarkv_ctx* ctx, snarkv_ipa_dk* dk) {
+  if (!ctx || !dk) return SNARKV_ERR_ARG;
+  if (dk->device != ctx->device) return SNARKV_ERR_ARG;
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  bool have;
+  return ipa_dk_table_prepare(ctx, dk, &have);  // a shard or a key over the cap: nothing to build, still OK
+}
+
+size_t SNARKV_API(ipa_dk_table_bytes)(const snarkv_ipa_dk* dk) {
+  if (!dk) return 0;
+  std::lock_guard<std::mutex> lk(dk->table_mu);
+  return dk->table_bytes;
 }
 
 uint32_t SNARKV_API(ipa_dk_k)(const snarkv_ipa_dk* dk) { return dk ? dk->k : 0; }
@@ -120,6 +170,28 @@ int SNARKV_API(ipa_decide_batch)(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const
   SNARKV_TRY(ctx_reserve(ctx, SLOT_IPA_XI, m * k * 32, &d_xi));
   SNARKV_TRY(ctx_reserve(ctx, SLOT_IPA_OUT, m * 64, &d_out));
   SNARKV_HIP(hipMemcpyAsync(d_xi, xi32, m * k * 32, hipMemcpyHostToDevice, ctx->stream));
+  // the shared-key MSM: the coefficients of a group of accumulators into one buffer, one launch for the group
+  bool shared = false;
+  if (shared_mode() != 0 && ipa_dk_table_fits(dk) &&
+      (shared_mode() == 1 || shared_by_threshold(k, m, SNARKV_API(ipa_dk_table_bytes)(dk) != 0)))
+    SNARKV_TRY(ipa_dk_table_prepare(ctx, dk, &shared));
+  if (shared) {
+    const size_t group = std::min<size_t>({m, (size_t)32768, std::max<size_t>(1, kDecideHCap / (n * 32))});
+    void* d_h;
+    SNARKV_TRY(ctx_reserve(ctx, SLOT_IPA_H, group * n * 32, &d_h));
+    for (size_t a0 = 0; a0 < m; a0 += group) {
+      const size_t g = std::min(group, m - a0);
+      hipLaunchKernelGGL(k_h_coeffs, dim3((uint32_t)((n + 255) / 256), (uint32_t)g), dim3(256), 0, ctx->stream,
+                         (const uint32_t*)d_xi + a0 * k * 8, k, 0u, (uint32_t)n, (uint32_t*)d_h);
+      SNARKV_HIP(hipGetLastError());
+      SNARKV_TRY(launch_msm_shared(ctx, dk, d_h, n, g, 0, (uint8_t*)d_out + 64 * a0));
+    }
+    std::vector<uint8_t> got(m * 64);
+    SNARKV_HIP(hipMemcpyAsync(got.data(), d_out, m * 64, hipMemcpyDeviceToHost, ctx->stream));
+    SNARKV_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t a = 0; a < m; ++a) ok[a] = memcmp(&got[64 * a], u64 + 64 * a, 64) == 0 ? 1 : 0;
+    return SNARKV_OK;
+  }
   // accumulators are independent: up to four in flight (the tail of one Pippenger -- bucket reduce,
   // shift chains -- overlaps the accumulation of the next), each lane with its own h buffer
   const bool lanes = m >= 2;

@@ -20,6 +20,7 @@
 #include "ctx.hpp"
 #include "fr29.h"
 #include "../../include/snarkv_ipa_prover.h"
+#include "../../include/snarkv_ipa_batch.h"
 
 namespace snarkv {
 
@@ -487,6 +488,82 @@ int SNARKV_API(ipa_commit)(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const uint8
   if (omega32) SNARKV_TRY(launch_msm_batched(ctx, sm + 128, sm, sm + 192, 1, 2, sm + 256));
   SNARKV_HIP(hipMemcpyAsync(out64, sm + 256, 64, hipMemcpyDeviceToHost, ctx->stream));
   SNARKV_HIP(hipStreamSynchronize(ctx->stream));
+  return SNARKV_OK;
+}
+
+// m commitments against the resident key: the shared-key MSM (msm_shared.hip) when the key can have its window table,
+// one MSM per vector otherwise (a key over kSharedTableCap, SNARKV_IPA_SHARED=0).  Device to device, enqueued.
+static int commit_batch_run(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_polys, size_t n, size_t m,
+                            uint32_t slices, void* d_out, uint8_t* d_small) {
+  static const bool never = [] {
+    const char* e = getenv("SNARKV_IPA_SHARED");
+    return e && *e && atoi(e) == 0;
+  }();
+  bool shared = false;
+  if (!never) SNARKV_TRY(ipa_dk_table_prepare(ctx, dk, &shared));
+  if (shared) return launch_msm_shared(ctx, dk, d_polys, n, m, slices, d_out);
+  const uint32_t off[2] = {0, (uint32_t)n};
+  SNARKV_HIP(hipMemcpyAsync(d_small + 8, off, sizeof(off), hipMemcpyHostToDevice, ctx->stream));
+  SNARKV_HIP(hipStreamSynchronize(ctx->stream));  // `off` lives on this frame
+  for (size_t a = 0; a < m; ++a)
+    SNARKV_TRY(ipa_msm(ctx, (const uint8_t*)d_polys + 32 * a * n, dk->d_points, n, d_small + 8, (uint8_t*)d_out + 64 * a));
+  return SNARKV_OK;
+}
+
+static int commit_batch_check(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* polys, size_t n, size_t m, const void* out) {
+  if (!ctx || !dk || !polys || !out) return SNARKV_ERR_ARG;
+  if (dk->device != ctx->device) return SNARKV_ERR_ARG;
+  if (n == 0 || m == 0) return SNARKV_ERR_EMPTY;
+  if (dk->first != 0 || n > dk->count) return SNARKV_ERR_LENGTH;
+  return SNARKV_OK;
+}
+
+// SNARKV_FLAG_VALIDATE over `total` device scalars
+static int commit_batch_validate(snarkv_ctx* ctx, const void* d_s, size_t total, uint8_t* d_small) {
+  if (!(ctx->flags & SNARKV_FLAG_VALIDATE)) return SNARKV_OK;
+  const size_t step = (size_t)1 << 30;
+  for (size_t i = 0; i < total; i += step) {
+    int bad = 0;
+    SNARKV_TRY(count_bad(ctx, (const uint8_t*)d_s + 32 * i, std::min(step, total - i), (int*)d_small, &bad));
+    if (bad) {
+      set_last_error("ipa_commit_batch: %d scalars are not canonical", bad);
+      return SNARKV_ERR_ENCODING;
+    }
+  }
+  return SNARKV_OK;
+}
+
+int SNARKV_API(ipa_commit_batch_dev)(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_polys32, size_t n, size_t m,
+                                     uint32_t slices, void* d_out64s) {
+  SNARKV_TRY(commit_batch_check(ctx, dk, d_polys32, n, m, d_out64s));
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  SNARKV_WIRE_FORM(ctx);
+  void* d_sm;
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_IPA_OUT, 64, &d_sm));
+  SNARKV_TRY(commit_batch_validate(ctx, d_polys32, m * n, (uint8_t*)d_sm));
+  return commit_batch_run(ctx, dk, d_polys32, n, m, slices, d_out64s, (uint8_t*)d_sm);
+}
+
+int SNARKV_API(ipa_commit_batch)(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const uint8_t* polys32, size_t n, size_t m,
+                                 uint8_t* out64s) {
+  SNARKV_TRY(commit_batch_check(ctx, dk, polys32, n, m, out64s));
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  SNARKV_WIRE_FORM(ctx);
+  // vectors are staged in groups of bounded size, so m x n is unbounded
+  const size_t cap = (size_t)64 << 20;
+  const size_t group = std::min(m, std::max<size_t>(1, cap / (n * 32)));
+  void *d_s, *d_o, *d_sm;
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_IN_SCALARS, group * n * 32, &d_s));
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_OUT, group * 64, &d_o));
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_IPA_OUT, 64, &d_sm));
+  for (size_t a0 = 0; a0 < m; a0 += group) {
+    const size_t g = std::min(group, m - a0);
+    SNARKV_HIP(hipMemcpyAsync(d_s, polys32 + 32 * a0 * n, g * n * 32, hipMemcpyHostToDevice, ctx->stream));
+    SNARKV_TRY(commit_batch_validate(ctx, d_s, g * n, (uint8_t*)d_sm));
+    SNARKV_TRY(commit_batch_run(ctx, dk, d_s, n, g, 0, d_o, (uint8_t*)d_sm));
+    SNARKV_HIP(hipMemcpyAsync(out64s + 64 * a0, d_o, g * 64, hipMemcpyDeviceToHost, ctx->stream));
+    SNARKV_HIP(hipStreamSynchronize(ctx->stream));
+  }
   return SNARKV_OK;
 }
 

@@ -17,6 +17,7 @@
 // entry point of the batched point decompression (decompress_pallas.hip) and the context-free pallas_* forms.
 #include <mutex>
 #include "ctx.hpp"
+#include "../../include/snarkv_ipa_batch.h"
 #include "../../include/snarkv_pallas.h"
 #include "../../include/snarkv_pallas_decompress.h"
 
@@ -94,6 +95,10 @@ int pallas_ipa_dk_create(const uint8_t* g_points64, size_t n, snarkv_ipa_dk** ou
 int pallas_ipa_decide_batch(const snarkv_ipa_dk* dk, const uint8_t* xi32, const uint8_t* u64, size_t m, uint8_t* ok) {
   PALLAS_DEFAULT_CTX();
   return snarkv_pallas_ipa_decide_batch(c, dk, xi32, u64, m, ok);
+}
+int pallas_ipa_commit_batch(const snarkv_ipa_dk* dk, const uint8_t* polys32, size_t n, size_t m, uint8_t* out64s) {
+  PALLAS_DEFAULT_CTX();
+  return snarkv_pallas_ipa_commit_batch(c, dk, polys32, n, m, out64s);
 }
 int pallas_g1_decompress(const uint8_t* in32, size_t n, uint8_t* out64, uint8_t* ok) {
   PALLAS_DEFAULT_CTX();

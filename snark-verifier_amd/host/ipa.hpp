@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/snarkv_ipa_prover.h"
+#include "../../include/snarkv_ipa_batch.h"
 #include "pcs.hpp"
 
 // the prover session of the library the mirror is linked against (include/snarkv_ipa_prover.h)
@@ -384,6 +385,21 @@ inline G1Affine commit(Ctx& ctx, const snarkv_ipa_dk* dk, const std::vector<Fr>&
   check(SNARKV_IPA_PROVER(ipa_commit)(ctx.c, dk, pb.data(), poly.size(), omega ? om : nullptr, omega ? s->b : nullptr,
                                       out.b),
         "ipa_commit");
+  return out;
+}
+// `commit` for several polynomials of one length against one key in a single call (include/snarkv_ipa_batch.h): the
+// commitments to polys[a] over the first polys[0].size() bases, no blinding
+inline std::vector<G1Affine> commit_batch(Ctx& ctx, const snarkv_ipa_dk* dk, const std::vector<std::vector<Fr>>& polys) {
+  std::vector<G1Affine> out(polys.size());
+  if (polys.empty()) return out;
+  const size_t n = polys[0].size();
+  std::vector<uint8_t> pb(32 * n * polys.size()), ob(64 * polys.size());
+  for (size_t a = 0; a < polys.size(); ++a) {
+    if (polys[a].size() != n) throw Panic("commit_batch: the polynomials of a batch have one length");
+    for (size_t i = 0; i < n; ++i) polys[a][i].to_bytes(&pb[32 * (a * n + i)]);
+  }
+  check(SNARKV_IPA_PROVER(ipa_commit_batch)(ctx.c, dk, pb.data(), n, polys.size(), ob.data()), "ipa_commit_batch");
+  for (size_t a = 0; a < polys.size(); ++a) memcpy(out[a].b, &ob[64 * a], 64);
   return out;
 }
 }  // namespace ipa_prover_detail

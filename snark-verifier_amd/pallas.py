@@ -150,7 +150,19 @@ class PallasContext:
         g = _as_bytes(g)
         h = ctypes.c_void_p()
         _check(self._lib.snarkv_pallas_ipa_dk_create(self._h, g if g else b"\x00", len(g) // 64, ctypes.byref(h)))
-        return PallasIpaDecidingKey(self._lib, h)
+        return PallasIpaDecidingKey(self._lib, h, self)
+
+    def ipa_commit_batch(self, dk, polys, n):
+        """m commitments against the resident key in one call (`snarkv_pallas_ipa_commit_batch`): `polys` = m x n scalars
+        -> m points (64 bytes each), concatenated."""
+        from . import ipa_batch
+
+        return ipa_batch.commit_batch(self, dk, polys, n)
+
+    def ipa_commit_batch_dev(self, dk, d_polys, n, m, d_out, slices=0):
+        from . import ipa_batch
+
+        ipa_batch.commit_batch_dev(self, dk, d_polys, n, m, d_out, slices)
 
     def ipa_decide_batch(self, dk, xi, u):
         """`IpaAs::decide_all` per accumulator on pallas (pcs/ipa/decider.rs:47-66) -> list of booleans."""
@@ -163,9 +175,21 @@ class PallasContext:
 
 
 class PallasIpaDecidingKey:
-    def __init__(self, lib, h):
-        self._lib, self._h = lib, h
+    def __init__(self, lib, h, ctx=None):
+        self._lib, self._h, self._ctx = lib, h, ctx
         self.k = lib.snarkv_pallas_ipa_dk_k(h)
+
+    def prepare(self, ctx=None):
+        """Build the key's window table now (`snarkv_pallas_ipa_dk_prepare`; include/snarkv_ipa_batch.h)."""
+        from . import ipa_batch
+
+        ipa_batch.dk_prepare(ctx or self._ctx, self)
+
+    @property
+    def table_bytes(self):
+        from . import ipa_batch
+
+        return ipa_batch.dk_table_bytes(self, True)
 
     def close(self):
         if self._h:

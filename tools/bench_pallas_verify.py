@@ -7,6 +7,8 @@ succinct-verified through
                thread, the key re-parsed on every call)
   (b) host     snarkv_host_pallas_plonk_succinct_verify_batch, SNARKV_HOST_PALLAS_DECOMPRESS_HOST
   (c) device   the same entry point, SNARKV_HOST_PALLAS_DECOMPRESS_DEVICE
+  (d) verify   snarkv_host_pallas_plonk_verify, DEVICE decompression: the succinct half of (c) AND `decide_all` over the N
+               accumulators (one process per setting of SNARKV_IPA_SHARED: the knob is read once; not in the default set)
 with 16 host threads.  The routes alternate inside one process; every call ends synchronised (the accumulators are
 back on the host), so a host clock around the call is the measurement: 3 warm-ups, then the median of --reps rounds,
 with min / max as the spread.  The kernel's own time comes from a separate run of this tool with `--routes c` under
@@ -131,7 +133,8 @@ def main():
     routes = a.routes.split(",")
     lines = ["# tools/bench_pallas_verify.py: k = %d, %d base proofs of %d bytes (%d points), host_threads = %d, reps = %d"
              % (K, BASE, len(d["proofs"][0]), 12 + 2 * K, THREADS, a.reps),
-             "# ms per call: median [min .. max];  a = hooks (decide = 0), b = API HOST, c = API DEVICE"]
+             "# ms per call: median [min .. max];  a = hooks (decide = 0), b = API HOST, c = API DEVICE, d = plonk_verify (c + decide_all)",
+             "# SNARKV_IPA_SHARED = %s" % os.environ.get("SNARKV_IPA_SHARED", "unset")]
     result = {}
     for n in [int(x) for x in a.n.split(",")]:
         ib = b"".join(d["instances"][i % BASE] for i in range(n))
@@ -141,6 +144,10 @@ def main():
 
         def run(route):
             t0 = time.perf_counter()
+            if route == "d":
+                ok = H.plonk_verify(protocol, dk, ib, pb, n, THREADS, H.DECOMPRESS_DEVICE)
+                assert ok, route
+                return (time.perf_counter() - t0) * 1e3, None
             if route == "a":
                 rc = fn(2, d["protocol"], len(d["protocol"]), ib, len(ib), pb, len(pb), n, svk, d["g"], 1 << K, THREADS, out, 0)
                 accs = out.raw
@@ -156,9 +163,9 @@ def main():
         for rep in range(3 + a.reps):
             for r in routes:  # the routes alternate: drift of the machine falls on all of them alike
                 dt, accs = run(r)
-                if ref is None:
+                if ref is None and accs is not None:
                     ref = accs
-                assert accs == ref, "route %s disagrees" % r
+                assert accs is None or accs == ref, "route %s disagrees" % r
                 if rep >= 3:
                     times[r].append(dt)
         row = {r: (statistics.median(t), min(t), max(t)) for r, t in times.items()}
