@@ -39,12 +39,14 @@ from . import host_api_pallas  # noqa: F401,E402  (the pasta flavour of the host
 from . import ipa_prover  # noqa: F401,E402  (the IPA prover on the device: include/snarkv_ipa_prover.h)
 from .ipa_prover import IpaProver  # noqa: F401,E402
 from . import ipa_batch  # noqa: F401,E402  (many vectors against one resident IPA key: include/snarkv_ipa_batch.h)
+from . import ipa_fold  # noqa: F401,E402  (decide_all as one folded check: include/snarkv_ipa_fold.h)
 
 __all__ = [
     "host_api",
     "host_api_pallas",
     "ipa_prover",
     "ipa_batch",
+    "ipa_fold",
     "IpaProver",
     "Context",
     "DecidingKey",

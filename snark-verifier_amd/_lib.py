@@ -659,6 +659,18 @@ class Context:
 
         ipa_batch.commit_batch_dev(self, dk, d_polys, n, m, d_out, slices)
 
+    def ipa_decide_folded(self, dk, xi, u, rho):
+        """`IpaAs::decide_all` as ONE folded check (`snarkv_ipa_decide_folded`; include/snarkv_ipa_fold.h): True iff
+        `sum rho^i U_i == <sum rho^i h_coeffs(xi_i), G>`.  The caller owns the soundness of `rho`."""
+        from . import ipa_fold
+
+        return ipa_fold.decide_folded(self, dk, xi, u, rho)
+
+    def ipa_fold_coeffs_dev(self, k, xi, rho, d_h, slices=0):
+        from . import ipa_fold
+
+        ipa_fold.fold_coeffs_dev(self, k, xi, rho, d_h, slices)
+
     def ipa_commit_partial_dev(self, dk, xi, d_partial):
         """This shard's part of commit(G, h(xi)) as a projective partial at device address `d_partial`."""
         xi = _as_bytes(xi)

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsnarkv_amd.so")
 UNITS = ["ctx", "msm_api", "capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "ipa_prover", "mgpu",
-         "decompress", "msm_shared"]
+         "decompress", "msm_shared", "ipa_fold"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
@@ -27,6 +27,7 @@ def _deps():
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_pallas_decompress.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_prover.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_batch.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_fold.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
 
@@ -74,7 +75,8 @@ def _link(lib, res, extra):
 
 
 # The pasta build of the curve-generic units (csrc/pallas.hip explains the flags, csrc/ctx.hpp the policy they select).
-PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover", "decompress_pallas", "msm_shared"]
+PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover", "decompress_pallas", "msm_shared",
+                "ipa_fold"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
 
@@ -131,20 +133,22 @@ HOST_LIB = os.path.join(HERE, "libsnarkv_host.so")                 # product: C 
 HOSTTEST_LIB = os.path.join(HERE, "libsnarkv_hosttest.so")         # test hooks only (host/test_driver.cpp)
 HOST_PALLAS_LIB = os.path.join(HERE, "libsnarkv_hosttest_pallas.so")  # pasta flavour of the mirror, test hooks
 HOST_PALLAS_API_LIB = os.path.join(HERE, "libsnarkv_host_pallas.so")  # pasta flavour, product C API (host/capi_pallas.cpp)
+# the folded decide on top of it (host/capi_pallas_fold.cpp, include/snarkv_host_pallas_fold.h)
+HOST_PALLAS_FOLD_LIB = os.path.join(HERE, "libsnarkv_host_pallas_fold.so")
 
 
 def _host_stale(out, dev_lib):
     inc = os.path.join(os.path.dirname(HERE), "include")
     srcs = [os.path.join(HOST, f) for f in os.listdir(HOST)] + [os.path.join(inc, h) for h in (
-        "snarkv_host.h", "snarkv_host_pallas.h", "snarkv_pallas_decompress.h")]
+        "snarkv_host.h", "snarkv_host_pallas.h", "snarkv_pallas_decompress.h", "snarkv_host_pallas_fold.h", "snarkv_ipa_fold.h")]
     newest = max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(dev_lib)])
     return not os.path.exists(out) or os.path.getmtime(out) < newest
 
 
-def _gxx(out, src, extra, dev):
+def _gxx(out, src, extra, dev, more_libs=()):
     # -mbmi2 -madx: mulx/adcx for the 4x64 Montgomery products (every x86-64 server CPU since 2015)
     cmd = ["g++", "-O3", "-mbmi2", "-madx", "-std=c++17", "-shared", "-fPIC"] + extra + ["-o", out, os.path.join(HOST, src),
-           "-L" + HERE, "-l" + dev, "-pthread", "-Wl,-rpath,$ORIGIN"]
+           "-L" + HERE] + ["-l" + l for l in more_libs] + ["-l" + dev, "-pthread", "-Wl,-rpath,$ORIGIN"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)
@@ -173,6 +177,9 @@ def build_host_driver():
     if jobs:
         with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
             list(ex.map(lambda j: _gxx(*j), jobs))
+    # links against the product library built above
+    if os.path.exists(HOST_PALLAS_API_LIB) and _host_stale(HOST_PALLAS_FOLD_LIB, HOST_PALLAS_API_LIB):
+        _gxx(HOST_PALLAS_FOLD_LIB, "capi_pallas_fold.cpp", pasta, "snarkv_pallas", ["snarkv_host_pallas"])
     return HOST_LIB
 
 
@@ -184,6 +191,11 @@ def build_host_driver_pallas():
 def build_host_api_pallas():
     build_host_driver()
     return HOST_PALLAS_API_LIB
+
+
+def build_host_api_pallas_fold():
+    build_host_driver()
+    return HOST_PALLAS_FOLD_LIB
 
 
 if __name__ == "__main__":

@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include "ctx.hpp"
 #include "../../include/snarkv_ipa_batch.h"
+#include "../../include/snarkv_ipa_fold.h"
 
 namespace snarkv {
 
@@ -775,6 +776,12 @@ int bn254_ipa_decide_batch(const snarkv_ipa_dk* dk, const uint8_t* xi32, const u
 int bn254_ipa_commit_batch(const snarkv_ipa_dk* dk, const uint8_t* polys32, size_t n, size_t m, uint8_t* out64s) {
   SNARKV_DEFAULT_LEASE(c);
   return snarkv_ipa_commit_batch(c, dk, polys32, n, m, out64s);
+}
+
+int bn254_ipa_decide_folded(const snarkv_ipa_dk* dk, const uint8_t* xi32, const uint8_t* u64, size_t m,
+                            const uint8_t rho32[32], int* all_ok) {
+  SNARKV_DEFAULT_LEASE(c);
+  return snarkv_ipa_decide_folded(c, dk, xi32, u64, m, rho32, all_ok);
 }
 
 int bn254_poseidon_transcript_batch(const snarkv_poseidon* ps, const uint8_t* elems, size_t n, size_t L,

@@ -77,6 +77,7 @@ enum Slot {
   SLOT_IPA_OUT,
   SLOT_MGPU_GRID,
   SLOT_MGPU_RECV,
+  SLOT_IPA_FOLD,     // the folded decide (ipa_fold.hip): challenges and powers in the Montgomery domain, partial vectors
   SLOT_COUNT
 };
 

@@ -18,6 +18,7 @@
 #include <mutex>
 #include "ctx.hpp"
 #include "../../include/snarkv_ipa_batch.h"
+#include "../../include/snarkv_ipa_fold.h"
 #include "../../include/snarkv_pallas.h"
 #include "../../include/snarkv_pallas_decompress.h"
 
@@ -99,6 +100,11 @@ int pallas_ipa_decide_batch(const snarkv_ipa_dk* dk, const uint8_t* xi32, const 
 int pallas_ipa_commit_batch(const snarkv_ipa_dk* dk, const uint8_t* polys32, size_t n, size_t m, uint8_t* out64s) {
   PALLAS_DEFAULT_CTX();
   return snarkv_pallas_ipa_commit_batch(c, dk, polys32, n, m, out64s);
+}
+int pallas_ipa_decide_folded(const snarkv_ipa_dk* dk, const uint8_t* xi32, const uint8_t* u64, size_t m,
+                             const uint8_t rho32[32], int* all_ok) {
+  PALLAS_DEFAULT_CTX();
+  return snarkv_pallas_ipa_decide_folded(c, dk, xi32, u64, m, rho32, all_ok);
 }
 int pallas_g1_decompress(const uint8_t* in32, size_t n, uint8_t* out64, uint8_t* ok) {
   PALLAS_DEFAULT_CTX();

@@ -256,7 +256,10 @@ class Blake2bTranscript : public Transcript {
     state_.update(&prefix, 1);
     uint8_t h[64];
     state_.digest(h);
-    // `from_uniform_bytes`: the 512-bit little-endian integer mod r = lo + hi * 2^256
+    return from_uniform_bytes(h);
+  }
+  // `from_uniform_bytes`: the 512-bit little-endian integer mod r = lo + hi * 2^256
+  static Fr from_uniform_bytes(const uint8_t h[64]) {
     Fr lo = fr_from_le_mod_r(h), hi = fr_from_le_mod_r(h + 32);
     return lo + hi * two_256();
   }

@@ -12,6 +12,7 @@
 #include <string>
 
 #include "blake2b_transcript.hpp"
+#include "capi_pallas_handles.hpp"
 #include "ipa.hpp"
 #include "plonk.hpp"
 #include "plonk_ipa_batch.hpp"
@@ -19,12 +20,6 @@
 
 using namespace snarkv_host;
 
-struct snarkv_host_pallas_protocol {
-  PlonkProtocol pr;
-};
-struct snarkv_host_pallas_ipa_dk {
-  IpaDecidingKey dk;
-};
 
 namespace {
 thread_local std::string g_last_error;

@@ -48,7 +48,18 @@ _SIGNATURES = {
                                             _vp]),
 }
 
+# name -> (restype, argtypes); every function include/snarkv_host_pallas_fold.h declares (libsnarkv_host_pallas_fold.so: a
+# library and a table of its own, as the header is)
+_FOLD_LIB_NAME = "libsnarkv_host_pallas_fold.so"
+_FOLD_SIGNATURES = {
+    "snarkv_host_pallas_fold_last_error": (_cp, []),
+    "snarkv_host_pallas_ipa_fold_challenge": (_int, [_vp, _cp, _u32, _cp, _vp]),
+    "snarkv_host_pallas_ipa_decide_all_folded": (_int, [_vp, _cp, _u32, _cp, _vp]),
+    "snarkv_host_pallas_plonk_verify_folded": (_int, [_vp, _vp, _cp, _sz, _cp, _sz, _u32, _uint, _int, _cp]),
+}
+
 _lib = None
+_fold_lib = None
 
 
 def lib_path():
@@ -71,6 +82,32 @@ def load_library():
             fn.restype, fn.argtypes = res, args
         _lib = L
     return _lib
+
+
+def fold_lib_path():
+    return os.environ.get("SNARKV_HOST_PALLAS_FOLD_LIB") or os.path.join(HERE, _FOLD_LIB_NAME)
+
+
+def load_fold_library():
+    """Loads libsnarkv_host_pallas_fold.so (which binds libsnarkv_host_pallas.so and libsnarkv_pallas.so next to it)."""
+    global _fold_lib
+    if _fold_lib is None:
+        path = fold_lib_path()
+        if not os.path.exists(path):
+            raise HostError(ERR_DEVICE, "%s not built (run `python __graft_entry__.py`)" % path)
+        load_library()
+        L = ctypes.CDLL(path)
+        for name, (res, args) in _FOLD_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
+        _fold_lib = L
+    return _fold_lib
+
+
+def _check_fold(rc):
+    if rc < 0:
+        raise HostError(rc, (load_fold_library().snarkv_host_pallas_fold_last_error() or b"").decode(errors="replace"))
+    return rc
 
 
 def _check(rc):
@@ -145,6 +182,37 @@ def ipa_decide_all(dk, accs):
 def plonk_verify(protocol, dk, instances, proofs, n, host_threads=0, decompress=DECOMPRESS_AUTO):
     return _check(load_library().snarkv_host_pallas_plonk_verify(protocol._h, dk._h, instances, len(instances), proofs, len(proofs),
                                                                  n, host_threads, decompress)) == 1
+
+
+def _seed(seed):
+    assert seed is None or len(seed) == 32
+    return None if seed is None else bytes(seed)
+
+
+def ipa_fold_challenge(dk, accs, seed=None):
+    """rho of the folded decide: BLAKE2b-512 (personalisation `snarkv_ipa_fold1`) over `u32le k | u32le m | accs | seed`,
+    reduced mod r as the Blake2b transcript squeezes -> 32 bytes LE.  No device work."""
+    m = len(accs) // dk.acc_bytes
+    assert len(accs) == m * dk.acc_bytes
+    rho = ctypes.create_string_buffer(32)
+    _check_fold(load_fold_library().snarkv_host_pallas_ipa_fold_challenge(dk._h, bytes(accs), m, _seed(seed), rho))
+    return rho.raw
+
+
+def ipa_decide_all_folded(dk, accs, seed=None, verdicts=True):
+    """`decide_all` as one folded check with rho derived from the accumulators -> (all accepted, per-accumulator verdicts
+    or None).  With `verdicts` a rejected batch is decided again one by one to name the culprits."""
+    m = len(accs) // dk.acc_bytes
+    assert len(accs) == m * dk.acc_bytes
+    ok = ctypes.create_string_buffer(max(1, m)) if verdicts else None
+    rc = _check_fold(load_fold_library().snarkv_host_pallas_ipa_decide_all_folded(dk._h, bytes(accs), m, _seed(seed), ok))
+    return rc == 1, ([b != 0 for b in ok.raw[:m]] if verdicts else None)
+
+
+def plonk_verify_folded(protocol, dk, instances, proofs, n, host_threads=0, decompress=DECOMPRESS_AUTO, seed=None):
+    """`plonk_verify` with the folded decide as its second half"""
+    return _check_fold(load_fold_library().snarkv_host_pallas_plonk_verify_folded(
+        protocol._h, dk._h, instances, len(instances), proofs, len(proofs), n, host_threads, decompress, _seed(seed))) == 1
 
 
 def _as_proof_cap(dk):

@@ -164,6 +164,18 @@ class PallasContext:
 
         ipa_batch.commit_batch_dev(self, dk, d_polys, n, m, d_out, slices)
 
+    def ipa_decide_folded(self, dk, xi, u, rho):
+        """`IpaAs::decide_all` as ONE folded check on pallas (`snarkv_pallas_ipa_decide_folded`;
+        include/snarkv_ipa_fold.h).  The caller owns the soundness of `rho`."""
+        from . import ipa_fold
+
+        return ipa_fold.decide_folded(self, dk, xi, u, rho)
+
+    def ipa_fold_coeffs_dev(self, k, xi, rho, d_h, slices=0):
+        from . import ipa_fold
+
+        ipa_fold.fold_coeffs_dev(self, k, xi, rho, d_h, slices)
+
     def ipa_decide_batch(self, dk, xi, u):
         """`IpaAs::decide_all` per accumulator on pallas (pcs/ipa/decider.rs:47-66) -> list of booleans."""
         xi, u = _as_bytes(xi), _as_bytes(u)
