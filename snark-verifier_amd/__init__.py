@@ -40,6 +40,7 @@ from . import ipa_prover  # noqa: F401,E402  (the IPA prover on the device: incl
 from .ipa_prover import IpaProver  # noqa: F401,E402
 from . import ipa_batch  # noqa: F401,E402  (many vectors against one resident IPA key: include/snarkv_ipa_batch.h)
 from . import ipa_fold  # noqa: F401,E402  (decide_all as one folded check: include/snarkv_ipa_fold.h)
+from . import ipa_create  # noqa: F401,E402  (Ipa::create_proof in one call, Blake2b transcript on the device: include/snarkv_ipa_create.h)
 
 __all__ = [
     "host_api",
@@ -47,6 +48,7 @@ __all__ = [
     "ipa_prover",
     "ipa_batch",
     "ipa_fold",
+    "ipa_create",
     "IpaProver",
     "Context",
     "DecidingKey",

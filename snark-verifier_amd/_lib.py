@@ -671,6 +671,13 @@ class Context:
 
         ipa_fold.fold_coeffs_dev(self, k, xi, rho, d_h, slices)
 
+    def ipa_create_proof(self, dk, h, s, p, z, omega=None, p_bar=None, omega_bar=None, absorbed=b""):
+        """`Ipa::create_proof` in one call, halo2's Blake2b transcript on the device (`snarkv_ipa_create_proof`;
+        include/snarkv_ipa_create.h) -> (proof bytes, (xi, U))."""
+        from . import ipa_create
+
+        return ipa_create.create_proof(self, dk, h, s, p, z, omega, p_bar, omega_bar, absorbed)
+
     def ipa_commit_partial_dev(self, dk, xi, d_partial):
         """This shard's part of commit(G, h(xi)) as a projective partial at device address `d_partial`."""
         xi = _as_bytes(xi)

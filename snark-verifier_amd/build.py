@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsnarkv_amd.so")
 UNITS = ["ctx", "msm_api", "capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "ipa_prover", "mgpu",
-         "decompress", "msm_shared", "ipa_fold"]
+         "decompress", "msm_shared", "ipa_fold", "ipa_create"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
@@ -28,6 +28,7 @@ def _deps():
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_prover.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_batch.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_fold.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_create.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
 
@@ -76,7 +77,7 @@ def _link(lib, res, extra):
 
 # The pasta build of the curve-generic units (csrc/pallas.hip explains the flags, csrc/ctx.hpp the policy they select).
 PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover", "decompress_pallas", "msm_shared",
-                "ipa_fold"]
+                "ipa_fold", "ipa_create"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
 
@@ -135,12 +136,15 @@ HOST_PALLAS_LIB = os.path.join(HERE, "libsnarkv_hosttest_pallas.so")  # pasta fl
 HOST_PALLAS_API_LIB = os.path.join(HERE, "libsnarkv_host_pallas.so")  # pasta flavour, product C API (host/capi_pallas.cpp)
 # the folded decide on top of it (host/capi_pallas_fold.cpp, include/snarkv_host_pallas_fold.h)
 HOST_PALLAS_FOLD_LIB = os.path.join(HERE, "libsnarkv_host_pallas_fold.so")
+# Ipa::create_proof in one call on top of it (host/capi_pallas_prove.cpp, include/snarkv_host_pallas_prove.h)
+HOST_PALLAS_PROVE_LIB = os.path.join(HERE, "libsnarkv_host_pallas_prove.so")
 
 
 def _host_stale(out, dev_lib):
     inc = os.path.join(os.path.dirname(HERE), "include")
     srcs = [os.path.join(HOST, f) for f in os.listdir(HOST)] + [os.path.join(inc, h) for h in (
-        "snarkv_host.h", "snarkv_host_pallas.h", "snarkv_pallas_decompress.h", "snarkv_host_pallas_fold.h", "snarkv_ipa_fold.h")]
+        "snarkv_host.h", "snarkv_host_pallas.h", "snarkv_pallas_decompress.h", "snarkv_host_pallas_fold.h", "snarkv_ipa_fold.h",
+        "snarkv_host_pallas_prove.h", "snarkv_ipa_create.h")]
     newest = max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(dev_lib)])
     return not os.path.exists(out) or os.path.getmtime(out) < newest
 
@@ -180,6 +184,8 @@ def build_host_driver():
     # links against the product library built above
     if os.path.exists(HOST_PALLAS_API_LIB) and _host_stale(HOST_PALLAS_FOLD_LIB, HOST_PALLAS_API_LIB):
         _gxx(HOST_PALLAS_FOLD_LIB, "capi_pallas_fold.cpp", pasta, "snarkv_pallas", ["snarkv_host_pallas"])
+    if os.path.exists(HOST_PALLAS_API_LIB) and _host_stale(HOST_PALLAS_PROVE_LIB, HOST_PALLAS_API_LIB):
+        _gxx(HOST_PALLAS_PROVE_LIB, "capi_pallas_prove.cpp", pasta, "snarkv_pallas", ["snarkv_host_pallas"])
     return HOST_LIB
 
 
@@ -196,6 +202,11 @@ def build_host_api_pallas():
 def build_host_api_pallas_fold():
     build_host_driver()
     return HOST_PALLAS_FOLD_LIB
+
+
+def build_host_api_pallas_prove():
+    build_host_driver()
+    return HOST_PALLAS_PROVE_LIB
 
 
 if __name__ == "__main__":

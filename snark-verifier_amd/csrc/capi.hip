@@ -14,6 +14,7 @@
 #include "ctx.hpp"
 #include "../../include/snarkv_ipa_batch.h"
 #include "../../include/snarkv_ipa_fold.h"
+#include "../../include/snarkv_ipa_create.h"
 
 namespace snarkv {
 
@@ -782,6 +783,15 @@ int bn254_ipa_decide_folded(const snarkv_ipa_dk* dk, const uint8_t* xi32, const 
                             const uint8_t rho32[32], int* all_ok) {
   SNARKV_DEFAULT_LEASE(c);
   return snarkv_ipa_decide_folded(c, dk, xi32, u64, m, rho32, all_ok);
+}
+
+int bn254_ipa_create_proof(const snarkv_ipa_dk* dk, const uint8_t h64[64], const uint8_t* s64, const uint8_t* coeffs32, size_t n,
+                           const uint8_t z32[32], const uint8_t* omega32, const uint8_t* pbar32, const uint8_t* omega_bar32,
+                           const uint8_t* absorbed, size_t absorbed_len, uint8_t* proof_out, size_t proof_cap,
+                           size_t* proof_len, uint8_t* xi_out32, uint8_t u_out64[64]) {
+  SNARKV_DEFAULT_LEASE(c);
+  return snarkv_ipa_create_proof(c, dk, h64, s64, coeffs32, n, z32, omega32, pbar32, omega_bar32, absorbed, absorbed_len, proof_out,
+                                 proof_cap, proof_len, xi_out32, u_out64);
 }
 
 int bn254_poseidon_transcript_batch(const snarkv_poseidon* ps, const uint8_t* elems, size_t n, size_t L,

@@ -17,28 +17,11 @@
 #include <algorithm>
 #include <string.h>
 #include <vector>
-#include "ctx.hpp"
-#include "fr29.h"
+#include "ipa_prover.hpp"
 #include "../../include/snarkv_ipa_prover.h"
 #include "../../include/snarkv_ipa_batch.h"
 
 namespace snarkv {
-
-__device__ __forceinline__ Fr29 ld_fr(const uint32_t* __restrict__ p) {
-  const uint4* s = reinterpret_cast<const uint4*>(p);
-  uint4 a = s[0], b = s[1];
-  uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  return fr29_from_canonical(w);
-}
-__device__ __forceinline__ void st_fr(uint32_t* __restrict__ p, const Fr29& v) {
-  uint32_t w[8];
-  fr29_to_canonical(v, w);
-  uint4* o = reinterpret_cast<uint4*>(p);
-  o[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  o[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-// a + b brought back to (-r/8, 9r/8) (one Montgomery product by 1), so sums of any length stay in fr29_mul's range
-__device__ __forceinline__ Fr29 fr_add_red(const Fr29& a, const Fr29& b) { return fr29_mul(fr29_add(a, b), fr29_one()); }
 
 // zs[i] = z^i, i < n (the reference's `powers(*z)`): z^(2^b) in LDS, one product per set bit of i
 __global__ void __launch_bounds__(256) k_ipa_powers(const uint32_t* __restrict__ z_canon, uint32_t k, uint32_t n,
@@ -64,22 +47,7 @@ __global__ void __launch_bounds__(256) k_ipa_powers(const uint32_t* __restrict__
 // xi_pair[8..16) = xi_pair[0..8)^(r-2), on one lane (254 squarings)
 __global__ void k_ipa_xi_inv(uint32_t* __restrict__ xi_pair) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  constexpr uint32_t rw[8] = SNARKV_FR_R_LIMBS;
-  uint32_t e[8];
-  uint32_t borrow = 2;
-  for (int i = 0; i < 8; ++i) {
-    uint32_t v = rw[i];
-    e[i] = v - borrow;
-    borrow = v < borrow ? 1u : 0u;
-  }
-  const Fr29 x = ld_fr(xi_pair);
-  Fr29 acc = fr29_one();
-#pragma unroll 1
-  for (int b = 255; b >= 0; --b) {
-    acc = fr29_mul(acc, acc);
-    if ((e[b >> 5] >> (b & 31)) & 1u) acc = fr29_mul(acc, x);
-  }
-  st_fr(xi_pair + 8, acc);
+  st_fr(xi_pair + 8, fr_inv(ld_fr(xi_pair)));
 }
 
 // coeffs[j] += xi^-1 coeffs[half + j],  zs[j] += xi zs[half + j]   (in place: lane j alone reads half+j and writes j)
@@ -114,9 +82,13 @@ __global__ void __launch_bounds__(256) k_ipa_fold_terms(const uint32_t* __restri
   for (int q = 0; q < 4; ++q) p[4 + q] = b[q];
 }
 
+// the offsets of the base fold's 2-term MSMs: {0, 2, 4, ..., 2 (count - 1)}
+__global__ void __launch_bounds__(256) k_ipa_fold_offsets(uint32_t* __restrict__ foff, uint32_t count) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j < count) foff[j] = 2u * j;
+}
+
 // per-workgroup partial sums of <coeffs[half..], zs[..half]> (L) and <coeffs[..half], zs[half..]> (R)
-constexpr uint32_t kIpThreads = 256;
-constexpr uint32_t kIpMaxBlocks = 512;
 __global__ void __launch_bounds__(kIpThreads) k_ipa_inner2(const uint32_t* __restrict__ coeffs, const uint32_t* __restrict__ zs,
                                                            uint32_t half, Fr29* __restrict__ partials) {
   __shared__ Fr29 sl[kIpThreads], sr[kIpThreads];
@@ -210,7 +182,7 @@ __global__ void __launch_bounds__(256) k_ipa_as_combine(const Fr29* __restrict__
   st_fr(h + 8 * (size_t)j, acc);
 }
 
-static bool host_canonical(const uint8_t* s32) {
+bool host_canonical(const uint8_t* s32) {
   constexpr uint32_t rw[8] = SNARKV_FR_R_LIMBS;
   for (int w = 7; w >= 0; --w) {
     uint32_t v;
@@ -220,8 +192,6 @@ static bool host_canonical(const uint8_t* s32) {
   return false;
 }
 
-// one MSM of n terms on the device: the naive segmented kernels up to SNARKV_IPA_NAIVE_MAX terms, the Pippenger beyond
-// (`d_off01n` = the offsets {0, n} in device memory)
 static size_t naive_max() {
   static const size_t v = [] {
     const char* e = getenv("SNARKV_IPA_NAIVE_MAX");
@@ -229,50 +199,12 @@ static size_t naive_max() {
   }();
   return v;
 }
-static int ipa_msm(snarkv_ctx* ctx, const void* d_s, const void* d_p, size_t n, const void* d_off01n, void* d_out) {
+int ipa_msm(snarkv_ctx* ctx, const void* d_s, const void* d_p, size_t n, const void* d_off01n, void* d_out) {
   if (n <= naive_max()) return launch_msm_batched(ctx, d_s, d_p, d_off01n, 1, n, d_out);
   return launch_msm_pippenger_auto(ctx, d_s, d_p, n, 0, d_out, false);  // the product path of snarkv_g1_msm_pippenger_dev
 }
 
-}  // namespace snarkv
-
-using namespace snarkv;
-
-// layout of a session's small device buffer
-enum : size_t {
-  SM_COMB_S = 0,      // [1, ip_L, 1, ip_R]         4 x 32
-  SM_COMB_P = 128,    // [MSM_L, h', MSM_R, h']     4 x 64
-  SM_COMB_OFF = 384,  // {0, 2, 4}
-  SM_LR = 400,        // L | R out                  128
-  SM_XI = 528,        // xi | xi^-1                 64 (+ 32 spare)
-  SM_Z = 624,         // z                          32
-  SM_OFF1 = 656,      // {0, 1}
-  SM_OFFN = 672,      // {0, 2^b} for b < 32        256
-  SM_BAD = 928,       // SNARKV_FLAG_VALIDATE count
-  SM_PARTIALS = 1024, // kIpMaxBlocks x 2 Fr29
-  SM_BYTES = SM_PARTIALS + kIpMaxBlocks * 2 * sizeof(Fr29),
-};
-
-struct snarkv_ipa_prover {
-  enum State { WANT_ROUND, WANT_FOLD, DONE, FAILED };
-  snarkv_ctx* ctx;
-  uint32_t k;
-  uint32_t rounds;  // rounds completed (folds done)
-  State state;
-  const void* d_key;  // the deciding key's points: read until the first fold
-  void* d_coeffs;     // n x 32
-  void* d_zs;         // n x 32
-  void* d_bases;      // n/2 x 64
-  void* d_ts;         // n/2 x 2 x 32: the base fold's scalars
-  void* d_tp;         // n/2 x 2 x 64: its points
-  void* d_foff;       // n/2 + 1 offsets {0, 2, 4, ...}
-  uint8_t* d_small;
-  uint8_t xi_host[32];
-};
-
-namespace {
-
-void prover_free(snarkv_ipa_prover* p) {
+static void prover_free(snarkv_ipa_prover* p) {
   void* bufs[] = {p->d_coeffs, p->d_zs, p->d_bases, p->d_ts, p->d_tp, p->d_foff, p->d_small};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -297,20 +229,29 @@ int count_bad(snarkv_ctx* ctx, const void* d_s, size_t n, int* d_bad, int* bad) 
   return SNARKV_OK;
 }
 
-int prover_begin(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* coeffs, bool on_device, size_t n,
-                 const uint8_t* z32, const uint8_t* h64, const uint8_t* xi0_32, snarkv_ipa_prover** out) {
-  if (!ctx || !dk || !coeffs || !z32 || !h64 || !xi0_32 || !out) return SNARKV_ERR_ARG;
+void session_free(snarkv_ipa_prover* p) {
+  prover_free(p);
+  delete p;
+}
+
+void session_close(snarkv_ipa_prover* p) {
+  (void)hipSetDevice(p->ctx->device);
+  (void)hipStreamSynchronize(p->ctx->stream);  // enqueued work may still read the buffers
+  session_free(p);
+}
+
+int session_open(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* coeffs, bool on_device, size_t n, const uint8_t* z32,
+                 const uint8_t* h64, const uint8_t* xi0_32, const char* who, snarkv_ipa_prover** out) {
   *out = nullptr;
   if (dk->device != ctx->device) return SNARKV_ERR_ARG;
   if (dk->first != 0 || dk->count != ((size_t)1 << dk->k)) return SNARKV_ERR_LENGTH;  // a shard cannot prove alone
   if (n != dk->count) return SNARKV_ERR_LENGTH;
   const bool validate = (ctx->flags & SNARKV_FLAG_VALIDATE) != 0;
-  if (validate && (!host_canonical(z32) || !host_canonical(xi0_32))) {
-    set_last_error("ipa_prover_begin: z or xi_0 is not canonical");
+  if (validate && (!host_canonical(z32) || (xi0_32 && !host_canonical(xi0_32)))) {
+    set_last_error("%s: z or xi_0 is not canonical", who);
     return SNARKV_ERR_ENCODING;
   }
   SNARKV_HIP(hipSetDevice(ctx->device));
-  SNARKV_WIRE_FORM(ctx);
   snarkv_ipa_prover* p = new snarkv_ipa_prover();
   memset(p, 0, sizeof(*p));
   p->ctx = ctx;
@@ -319,18 +260,16 @@ int prover_begin(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* coeffs, b
   const size_t half = n / 2;
   int rc = SNARKV_OK;
   auto fail = [&](int code) {
-    (void)hipStreamSynchronize(ctx->stream);
-    prover_free(p);
-    delete p;
+    session_close(p);
     return code;
   };
   if ((rc = device_malloc(&p->d_coeffs, n * 32)) || (rc = device_malloc(&p->d_zs, n * 32)) ||
       (rc = device_malloc(&p->d_bases, half * 64)) || (rc = device_malloc((void**)&p->d_small, SM_BYTES)))
     return fail(rc);
-  // the constant part of the small buffer and the base fold's offsets, staged once
+  // the constant part of the small buffer, staged once
   std::vector<uint8_t> st(SM_BAD, 0);
   st[SM_COMB_S] = 1;
-  memcpy(&st[SM_COMB_S + 32], xi0_32, 32);  // slot of ip_L: xi_0 until h' is formed
+  if (xi0_32) memcpy(&st[SM_COMB_S + 32], xi0_32, 32);  // slot of ip_L: xi_0 until h' is formed
   st[SM_COMB_S + 64] = 1;
   memcpy(&st[SM_COMB_P + 64], h64, 64);
   const uint32_t comb_off[3] = {0, 2, 4};
@@ -343,42 +282,46 @@ int prover_begin(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* coeffs, b
     memcpy(&st[SM_OFFN + 8 * b], o, 8);
   }
   hipStream_t s = ctx->stream;
+  // `st` is pageable memory: the copy has left it when hipMemcpyAsync returns
   if (hipMemcpyAsync(p->d_small, st.data(), st.size(), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(p->d_coeffs, coeffs, n * 32, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s) !=
           hipSuccess) {
-    set_last_error("ipa_prover_begin: upload failed");
+    set_last_error("%s: upload failed", who);
     return fail(SNARKV_ERR_DEVICE);
   }
   if (validate) {
     int bad = 0;
     if ((rc = count_bad(ctx, p->d_coeffs, n, (int*)(p->d_small + SM_BAD), &bad))) return fail(rc);
     if (bad) {
-      set_last_error("ipa_prover_begin: %d of %zu coefficients are not canonical", bad, n);
+      set_last_error("%s: %d of %zu coefficients are not canonical", who, bad, n);
       return fail(SNARKV_ERR_ENCODING);
     }
-  }
-  hipLaunchKernelGGL(k_ipa_powers, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s,
-                     (const uint32_t*)(p->d_small + SM_Z), p->k, (uint32_t)n, (uint32_t*)p->d_zs);
-  if (hipGetLastError() != hipSuccess) {
-    set_last_error("ipa_prover_begin: k_ipa_powers launch failed");
-    return fail(SNARKV_ERR_DEVICE);
-  }
-  // h' = xi_0 h (ipa.rs:71), into both h' slots of the L / R combination
-  uint8_t* sm = p->d_small;
-  if ((rc = launch_msm_batched(ctx, sm + SM_COMB_S + 32, sm + SM_COMB_P + 64, sm + SM_OFF1, 1, 1, sm + SM_LR)))
-    return fail(rc);
-  if (hipMemcpyAsync(sm + SM_COMB_P + 64, sm + SM_LR, 64, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(sm + SM_COMB_P + 192, sm + SM_LR, 64, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) {
-    set_last_error("ipa_prover_begin: %s", hipGetErrorString(hipGetLastError()));
-    return fail(SNARKV_ERR_DEVICE);
   }
   p->state = snarkv_ipa_prover::WANT_ROUND;
   *out = p;
   return SNARKV_OK;
 }
 
-int prover_round(snarkv_ipa_prover* p, uint8_t* l64, uint8_t* r64) {
+int session_enqueue_powers(snarkv_ipa_prover* p) {
+  const size_t n = (size_t)1 << p->k;
+  hipLaunchKernelGGL(k_ipa_powers, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, p->ctx->stream,
+                     (const uint32_t*)(p->d_small + SM_Z), p->k, (uint32_t)n, (uint32_t*)p->d_zs);
+  SNARKV_HIP(hipGetLastError());
+  return SNARKV_OK;
+}
+
+// h' = xi_0 h (ipa.rs:71), into both h' slots of the L / R combination
+int session_enqueue_hprime(snarkv_ipa_prover* p) {
+  snarkv_ctx* ctx = p->ctx;
+  SNARKV_WIRE_FORM(ctx);
+  uint8_t* sm = p->d_small;
+  SNARKV_TRY(launch_msm_batched(ctx, sm + SM_COMB_S + 32, sm + SM_COMB_P + 64, sm + SM_OFF1, 1, 1, sm + SM_LR));
+  SNARKV_HIP(hipMemcpyAsync(sm + SM_COMB_P + 64, sm + SM_LR, 64, hipMemcpyDeviceToDevice, ctx->stream));
+  SNARKV_HIP(hipMemcpyAsync(sm + SM_COMB_P + 192, sm + SM_LR, 64, hipMemcpyDeviceToDevice, ctx->stream));
+  return SNARKV_OK;
+}
+
+int session_enqueue_round(snarkv_ipa_prover* p) {
   snarkv_ctx* ctx = p->ctx;
   SNARKV_HIP(hipSetDevice(ctx->device));
   SNARKV_WIRE_FORM(ctx);
@@ -396,9 +339,77 @@ int prover_round(snarkv_ipa_prover* p, uint8_t* l64, uint8_t* r64) {
   const uint8_t* offn = sm + SM_OFFN + 8 * (p->k - p->rounds - 1);
   SNARKV_TRY(ipa_msm(ctx, coeffs + 32 * half, bases, half, offn, sm + SM_COMB_P));       // <coeffs[half..], G[..half]>
   SNARKV_TRY(ipa_msm(ctx, coeffs, bases + 64 * half, half, offn, sm + SM_COMB_P + 128)); // <coeffs[..half], G[half..]>
-  SNARKV_TRY(launch_msm_batched(ctx, sm + SM_COMB_S, sm + SM_COMB_P, sm + SM_COMB_OFF, 2, 4, sm + SM_LR));
+  return launch_msm_batched(ctx, sm + SM_COMB_S, sm + SM_COMB_P, sm + SM_COMB_OFF, 2, 4, sm + SM_LR);
+}
+
+// the staging of the base fold (half 2-term MSMs through the segmented kernels of msm_naive.hip) and its offsets
+int session_fold_staging(snarkv_ipa_prover* p) {
+  if (p->d_ts) return SNARKV_OK;
+  const size_t nh = (size_t)1 << (p->k - 1);
+  SNARKV_TRY(device_malloc(&p->d_ts, nh * 64));
+  SNARKV_TRY(device_malloc(&p->d_tp, nh * 128));
+  SNARKV_TRY(device_malloc(&p->d_foff, (nh + 1) * 4));
+  hipLaunchKernelGGL(k_ipa_fold_offsets, dim3((uint32_t)((nh + 1 + 255) / 256)), dim3(256), 0, p->ctx->stream,
+                     (uint32_t*)p->d_foff, (uint32_t)(nh + 1));
+  SNARKV_HIP(hipGetLastError());
+  return SNARKV_OK;
+}
+
+int session_enqueue_fold(snarkv_ipa_prover* p) {
+  snarkv_ctx* ctx = p->ctx;
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  SNARKV_WIRE_FORM(ctx);
+  const size_t half = (size_t)1 << (p->k - p->rounds - 1);
+  const uint8_t* bases = (const uint8_t*)(p->rounds == 0 ? p->d_key : p->d_bases);
+  uint8_t* sm = p->d_small;
+  hipStream_t s = ctx->stream;
+  const uint32_t grid = (uint32_t)((half + 255) / 256);
+  hipLaunchKernelGGL(k_ipa_fold_scalars, dim3(grid), dim3(256), 0, s, (uint32_t*)p->d_coeffs, (uint32_t*)p->d_zs,
+                     (uint32_t)half, (const uint32_t*)(sm + SM_XI));
+  SNARKV_TRY(session_fold_staging(p));
+  hipLaunchKernelGGL(k_ipa_fold_terms, dim3(grid), dim3(256), 0, s, (const uint32_t*)bases, (uint32_t)half,
+                     (const uint32_t*)(sm + SM_XI), (uint32_t*)p->d_ts, (uint32_t*)p->d_tp);
+  SNARKV_HIP(hipGetLastError());
+  return launch_msm_batched(ctx, p->d_ts, p->d_tp, p->d_foff, half, 2 * half, p->d_bases);
+}
+
+int ipa_enqueue_commit(snarkv_ctx* ctx, const void* d_points, const void* d_s, size_t n, const void* d_off0n, void* d_pts2,
+                       const void* d_sc2, const void* d_off02, void* d_out, bool blind) {
+  SNARKV_TRY(ipa_msm(ctx, d_s, d_points, n, d_off0n, blind ? d_pts2 : d_out));
+  if (blind) SNARKV_TRY(launch_msm_batched(ctx, d_sc2, d_pts2, d_off02, 1, 2, d_out));
+  return SNARKV_OK;
+}
+
+}  // namespace snarkv
+
+using namespace snarkv;
+
+namespace {
+
+int prover_begin(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* coeffs, bool on_device, size_t n,
+                 const uint8_t* z32, const uint8_t* h64, const uint8_t* xi0_32, snarkv_ipa_prover** out) {
+  if (!ctx || !dk || !coeffs || !z32 || !h64 || !xi0_32 || !out) return SNARKV_ERR_ARG;
+  snarkv_ipa_prover* p = nullptr;
+  SNARKV_TRY(session_open(ctx, dk, coeffs, on_device, n, z32, h64, xi0_32, "ipa_prover_begin", &p));
+  int rc = SNARKV_OK;
+  if ((rc = session_enqueue_powers(p)) || (rc = session_enqueue_hprime(p))) {
+    session_close(p);
+    return rc;
+  }
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
+    set_last_error("ipa_prover_begin: %s", hipGetErrorString(hipGetLastError()));
+    session_close(p);
+    return SNARKV_ERR_DEVICE;
+  }
+  *out = p;
+  return SNARKV_OK;
+}
+
+int prover_round(snarkv_ipa_prover* p, uint8_t* l64, uint8_t* r64) {
+  SNARKV_TRY(session_enqueue_round(p));
+  hipStream_t s = p->ctx->stream;
   uint8_t lr[128];
-  SNARKV_HIP(hipMemcpyAsync(lr, sm + SM_LR, 128, hipMemcpyDeviceToHost, s));
+  SNARKV_HIP(hipMemcpyAsync(lr, p->d_small + SM_LR, 128, hipMemcpyDeviceToHost, s));
   SNARKV_HIP(hipStreamSynchronize(s));
   memcpy(l64, lr, 64);
   memcpy(r64, lr + 64, 64);
@@ -408,31 +419,11 @@ int prover_round(snarkv_ipa_prover* p, uint8_t* l64, uint8_t* r64) {
 int prover_fold(snarkv_ipa_prover* p) {
   snarkv_ctx* ctx = p->ctx;
   SNARKV_HIP(hipSetDevice(ctx->device));
-  SNARKV_WIRE_FORM(ctx);
-  const size_t half = (size_t)1 << (p->k - p->rounds - 1);
-  const uint8_t* bases = (const uint8_t*)(p->rounds == 0 ? p->d_key : p->d_bases);
   uint8_t* sm = p->d_small;
   hipStream_t s = ctx->stream;
-  const uint32_t grid = (uint32_t)((half + 255) / 256);
   SNARKV_HIP(hipMemcpyAsync(sm + SM_XI, p->xi_host, 32, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_ipa_xi_inv, dim3(1), dim3(64), 0, s, (uint32_t*)(sm + SM_XI));
-  hipLaunchKernelGGL(k_ipa_fold_scalars, dim3(grid), dim3(256), 0, s, (uint32_t*)p->d_coeffs, (uint32_t*)p->d_zs,
-                     (uint32_t)half, (const uint32_t*)(sm + SM_XI));
-  // the base fold: half 2-term MSMs through the segmented kernels of msm_naive.hip (staging allocated on first use)
-  if (!p->d_ts) {
-    const size_t nh = (size_t)1 << (p->k - 1);
-    SNARKV_TRY(device_malloc(&p->d_ts, nh * 64));
-    SNARKV_TRY(device_malloc(&p->d_tp, nh * 128));
-    SNARKV_TRY(device_malloc(&p->d_foff, (nh + 1) * 4));
-    std::vector<uint32_t> foff(nh + 1);
-    for (size_t j = 0; j <= nh; ++j) foff[j] = (uint32_t)(2 * j);
-    SNARKV_HIP(hipMemcpyAsync(p->d_foff, foff.data(), foff.size() * 4, hipMemcpyHostToDevice, s));
-    SNARKV_HIP(hipStreamSynchronize(s));
-  }
-  hipLaunchKernelGGL(k_ipa_fold_terms, dim3(grid), dim3(256), 0, s, (const uint32_t*)bases, (uint32_t)half,
-                     (const uint32_t*)(sm + SM_XI), (uint32_t*)p->d_ts, (uint32_t*)p->d_tp);
-  SNARKV_HIP(hipGetLastError());
-  SNARKV_TRY(launch_msm_batched(ctx, p->d_ts, p->d_tp, p->d_foff, half, 2 * half, p->d_bases));
+  SNARKV_TRY(session_enqueue_fold(p));
   if (p->rounds == 0) {
     SNARKV_HIP(hipStreamSynchronize(s));  // the key is no longer read: the caller may destroy it
     p->d_key = nullptr;
@@ -484,8 +475,7 @@ int SNARKV_API(ipa_commit)(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const uint8
       return SNARKV_ERR_ENCODING;
     }
   }
-  SNARKV_TRY(ipa_msm(ctx, d_s, dk->d_points, n, sm + 200, omega32 ? sm : sm + 256));
-  if (omega32) SNARKV_TRY(launch_msm_batched(ctx, sm + 128, sm, sm + 192, 1, 2, sm + 256));
+  SNARKV_TRY(ipa_enqueue_commit(ctx, dk->d_points, d_s, n, sm + 200, sm, sm + 128, sm + 192, sm + 256, omega32 != nullptr));
   SNARKV_HIP(hipMemcpyAsync(out64, sm + 256, 64, hipMemcpyDeviceToHost, ctx->stream));
   SNARKV_HIP(hipStreamSynchronize(ctx->stream));
   return SNARKV_OK;
@@ -623,10 +613,7 @@ int SNARKV_API(ipa_prover_finish)(snarkv_ipa_prover* p, uint8_t u64[64], uint8_t
 
 void SNARKV_API(ipa_prover_destroy)(snarkv_ipa_prover* p) {
   if (!p) return;
-  (void)hipSetDevice(p->ctx->device);
-  (void)hipStreamSynchronize(p->ctx->stream);  // enqueued folds may still read the buffers
-  prover_free(p);
-  delete p;
+  session_close(p);  // waits: enqueued folds may still read the buffers
 }
 
 int SNARKV_API(ipa_as_combine_dev)(snarkv_ctx* ctx, const uint8_t* xi32, size_t m, uint32_t k, const uint8_t alpha32[32],

@@ -19,6 +19,7 @@
 #include "ctx.hpp"
 #include "../../include/snarkv_ipa_batch.h"
 #include "../../include/snarkv_ipa_fold.h"
+#include "../../include/snarkv_ipa_create.h"
 #include "../../include/snarkv_pallas.h"
 #include "../../include/snarkv_pallas_decompress.h"
 
@@ -105,6 +106,14 @@ int pallas_ipa_decide_folded(const snarkv_ipa_dk* dk, const uint8_t* xi32, const
                              const uint8_t rho32[32], int* all_ok) {
   PALLAS_DEFAULT_CTX();
   return snarkv_pallas_ipa_decide_folded(c, dk, xi32, u64, m, rho32, all_ok);
+}
+int pallas_ipa_create_proof(const snarkv_ipa_dk* dk, const uint8_t h64[64], const uint8_t* s64, const uint8_t* coeffs32, size_t n,
+                           const uint8_t z32[32], const uint8_t* omega32, const uint8_t* pbar32, const uint8_t* omega_bar32,
+                           const uint8_t* absorbed, size_t absorbed_len, uint8_t* proof_out, size_t proof_cap,
+                           size_t* proof_len, uint8_t* xi_out32, uint8_t u_out64[64]) {
+  PALLAS_DEFAULT_CTX();
+  return snarkv_pallas_ipa_create_proof(c, dk, h64, s64, coeffs32, n, z32, omega32, pbar32, omega_bar32, absorbed, absorbed_len, proof_out,
+                                 proof_cap, proof_len, xi_out32, u_out64);
 }
 int pallas_g1_decompress(const uint8_t* in32, size_t n, uint8_t* out64, uint8_t* ok) {
   PALLAS_DEFAULT_CTX();

@@ -58,8 +58,16 @@ _FOLD_SIGNATURES = {
     "snarkv_host_pallas_plonk_verify_folded": (_int, [_vp, _vp, _cp, _sz, _cp, _sz, _u32, _uint, _int, _cp]),
 }
 
+# name -> (restype, argtypes); every function include/snarkv_host_pallas_prove.h declares (libsnarkv_host_pallas_prove.so)
+_PROVE_LIB_NAME = "libsnarkv_host_pallas_prove.so"
+_PROVE_SIGNATURES = {
+    "snarkv_host_pallas_prove_last_error": (_cp, []),
+    "snarkv_host_pallas_ipa_create_proof": (_int, [_vp, _cp, _sz, _cp, _cp, _cp, _cp, _cp, _sz, _vp, _sz, _psz, _vp]),
+}
+
 _lib = None
 _fold_lib = None
+_prove_lib = None
 
 
 def lib_path():
@@ -102,6 +110,26 @@ def load_fold_library():
             fn.restype, fn.argtypes = res, args
         _fold_lib = L
     return _fold_lib
+
+
+def prove_lib_path():
+    return os.environ.get("SNARKV_HOST_PALLAS_PROVE_LIB") or os.path.join(HERE, _PROVE_LIB_NAME)
+
+
+def load_prove_library():
+    """Loads libsnarkv_host_pallas_prove.so (which binds libsnarkv_host_pallas.so and libsnarkv_pallas.so next to it)."""
+    global _prove_lib
+    if _prove_lib is None:
+        path = prove_lib_path()
+        if not os.path.exists(path):
+            raise HostError(ERR_DEVICE, "%s not built (run `python __graft_entry__.py`)" % path)
+        load_library()
+        L = ctypes.CDLL(path)
+        for name, (res, args) in _PROVE_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
+        _prove_lib = L
+    return _prove_lib
 
 
 def _check_fold(rc):
@@ -213,6 +241,22 @@ def plonk_verify_folded(protocol, dk, instances, proofs, n, host_threads=0, deco
     """`plonk_verify` with the folded decide as its second half"""
     return _check_fold(load_fold_library().snarkv_host_pallas_plonk_verify_folded(
         protocol._h, dk._h, instances, len(instances), proofs, len(proofs), n, host_threads, decompress, _seed(seed))) == 1
+
+
+def ipa_create_proof(dk, poly, z, omega=None, p_bar=None, omega_bar=None, absorbed=b""):
+    """`Ipa::create_proof` in one call, halo2's Blake2b transcript on the device -> (proof bytes, accumulator bytes).
+    `poly` (and `p_bar`) = 2^k scalars packed 32 bytes each, `z`, `omega`, `omega_bar` 32 bytes; a zero-knowledge key
+    takes omega, p_bar and omega_bar, any other key none of them.  `absorbed`: what the transcript's hasher took so far."""
+    L = load_prove_library()
+    cap = 64 * dk.k + 128
+    proof, ln, acc = ctypes.create_string_buffer(cap), ctypes.c_size_t(0), ctypes.create_string_buffer(dk.acc_bytes)
+    opt = lambda v: None if v is None else bytes(v)  # noqa: E731
+    rc = L.snarkv_host_pallas_ipa_create_proof(dk._h, bytes(poly), len(poly) // 32, bytes(z), opt(omega), opt(p_bar),
+                                               opt(omega_bar), bytes(absorbed) or None, len(absorbed), proof, cap,
+                                               ctypes.byref(ln), acc)
+    if rc < 0:
+        raise HostError(rc, (L.snarkv_host_pallas_prove_last_error() or b"").decode(errors="replace"))
+    return proof.raw[:ln.value], acc.raw
 
 
 def _as_proof_cap(dk):

@@ -176,6 +176,13 @@ class PallasContext:
 
         ipa_fold.fold_coeffs_dev(self, k, xi, rho, d_h, slices)
 
+    def ipa_create_proof(self, dk, h, s, p, z, omega=None, p_bar=None, omega_bar=None, absorbed=b""):
+        """`Ipa::create_proof` in one call, halo2's Blake2b transcript on the device (`snarkv_pallas_ipa_create_proof`;
+        include/snarkv_ipa_create.h) -> (proof bytes, (xi, U))."""
+        from . import ipa_create
+
+        return ipa_create.create_proof(self, dk, h, s, p, z, omega, p_bar, omega_bar, absorbed)
+
     def ipa_decide_batch(self, dk, xi, u):
         """`IpaAs::decide_all` per accumulator on pallas (pcs/ipa/decider.rs:47-66) -> list of booleans."""
         xi, u = _as_bytes(xi), _as_bytes(u)
