@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsnarkv_amd.so")
 UNITS = ["ctx", "msm_api", "capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "ipa_prover", "mgpu",
-         "decompress", "msm_shared", "ipa_fold", "ipa_create"]
+         "decompress", "msm_shared", "ipa_fold", "ipa_create", "poly", "ipa_multiopen"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
@@ -29,6 +29,8 @@ def _deps():
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_batch.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_fold.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_create.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_poly.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_multiopen.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
 
@@ -57,6 +59,7 @@ def build(verbose=False):
     with ThreadPoolExecutor(max_workers=min(len(jobs) + len(DEVTEST_FLAVOURS), os.cpu_count() or 4)) as ex:
         devtest = [ex.submit(build_devtest, f) for f in DEVTEST_FLAVOURS]  # the test-only device units ride in the same pool
         devtest += [ex.submit(build_hosttest_curve, c) for c in ("bn254", "pallas")]
+        devtest += [ex.submit(build_hosttest_poly, c) for c in ("bn254", "pallas")]
         res = list(ex.map(lambda j: _compile(j[0], verbose, j[1], j[2]), jobs))
         for d in devtest:
             d.result()
@@ -77,7 +80,7 @@ def _link(lib, res, extra):
 
 # The pasta build of the curve-generic units (csrc/pallas.hip explains the flags, csrc/ctx.hpp the policy they select).
 PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover", "decompress_pallas", "msm_shared",
-                "ipa_fold", "ipa_create"]
+                "ipa_fold", "ipa_create", "poly", "ipa_multiopen"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
 
@@ -109,6 +112,21 @@ def build_hosttest_curve(curve):
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)
         raise RuntimeError("host build failed: hosttest_curve.cpp (%s)" % curve)
+    return out
+
+
+# The blocked scan of the polynomial division (csrc/poly_scan.h) and the multi-open prover's query-set grouping
+# (csrc/ipa_multiopen_sets.h) for the host (tests/hosttest/hosttest_poly.cpp), one library per curve.
+def build_hosttest_poly(curve):
+    out = os.path.join(HOSTTEST_DIR, "libhosttest_poly_%s.so" % curve)
+    src = os.path.join(HOSTTEST_DIR, "hosttest_poly.cpp")
+    if os.path.exists(out) and os.path.getmtime(out) >= max(_deps(), os.path.getmtime(src)):
+        return out
+    flags = ["-DSNARKV_CURVE_PALLAS"] if curve == "pallas" else []
+    r = subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC"] + flags + ["-o", out, src], capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout + r.stderr)
+        raise RuntimeError("host build failed: hosttest_poly.cpp (%s)" % curve)
     return out
 
 

@@ -78,6 +78,7 @@ enum Slot {
   SLOT_MGPU_GRID,
   SLOT_MGPU_RECV,
   SLOT_IPA_FOLD,     // the folded decide (ipa_fold.hip): challenges and powers in the Montgomery domain, partial vectors
+  SLOT_POLY,         // the polynomial calls (poly.hip): the roots and totals of the scan's levels, a staged pass of terms
   SLOT_COUNT
 };
 

@@ -1,0 +1,561 @@
+// The Bgh19 multi-open prover in one call (include/snarkv_ipa_multiopen.h), step by step as oracle/ipa.py::bgh19_create_proof:
+//   host    grouping (ipa_multiopen_sets.h), x_1, x_2, per set the blind, the points x shift and the interpolation r of the
+//           combined evaluations -- a handful of scalars each
+//   device  per set  q = sum x_1^j polys[..]              poly_enqueue_lincomb
+//                    f_i = (q - r) / prod (X - point)       k_mo_sub_low + poly_enqueue_div_linear per point, ping-pong;
+//                                                           a remainder marks the set in the status word (k_mo_check_rem)
+//           f = sum x_2^j f_i, commit(f, f_blind)           poly_enqueue_lincomb + ipa_enqueue_commit     -> sync 1: f, status
+//   host    writes f, squeezes x_3
+//   device  q_i(x_3), f(x_3)                                poly_enqueue_eval                              -> sync 2: S + 1 scalars
+//   host    writes the q_i(x_3), squeezes x_4, forms omega and p(x_3)'s correction
+//   device  p = x_4^S f + sum x_4^(S-i) q_i, p[0] -= ...    poly_enqueue_lincomb + k_mo_sub_low
+//           the zk opening of p at x_3 in Bgh19's order: p_bar[0] -= p_bar(x_3), s = commit(p_bar, omega_bar),
+//           k_mo_transcript_s (writes s, squeezes alpha, then xi_0), p' = p + alpha p_bar, k rounds of the session with
+//           k_ipa_transcript_round, k_mo_transcript_finish (writes c, omega', U)                            -> sync 3: the proof
+// The session (ipa_prover.hip) and the kernels of ipa_create.hip run unchanged; only the two transcript kernels around the
+// rounds differ from `Ipa::create_proof`, which writes omega' before xi_0 and U before c.
+#include <string.h>
+#include <algorithm>
+#include <vector>
+#include "blake2b_dev.h"
+#include "ipa_multiopen_sets.h"
+#include "ipa_prover.hpp"
+#include "poly.hpp"
+#include "../../include/snarkv_ipa_multiopen.h"
+
+namespace snarkv {
+
+// layout of the call's device buffer; the host stages [0, MO_STAGED) and the variable part behind MO_VAR
+enum : size_t {
+  MO_STATE = 0,       // Blake2bState, uploaded after x_4
+  MO_STATUS = 256,    // kMo* bits | the first set whose division left a remainder (0xffffffff: none)
+  MO_U = 272,         // U                                   64
+  MO_XI = 336,        // xi_1..xi_k                          32 x 32
+  MO_PROOF = 1360,    // s | k x (L | R) | c | omega' | U    64 x 32 + 128
+  MO_ALPHA = 3584,    // alpha                               32
+  MO_OMEGA = 3616,    // omega | omega_bar                   64, uploaded after x_4
+  MO_SC2F = 3680,     // [1, f_blind]                        64
+  MO_SC2S = 3744,     // [1, omega_bar]                      64
+  MO_PTS2 = 3808,     // [the MSM of a commitment, s]        128
+  MO_OFF02 = 3936,    // {0, 2}
+  MO_OFF0N = 3944,    // {0, n}
+  MO_COMMIT = 3968,   // the commitment of f, then s         64
+  MO_POINT = 4032,    // x_3                                 32
+  MO_DELTA = 4064,    // what p[0] is lowered by             32
+  MO_STAGED = 4096,
+  MO_PARTIALS = 4096, // kIpMaxBlocks Fr29
+  MO_VAR = MO_PARTIALS + ((kIpMaxBlocks * sizeof(Fr29) + 31) / 32) * 32,
+};
+static_assert(sizeof(Blake2bState) <= MO_STATUS - MO_STATE, "the transcript state has 256 bytes");
+constexpr uint32_t kMoRoundInf = 1, kMoUInf = 2, kMoSInf = 4;  // kMoRoundInf is what k_ipa_transcript_round sets
+
+__device__ __forceinline__ void mo_st_words(uint32_t* __restrict__ p, const uint32_t (&w)[8]) {
+  uint4* o = reinterpret_cast<uint4*>(p);
+  o[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+
+// poly[j] -= sub[j], j < m
+__global__ void __launch_bounds__(64) k_mo_sub_low(uint32_t* __restrict__ poly, const uint32_t* __restrict__ sub, uint32_t m) {
+#pragma unroll 1
+  for (uint32_t j = threadIdx.x; j < m; j += 64) {
+    const Fr29 a = ld_fr(poly + 8 * (size_t)j), b = ld_fr(sub + 8 * (size_t)j);
+    Fr29 d;  // (-r/2, 3r/2) minus the same: within fr29_to_canonical's 8 r
+#pragma unroll
+    for (int i = 0; i < 9; ++i) d.v[i] = a.v[i] - b.v[i];
+    st_fr(poly + 8 * (size_t)j, d);
+  }
+}
+
+// a remainder (canonical) that is not zero marks its set; the pipeline runs on
+__global__ void __launch_bounds__(64) k_mo_check_rem(const uint32_t* __restrict__ rem, uint32_t set, uint32_t* __restrict__ first_bad) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  uint32_t any = 0;
+  for (int w = 0; w < 8; ++w) any |= rem[w];
+  if (any) atomicMin(first_bad, set);
+}
+
+// Bgh19's order before the rounds: writes s, squeezes alpha (canonical to alpha_out), squeezes xi_0 into the slot the
+// session's h' = xi_0 h reads.  Two passes through the one absorbing site.
+__global__ void __launch_bounds__(64) k_mo_transcript_s(const uint8_t* __restrict__ s64, Blake2bState* __restrict__ st,
+                                                        uint8_t* __restrict__ proof32, uint32_t* __restrict__ alpha_out,
+                                                        uint32_t* __restrict__ xi0_out, uint32_t* __restrict__ status) {
+  __shared__ uint8_t msg[kTrPointBytes + 2 * kTrSqueezeBytes];
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (!tr_put_point(msg, s64, s64 + 32)) *status |= kMoSInf;
+  tr_put_squeeze(msg + kTrPointBytes);
+  tr_put_squeeze(msg + kTrPointBytes + kTrSqueezeBytes);
+  tr_compress_point(s64, s64 + 32, proof32);
+  const uint8_t* part = msg;
+  size_t part_len = kTrPointBytes + kTrSqueezeBytes;
+  uint32_t* out = alpha_out;
+#pragma unroll 1
+  for (int pass = 0; pass < 2; ++pass) {
+    b2b_update(*st, part, part_len);
+    uint32_t w[8];
+    (void)tr_challenge(*st, w);
+    mo_st_words(out, w);
+    part = msg + kTrPointBytes + kTrSqueezeBytes;
+    part_len = kTrSqueezeBytes;
+    out = xi0_out;
+  }
+}
+
+// ... and after them: writes c = the last coefficient, omega' = omega + alpha omega_bar, U = the last base; U also to u_out
+__global__ void __launch_bounds__(64) k_mo_transcript_finish(const uint8_t* __restrict__ u, const uint8_t* __restrict__ c,
+                                                             const uint32_t* __restrict__ omegas,
+                                                             const uint32_t* __restrict__ alpha, Blake2bState* __restrict__ st,
+                                                             uint8_t* __restrict__ proof128, uint8_t* __restrict__ u_out,
+                                                             uint32_t* __restrict__ status) {
+  __shared__ uint8_t msg[2 * kTrScalarBytes + kTrPointBytes];
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  tr_put_scalar(msg, c);
+  const Fr29 op = fr29_add(ld_fr(omegas), fr29_mul(ld_fr(alpha), ld_fr(omegas + 8)));
+  uint32_t w[8];
+  fr29_to_canonical(op, w);
+  uint8_t* sc = msg + kTrScalarBytes;
+  sc[0] = 0x02;
+  for (int i = 0; i < 32; ++i) {
+    const uint8_t b = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+    sc[1 + i] = b;
+    proof128[32 + i] = b;
+  }
+  if (!tr_put_point(msg + 2 * kTrScalarBytes, u, u + 32)) *status |= kMoUInf;
+  for (int i = 0; i < 32; ++i) proof128[i] = c[i];
+  tr_compress_point(u, u + 32, proof128 + 64);
+  for (int i = 0; i < 64; ++i) u_out[i] = u[i];
+  b2b_update(*st, msg, sizeof(msg));
+}
+
+namespace {
+
+// ---- the host's few scalars: Fr29 in the Montgomery domain, every result brought back to (-r/8, 9r/8) ----------------------
+Fr29 h_red(const Fr29& x) { return fr29_mul(fr29_norm(x), fr29_one()); }
+Fr29 h_load(const uint8_t* b32) {
+  uint32_t w[8];
+  memcpy(w, b32, 32);
+  return h_red(fr29_from_canonical(w));
+}
+void h_store(uint8_t* b32, const Fr29& v) {
+  uint32_t w[8];
+  fr29_to_canonical(v, w);
+  memcpy(b32, w, 32);
+}
+Fr29 h_add(const Fr29& a, const Fr29& b) { return h_red(fr29_add(a, b)); }
+Fr29 h_sub(const Fr29& a, const Fr29& b) {
+  Fr29 d;
+  for (int i = 0; i < 9; ++i) d.v[i] = a.v[i] - b.v[i];
+  return h_red(d);
+}
+Fr29 h_mul(const Fr29& a, const Fr29& b) { return h_red(fr29_mul(a, b)); }
+bool h_is_zero(const Fr29& v) {
+  uint8_t b[32];
+  h_store(b, v);
+  for (int i = 0; i < 32; ++i)
+    if (b[i]) return false;
+  return true;
+}
+Fr29 h_inv(const Fr29& x) {  // x^(r-2)
+  constexpr uint32_t rw[8] = SNARKV_FR_R_LIMBS;
+  uint32_t e[8], borrow = 2;
+  for (int i = 0; i < 8; ++i) {
+    e[i] = rw[i] - borrow;
+    borrow = rw[i] < borrow ? 1u : 0u;
+  }
+  Fr29 acc = fr29_one();
+  for (int b = 255; b >= 0; --b) {
+    acc = h_mul(acc, acc);
+    if ((e[b >> 5] >> (b & 31)) & 1u) acc = h_mul(acc, x);
+  }
+  return acc;
+}
+std::vector<Fr29> h_powers(const Fr29& x, size_t count) {
+  std::vector<Fr29> out(count, fr29_one());
+  for (size_t i = 1; i < count; ++i) out[i] = h_mul(out[i - 1], x);
+  return out;
+}
+Fr29 h_squeeze(Blake2bState& st, uint8_t* canon32_or_null) {
+  uint32_t w[8];
+  const Fr29 c = h_red(tr_squeeze(st, w));
+  if (canon32_or_null) memcpy(canon32_or_null, w, 32);
+  return c;
+}
+
+// the coefficients of the polynomial of degree < m through (pts[j], vals[j]); false when two points coincide
+bool h_interpolate(const std::vector<Fr29>& pts, const std::vector<Fr29>& vals, std::vector<Fr29>& out) {
+  const size_t m = pts.size();
+  out.assign(m, fr29_zero());
+  for (size_t j = 0; j < m; ++j) {
+    std::vector<Fr29> num(1, fr29_one());
+    Fr29 den = fr29_one();
+    for (size_t i = 0; i < m; ++i) {
+      if (i == j) continue;
+      std::vector<Fr29> next(num.size() + 1, fr29_zero());  // num (X - p_i)
+      for (size_t t = 0; t < num.size(); ++t) {
+        next[t + 1] = h_add(next[t + 1], num[t]);
+        next[t] = h_sub(next[t], h_mul(pts[i], num[t]));
+      }
+      num.swap(next);
+      den = h_mul(den, h_sub(pts[j], pts[i]));
+    }
+    if (h_is_zero(den)) return false;
+    const Fr29 f = h_mul(vals[j], h_inv(den));
+    for (size_t t = 0; t < m; ++t) out[t] = h_add(out[t], h_mul(num[t], f));
+  }
+  return true;
+}
+
+struct MoArgs {
+  const uint8_t *h64, *s64, *blinds32, *x32, *q_shift32, *q_eval32, *f_blind32, *omega_bar32, *absorbed;
+  const uint32_t* q_poly;
+  const void *polys, *pbar;
+  bool on_device;
+  size_t n, n_polys, n_queries, absorbed_len;
+};
+
+// what the host works out per set before any device work
+struct SetPlan {
+  std::vector<uint32_t> idx;     // the polynomials, reversed: the term of x_1^j
+  std::vector<uint8_t> scalars;  // x_1^j, canonical
+  Fr29 blind;
+  size_t first_point;            // where its points, remainders and r lie in the variable part
+  size_t m;
+};
+
+// device buffers of one call; freed when the call leaves, after the stream has drained
+struct Buffers {
+  hipStream_t stream;
+  std::vector<void*> all;
+  explicit Buffers(hipStream_t s) : stream(s) {}
+  int get(void** out, size_t bytes) {
+    SNARKV_TRY(device_malloc(out, bytes));
+    all.push_back(*out);
+    return SNARKV_OK;
+  }
+  ~Buffers() {
+    if (all.empty()) return;
+    (void)hipStreamSynchronize(stream);  // a failure may have left work in flight
+    for (void* b : all) (void)hipFree(b);
+  }
+};
+
+const char kInfinityText[] = "ipa_multiopen_create_proof: cannot write points at infinity to the transcript (%s)";
+
+int multiopen_run(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const MoArgs& a, const std::vector<MultiopenSet>& sets, size_t need,
+                  uint8_t* proof_out, uint8_t* xi_out32, uint8_t* u_out64) {
+  const size_t n = a.n, S = sets.size();
+  const uint32_t k = dk->k;
+  const bool validate = (ctx->flags & SNARKV_FLAG_VALIDATE) != 0;
+  hipStream_t s = ctx->stream;
+  SNARKV_WIRE_FORM(ctx);
+
+  // ---- host: x_1, x_2 and the plan of every set ---------------------------------------------------------------------------
+  Blake2bState ts;
+  tr_init(ts);
+  b2b_update(ts, a.absorbed, a.absorbed_len);
+  const Fr29 x1 = h_squeeze(ts, nullptr), x2 = h_squeeze(ts, nullptr);
+  const Fr29 x = h_load(a.x32);
+  size_t total_points = 0, most_polys = 0;
+  for (const MultiopenSet& st : sets) {
+    total_points += st.shifts.size();
+    most_polys = std::max(most_polys, st.polys.size());
+    if (st.shifts.size() > n) {
+      set_last_error("ipa_multiopen_create_proof: a polynomial is queried at %zu points, it has %zu coefficients", st.shifts.size(), n);
+      return SNARKV_ERR_ARG;
+    }
+  }
+  // the variable part of the device buffer: points | remainders | r | evaluations at x_3
+  const size_t var_pts = MO_VAR, var_rem = var_pts + 32 * total_points, var_r = var_rem + 32 * total_points,
+               var_ev = var_r + 32 * total_points, mo_bytes = var_ev + 32 * (S + 1);
+  std::vector<uint8_t> stage(mo_bytes, 0);
+  const std::vector<Fr29> px1 = h_powers(x1, most_polys);
+  std::vector<SetPlan> plan(S);
+  size_t at = 0;
+  for (size_t i = 0; i < S; ++i) {
+    const MultiopenSet& st = sets[i];
+    SetPlan& pl = plan[i];
+    const size_t np = st.polys.size(), m = st.shifts.size();
+    pl.m = m;
+    pl.first_point = at;
+    pl.blind = fr29_zero();
+    pl.scalars.resize(32 * np);
+    std::vector<Fr29> pts(m), vals(m, fr29_zero()), r;
+    for (size_t t = 0; t < m; ++t) pts[t] = h_mul(x, h_load(a.q_shift32 + 32 * st.shifts[t]));
+    for (size_t j = 0; j < np; ++j) {  // QuerySet::msm order: polys reversed against ascending powers of x_1
+      const size_t which = np - 1 - j;
+      pl.idx.push_back(st.polys[which]);
+      h_store(&pl.scalars[32 * j], px1[j]);
+      pl.blind = h_add(pl.blind, h_mul(px1[j], h_load(a.blinds32 + 32 * (size_t)st.polys[which])));
+      for (size_t t = 0; t < m; ++t) vals[t] = h_add(vals[t], h_mul(px1[j], h_load(a.q_eval32 + 32 * st.evals[which][t])));
+    }
+    if (!h_interpolate(pts, vals, r)) {
+      set_last_error("ipa_multiopen_create_proof: two points of query set %zu coincide", i);
+      return SNARKV_ERR_ARG;
+    }
+    for (size_t t = 0; t < m; ++t) {
+      h_store(&stage[var_pts + 32 * (at + t)], pts[t]);
+      h_store(&stage[var_r + 32 * (at + t)], r[t]);
+    }
+    at += m;
+  }
+  const uint32_t none = 0xffffffffu, off02[2] = {0, 2}, off0n[2] = {0, (uint32_t)n};
+  memcpy(&stage[MO_STATUS + 4], &none, 4);
+  stage[MO_SC2F] = 1;
+  memcpy(&stage[MO_SC2F + 32], a.f_blind32, 32);
+  stage[MO_SC2S] = 1;
+  memcpy(&stage[MO_SC2S + 32], a.omega_bar32, 32);
+  memcpy(&stage[MO_PTS2 + 64], a.s64, 64);
+  memcpy(&stage[MO_OFF02], off02, sizeof(off02));
+  memcpy(&stage[MO_OFF0N], off0n, sizeof(off0n));
+
+  // ---- device buffers: the polynomials (host form), q_1..q_S | f, f_1..f_S, two work polynomials, p_bar ------------------
+  Buffers bufs(s);
+  void *d_mo_, *d_polys_ = nullptr, *d_q_, *d_f_, *d_t_, *d_pbar_;
+  SNARKV_TRY(bufs.get(&d_mo_, mo_bytes));
+  if (!a.on_device) SNARKV_TRY(bufs.get(&d_polys_, 32 * n * a.n_polys));
+  SNARKV_TRY(bufs.get(&d_q_, 32 * n * (S + 1)));
+  SNARKV_TRY(bufs.get(&d_f_, 32 * n * S));
+  SNARKV_TRY(bufs.get(&d_t_, 32 * n * 2));
+  SNARKV_TRY(bufs.get(&d_pbar_, 32 * n));
+  uint8_t *mo = (uint8_t*)d_mo_, *d_q = (uint8_t*)d_q_, *d_f = (uint8_t*)d_f_, *d_t = (uint8_t*)d_t_, *d_pbar = (uint8_t*)d_pbar_;
+  const uint8_t* d_polys = a.on_device ? (const uint8_t*)a.polys : (const uint8_t*)d_polys_;
+  uint8_t* d_fpoly = d_q + 32 * n * S;
+  uint32_t* status = (uint32_t*)(mo + MO_STATUS);
+  SNARKV_HIP(hipMemcpyAsync(mo, stage.data(), MO_STAGED, hipMemcpyHostToDevice, s));
+  SNARKV_HIP(hipMemcpyAsync(mo + MO_VAR, stage.data() + MO_VAR, mo_bytes - MO_VAR, hipMemcpyHostToDevice, s));
+  if (!a.on_device) SNARKV_HIP(hipMemcpyAsync(d_polys_, a.polys, 32 * n * a.n_polys, hipMemcpyHostToDevice, s));
+  SNARKV_HIP(hipMemcpyAsync(d_pbar, a.pbar, 32 * n, a.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  if (validate) {
+    const size_t step = (size_t)1 << 30, total = n * a.n_polys;
+    int bad = 0;
+    for (size_t i = 0; i < total && !bad; i += step)
+      SNARKV_TRY(count_bad(ctx, d_polys + 32 * i, std::min(step, total - i), (int*)(mo + MO_DELTA), &bad));
+    if (bad) {
+      set_last_error("ipa_multiopen_create_proof: %d coefficients of the polynomials are not canonical", bad);
+      return SNARKV_ERR_ENCODING;
+    }
+    SNARKV_TRY(count_bad(ctx, d_pbar, n, (int*)(mo + MO_DELTA), &bad));
+    if (bad) {
+      set_last_error("ipa_multiopen_create_proof: %d of %zu scalars of p_bar are not canonical", bad, n);
+      return SNARKV_ERR_ENCODING;
+    }
+  }
+
+  // ---- per set: q, then f_i = (q - r) / prod (X - point) ------------------------------------------------------------------
+  for (size_t i = 0; i < S; ++i) {
+    const SetPlan& pl = plan[i];
+    uint8_t* q = d_q + 32 * n * i;
+    SNARKV_TRY(poly_enqueue_lincomb(ctx, d_polys, n, pl.idx.data(), pl.scalars.data(), pl.idx.size(), q));
+    SNARKV_HIP(hipMemcpyAsync(d_t, q, 32 * n, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(k_mo_sub_low, dim3(1), dim3(64), 0, s, (uint32_t*)d_t, (const uint32_t*)(mo + var_r + 32 * pl.first_point),
+                       (uint32_t)pl.m);
+    SNARKV_HIP(hipGetLastError());
+    uint8_t* src = d_t;
+    size_t len = n;
+    for (size_t t = 0; t < pl.m; ++t) {
+      uint8_t* dst = t + 1 == pl.m ? d_f + 32 * n * i : (src == d_t ? d_t + 32 * n : d_t);
+      uint8_t* rem = mo + var_rem + 32 * (pl.first_point + t);
+      SNARKV_TRY(poly_enqueue_div_linear(ctx, src, len, mo + var_pts + 32 * (pl.first_point + t), dst, rem));
+      len -= 1;
+      SNARKV_HIP(hipMemsetAsync(dst + 32 * len, 0, 32 * (n - len), s));  // the quotient has `len` coefficients, f_i has n
+      hipLaunchKernelGGL(k_mo_check_rem, dim3(1), dim3(64), 0, s, (const uint32_t*)rem, (uint32_t)i, status + 1);
+      SNARKV_HIP(hipGetLastError());
+      src = dst;
+    }
+  }
+  // ---- f = sum x_2^j f_(S-1-j), its commitment ---------------------------------------------------------------------------
+  {
+    const std::vector<Fr29> px2 = h_powers(x2, S);
+    std::vector<uint32_t> idx(S);
+    std::vector<uint8_t> sc(32 * S);
+    for (size_t j = 0; j < S; ++j) {
+      idx[j] = (uint32_t)(S - 1 - j);
+      h_store(&sc[32 * j], px2[j]);
+    }
+    SNARKV_TRY(poly_enqueue_lincomb(ctx, d_f, n, idx.data(), sc.data(), S, d_fpoly));
+  }
+  SNARKV_TRY(ipa_enqueue_commit(ctx, dk->d_points, d_fpoly, n, mo + MO_OFF0N, mo + MO_PTS2, mo + MO_SC2F, mo + MO_OFF02,
+                                mo + MO_COMMIT, true));
+  uint8_t f64[64];
+  uint32_t first_bad = none;
+  SNARKV_HIP(hipMemcpyAsync(f64, mo + MO_COMMIT, 64, hipMemcpyDeviceToHost, s));
+  SNARKV_HIP(hipMemcpyAsync(&first_bad, status + 1, 4, hipMemcpyDeviceToHost, s));
+  SNARKV_HIP(hipStreamSynchronize(s));  // 1 of 3
+  if (first_bad != none) {
+    set_last_error("ipa_multiopen_create_proof: evaluation does not match the polynomial (query set %u)", first_bad);
+    return SNARKV_ERR_ARG;
+  }
+  std::vector<uint8_t> proof(need);
+  if (!tr_common_point(ts, f64, f64 + 32)) {
+    set_last_error(kInfinityText, "f");
+    return SNARKV_ERR_ENCODING;
+  }
+  tr_compress_point(f64, f64 + 32, &proof[0]);
+  uint8_t x3b[32];
+  (void)h_squeeze(ts, x3b);
+  // ---- q_i(x_3) and f(x_3) -------------------------------------------------------------------------------------------------
+  SNARKV_HIP(hipMemcpyAsync(mo + MO_POINT, x3b, 32, hipMemcpyHostToDevice, s));
+  for (size_t i = 0; i <= S; ++i) SNARKV_TRY(poly_enqueue_eval(ctx, d_q + 32 * n * i, n, mo + MO_POINT, mo + var_ev + 32 * i));
+  std::vector<uint8_t> evb(32 * (S + 1));
+  SNARKV_HIP(hipMemcpyAsync(evb.data(), mo + var_ev, evb.size(), hipMemcpyDeviceToHost, s));
+  SNARKV_HIP(hipStreamSynchronize(s));  // 2 of 3
+  for (size_t i = 0; i < S; ++i) {
+    tr_common_scalar(ts, &evb[32 * i]);
+    memcpy(&proof[32 + 32 * i], &evb[32 * i], 32);
+  }
+  const Fr29 x4 = h_squeeze(ts, nullptr);
+  // ---- p = x_4^S f + sum x_4^(S-1-i) q_i, lowered so that p(x_3) = 0; omega the same combination of the blinds -----------
+  uint8_t* d_p = d_t;
+  {
+    const std::vector<Fr29> px4 = h_powers(x4, S + 1);
+    std::vector<uint32_t> idx(S + 1);
+    std::vector<uint8_t> sc(32 * (S + 1));
+    idx[0] = (uint32_t)S;
+    h_store(&sc[0], px4[S]);
+    Fr29 omega = h_mul(h_load(a.f_blind32), px4[S]), delta = h_mul(h_load(&evb[32 * S]), px4[S]);
+    for (size_t i = 0; i < S; ++i) {
+      idx[1 + i] = (uint32_t)i;
+      h_store(&sc[32 * (1 + i)], px4[S - 1 - i]);
+      omega = h_add(omega, h_mul(plan[i].blind, px4[S - 1 - i]));
+      delta = h_add(delta, h_mul(h_load(&evb[32 * i]), px4[S - 1 - i]));
+    }
+    SNARKV_TRY(poly_enqueue_lincomb(ctx, d_q, n, idx.data(), sc.data(), S + 1, d_p));
+    uint8_t small[96];
+    h_store(small, delta);
+    h_store(small + 32, omega);
+    memcpy(small + 64, a.omega_bar32, 32);
+    SNARKV_HIP(hipMemcpyAsync(mo + MO_DELTA, small, 32, hipMemcpyHostToDevice, s));
+    SNARKV_HIP(hipMemcpyAsync(mo + MO_OMEGA, small + 32, 64, hipMemcpyHostToDevice, s));
+    SNARKV_HIP(hipMemcpyAsync(mo + MO_STATE, &ts, sizeof(ts), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_mo_sub_low, dim3(1), dim3(64), 0, s, (uint32_t*)d_p, (const uint32_t*)(mo + MO_DELTA), 1u);
+    SNARKV_HIP(hipGetLastError());
+  }
+  // ---- the zk opening of p at x_3, Bgh19's transcript order ----------------------------------------------------------------
+  snarkv_ipa_prover* p = nullptr;
+  SNARKV_TRY(session_open(ctx, dk, d_p, true, n, x3b, a.h64, nullptr, "ipa_multiopen_create_proof", &p));
+  std::vector<uint8_t> host;
+  auto rounds = [&]() -> int {
+    uint8_t* sm = p->d_small;
+    Blake2bState* st = (Blake2bState*)(mo + MO_STATE);
+    uint8_t* dproof = mo + MO_PROOF;
+    SNARKV_TRY(session_fold_staging(p));  // every allocation before the first kernel
+    SNARKV_TRY(session_enqueue_powers(p));
+    const uint32_t blocks = (uint32_t)std::min<size_t>(kIpMaxBlocks, (n + kIpThreads - 1) / kIpThreads);
+    hipLaunchKernelGGL(k_ipa_eval_partials, dim3(blocks), dim3(kIpThreads), 0, s, (const uint32_t*)d_pbar, (const uint32_t*)p->d_zs,
+                       (uint32_t)n, (Fr29*)(mo + MO_PARTIALS));
+    hipLaunchKernelGGL(k_ipa_eval_sub, dim3(1), dim3(kIpThreads), 0, s, (const Fr29*)(mo + MO_PARTIALS), blocks, (uint32_t*)d_pbar);
+    SNARKV_HIP(hipGetLastError());
+    SNARKV_TRY(ipa_enqueue_commit(ctx, dk->d_points, d_pbar, n, mo + MO_OFF0N, mo + MO_PTS2, mo + MO_SC2S, mo + MO_OFF02,
+                                  mo + MO_COMMIT, true));
+    hipLaunchKernelGGL(k_mo_transcript_s, dim3(1), dim3(64), 0, s, (const uint8_t*)(mo + MO_COMMIT), st, dproof,
+                       (uint32_t*)(mo + MO_ALPHA), (uint32_t*)(sm + SM_COMB_S + 32), status);
+    hipLaunchKernelGGL(k_ipa_axpy, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (uint32_t*)p->d_coeffs,
+                       (const uint32_t*)d_pbar, (const uint32_t*)(mo + MO_ALPHA), (uint32_t)n);
+    SNARKV_HIP(hipGetLastError());
+    SNARKV_TRY(session_enqueue_hprime(p));
+    for (uint32_t i = 0; i < k; ++i) {
+      SNARKV_TRY(session_enqueue_round(p));
+      hipLaunchKernelGGL(k_ipa_transcript_round, dim3(1), dim3(64), 0, s, (const uint8_t*)(sm + SM_LR), (uint32_t*)(sm + SM_XI), st,
+                         dproof + 32 + 64 * i, (uint32_t*)(mo + MO_XI + 32 * i), status);
+      SNARKV_HIP(hipGetLastError());
+      SNARKV_TRY(session_enqueue_fold(p));
+      p->rounds += 1;
+    }
+    hipLaunchKernelGGL(k_mo_transcript_finish, dim3(1), dim3(64), 0, s, (const uint8_t*)p->d_bases, (const uint8_t*)p->d_coeffs,
+                       (const uint32_t*)(mo + MO_OMEGA), (const uint32_t*)(mo + MO_ALPHA), st, dproof + 32 + 64 * k, mo + MO_U, status);
+    SNARKV_HIP(hipGetLastError());
+    host.resize(MO_PROOF - MO_STATUS + 64 * (size_t)k + 128);
+    SNARKV_HIP(hipMemcpyAsync(host.data(), mo + MO_STATUS, host.size(), hipMemcpyDeviceToHost, s));
+    SNARKV_HIP(hipStreamSynchronize(s));  // 3 of 3
+    return SNARKV_OK;
+  };
+  const int rc = rounds();
+  if (rc == SNARKV_OK) session_free(p);
+  else session_close(p);  // a failure may have left work in flight
+  if (rc != SNARKV_OK) return rc;
+  uint32_t st_bits;
+  memcpy(&st_bits, host.data(), 4);
+  if (st_bits) {
+    set_last_error(kInfinityText, st_bits & kMoSInf ? "s" : (st_bits & kMoRoundInf ? "L or R of a round" : "U"));
+    return SNARKV_ERR_ENCODING;
+  }
+  memcpy(&proof[32 + 32 * S], &host[MO_PROOF - MO_STATUS], 64 * (size_t)k + 128);
+  memcpy(u_out64, &host[MO_U - MO_STATUS], 64);
+  memcpy(xi_out32, &host[MO_XI - MO_STATUS], 32 * (size_t)k);
+  memcpy(proof_out, proof.data(), need);
+  return SNARKV_OK;
+}
+
+int multiopen_create_proof(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const MoArgs& a, uint8_t* proof_out, size_t proof_cap,
+                           size_t* proof_len, uint8_t* xi_out32, uint8_t* u_out64) {
+  if (!ctx || !dk || !a.h64 || !a.s64 || !a.polys || !a.blinds32 || !a.x32 || !a.q_poly || !a.q_shift32 || !a.q_eval32 ||
+      !a.f_blind32 || !a.pbar || !a.omega_bar32 || !proof_out || !proof_len || !xi_out32 || !u_out64 ||
+      (a.absorbed_len && !a.absorbed)) {
+    set_last_error("ipa_multiopen_create_proof: a null argument (h and s are both required: the scheme is zero-knowledge)");
+    return SNARKV_ERR_ARG;
+  }
+  *proof_len = 0;
+  if (dk->device != ctx->device) return SNARKV_ERR_ARG;
+  if (dk->first != 0 || dk->count != ((size_t)1 << dk->k) || dk->k < 1 || dk->k > 30) return SNARKV_ERR_LENGTH;
+  if (a.n != dk->count) return SNARKV_ERR_LENGTH;
+  if (a.n_polys == 0 || a.n_queries == 0) return SNARKV_ERR_EMPTY;
+  if (a.on_device && ((uintptr_t)a.polys % 16 || (uintptr_t)a.pbar % 16)) return SNARKV_ERR_ARG;
+  for (size_t i = 0; i < a.n_queries; ++i)
+    if (a.q_poly[i] >= a.n_polys) {
+      set_last_error("ipa_multiopen_create_proof: query %zu names polynomial %u of %zu", i, a.q_poly[i], a.n_polys);
+      return SNARKV_ERR_ARG;
+    }
+  const std::vector<MultiopenSet> sets = multiopen_query_sets(a.q_poly, a.q_shift32, a.n_queries);
+  const size_t need = 64 * (size_t)dk->k + 32 * sets.size() + 160;
+  if (proof_cap < need) {
+    *proof_len = need;
+    set_last_error("ipa_multiopen_create_proof: the proof has %zu bytes, proof_cap is %zu", need, proof_cap);
+    return SNARKV_ERR_LENGTH;
+  }
+  if (ctx->flags & SNARKV_FLAG_VALIDATE) {
+    bool ok = host_canonical(a.x32) && host_canonical(a.f_blind32) && host_canonical(a.omega_bar32);
+    for (size_t i = 0; ok && i < a.n_polys; ++i) ok = host_canonical(a.blinds32 + 32 * i);
+    for (size_t i = 0; ok && i < a.n_queries; ++i) ok = host_canonical(a.q_shift32 + 32 * i) && host_canonical(a.q_eval32 + 32 * i);
+    if (!ok) {
+      set_last_error("ipa_multiopen_create_proof: x, a blind, a shift, an evaluation, f_blind or omega_bar is not canonical");
+      return SNARKV_ERR_ENCODING;
+    }
+  }
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  SNARKV_TRY(multiopen_run(ctx, dk, a, sets, need, proof_out, xi_out32, u_out64));
+  *proof_len = need;
+  return SNARKV_OK;
+}
+
+}  // namespace
+}  // namespace snarkv
+
+using namespace snarkv;
+
+extern "C" {
+
+int SNARKV_API(ipa_multiopen_create_proof)(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const uint8_t h64[64], const uint8_t s64[64],
+                                           const uint8_t* polys32, size_t n, size_t n_polys, const uint8_t* blinds32,
+                                           const uint8_t x32[32], const uint32_t* q_poly, const uint8_t* q_shift32,
+                                           const uint8_t* q_eval32, size_t n_queries, const uint8_t f_blind32[32],
+                                           const uint8_t* pbar32, const uint8_t omega_bar32[32], const uint8_t* absorbed,
+                                           size_t absorbed_len, uint8_t* proof_out, size_t proof_cap, size_t* proof_len,
+                                           uint8_t* xi_out32, uint8_t u_out64[64]) {
+  const MoArgs a = {h64, s64, blinds32, x32, q_shift32, q_eval32, f_blind32, omega_bar32, absorbed, q_poly, polys32, pbar32, false,
+                    n, n_polys, n_queries, absorbed_len};
+  return multiopen_create_proof(ctx, dk, a, proof_out, proof_cap, proof_len, xi_out32, u_out64);
+}
+
+int SNARKV_API(ipa_multiopen_create_proof_dev)(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const uint8_t h64[64],
+                                               const uint8_t s64[64], const void* d_polys32, size_t n, size_t n_polys,
+                                               const uint8_t* blinds32, const uint8_t x32[32], const uint32_t* q_poly,
+                                               const uint8_t* q_shift32, const uint8_t* q_eval32, size_t n_queries,
+                                               const uint8_t f_blind32[32], const void* d_pbar32, const uint8_t omega_bar32[32],
+                                               const uint8_t* absorbed, size_t absorbed_len, uint8_t* proof_out, size_t proof_cap,
+                                               size_t* proof_len, uint8_t* xi_out32, uint8_t u_out64[64]) {
+  const MoArgs a = {h64, s64, blinds32, x32, q_shift32, q_eval32, f_blind32, omega_bar32, absorbed, q_poly, d_polys32, d_pbar32, true,
+                    n, n_polys, n_queries, absorbed_len};
+  return multiopen_create_proof(ctx, dk, a, proof_out, proof_cap, proof_len, xi_out32, u_out64);
+}
+
+}  // extern "C"

@@ -20,6 +20,7 @@
 #include "../../include/snarkv_ipa_batch.h"
 #include "../../include/snarkv_ipa_fold.h"
 #include "../../include/snarkv_ipa_create.h"
+#include "../../include/snarkv_ipa_multiopen.h"
 #include "../../include/snarkv_pallas.h"
 #include "../../include/snarkv_pallas_decompress.h"
 
@@ -115,6 +116,16 @@ int pallas_ipa_create_proof(const snarkv_ipa_dk* dk, const uint8_t h64[64], cons
   return snarkv_pallas_ipa_create_proof(c, dk, h64, s64, coeffs32, n, z32, omega32, pbar32, omega_bar32, absorbed, absorbed_len, proof_out,
                                  proof_cap, proof_len, xi_out32, u_out64);
 }
+int pallas_ipa_multiopen_create_proof(const snarkv_ipa_dk* dk, const uint8_t h64[64], const uint8_t s64[64], const uint8_t* polys32, size_t n, size_t n_polys,
+    const uint8_t* blinds32, const uint8_t x32[32], const uint32_t* q_poly, const uint8_t* q_shift32, const uint8_t* q_eval32,
+    size_t n_queries, const uint8_t f_blind32[32], const uint8_t* pbar32, const uint8_t omega_bar32[32], const uint8_t* absorbed,
+    size_t absorbed_len, uint8_t* proof_out, size_t proof_cap, size_t* proof_len, uint8_t* xi_out32, uint8_t u_out64[64]) {
+  PALLAS_DEFAULT_CTX();
+  return snarkv_pallas_ipa_multiopen_create_proof(c, dk, h64, s64, polys32, n, n_polys, blinds32, x32, q_poly, q_shift32, q_eval32, n_queries,
+                                           f_blind32, pbar32, omega_bar32, absorbed, absorbed_len, proof_out, proof_cap, proof_len,
+                                           xi_out32, u_out64);
+}
+
 int pallas_g1_decompress(const uint8_t* in32, size_t n, uint8_t* out64, uint8_t* ok) {
   PALLAS_DEFAULT_CTX();
   return snarkv_pallas_g1_decompress(c, in32, n, out64, ok);
