@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsnarkv_amd.so")
 UNITS = ["ctx", "msm_api", "capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "ipa_prover", "mgpu",
-         "decompress", "msm_shared", "ipa_fold", "ipa_create", "poly", "ipa_multiopen"]
+         "decompress", "msm_shared", "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
@@ -80,7 +80,7 @@ def _link(lib, res, extra):
 
 # The pasta build of the curve-generic units (csrc/pallas.hip explains the flags, csrc/ctx.hpp the policy they select).
 PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover", "decompress_pallas", "msm_shared",
-                "ipa_fold", "ipa_create", "poly", "ipa_multiopen"]
+                "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
 

@@ -4,7 +4,7 @@
 //   prefix   0x00 before a challenge, 0x01 before a point (x | y, 32 bytes little-endian each), 0x02 before a scalar
 //   squeeze  digest of a COPY of the state, read as a 512-bit little-endian integer, reduced mod r (`from_uniform_bytes`)
 //   points   travel compressed: x with the parity of y in bit 255; the identity is never written
-// Same source for the kernels of ipa_create.hip and for the host (tests/hosttest/hosttest_blake2b.cpp, and the host side of
+// Same source for the kernels of ipa_opening.hip and for the host (tests/hosttest/hosttest_blake2b.cpp, and the host side of
 // snarkv_ipa_create_proof, which hashes the caller's prefix with it), as ipa_fold.h.
 //
 // The state is meant to live in memory (device global memory between launches): `buf` is written byte by byte at the

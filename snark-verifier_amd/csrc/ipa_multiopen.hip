@@ -9,51 +9,21 @@
 //   device  q_i(x_3), f(x_3)                                poly_enqueue_eval                              -> sync 2: S + 1 scalars
 //   host    writes the q_i(x_3), squeezes x_4, forms omega and p(x_3)'s correction
 //   device  p = x_4^S f + sum x_4^(S-i) q_i, p[0] -= ...    poly_enqueue_lincomb + k_mo_sub_low
-//           the zk opening of p at x_3 in Bgh19's order: p_bar[0] -= p_bar(x_3), s = commit(p_bar, omega_bar),
-//           k_mo_transcript_s (writes s, squeezes alpha, then xi_0), p' = p + alpha p_bar, k rounds of the session with
-//           k_ipa_transcript_round, k_mo_transcript_finish (writes c, omega', U)                            -> sync 3: the proof
-// The session (ipa_prover.hip) and the kernels of ipa_create.hip run unchanged; only the two transcript kernels around the
-// rounds differ from `Ipa::create_proof`, which writes omega' before xi_0 and U before c.
+//           the blinded opening of p at x_3 (ipa_opening.hip) in `TranscriptOrder::Bgh19`: s, alpha, xi_0 before the k
+//           rounds, c, omega', U after them, where `Ipa::create_proof` writes omega' before xi_0 and U before c
+//                                                                                                         -> sync 3: the proof
 #include <string.h>
 #include <algorithm>
 #include <vector>
-#include "blake2b_dev.h"
 #include "ipa_multiopen_sets.h"
-#include "ipa_prover.hpp"
+#include "ipa_opening.hpp"
 #include "poly.hpp"
 #include "../../include/snarkv_ipa_multiopen.h"
 
 namespace snarkv {
 
-// layout of the call's device buffer; the host stages [0, MO_STAGED) and the variable part behind MO_VAR
-enum : size_t {
-  MO_STATE = 0,       // Blake2bState, uploaded after x_4
-  MO_STATUS = 256,    // kMo* bits | the first set whose division left a remainder (0xffffffff: none)
-  MO_U = 272,         // U                                   64
-  MO_XI = 336,        // xi_1..xi_k                          32 x 32
-  MO_PROOF = 1360,    // s | k x (L | R) | c | omega' | U    64 x 32 + 128
-  MO_ALPHA = 3584,    // alpha                               32
-  MO_OMEGA = 3616,    // omega | omega_bar                   64, uploaded after x_4
-  MO_SC2F = 3680,     // [1, f_blind]                        64
-  MO_SC2S = 3744,     // [1, omega_bar]                      64
-  MO_PTS2 = 3808,     // [the MSM of a commitment, s]        128
-  MO_OFF02 = 3936,    // {0, 2}
-  MO_OFF0N = 3944,    // {0, n}
-  MO_COMMIT = 3968,   // the commitment of f, then s         64
-  MO_POINT = 4032,    // x_3                                 32
-  MO_DELTA = 4064,    // what p[0] is lowered by             32
-  MO_STAGED = 4096,
-  MO_PARTIALS = 4096, // kIpMaxBlocks Fr29
-  MO_VAR = MO_PARTIALS + ((kIpMaxBlocks * sizeof(Fr29) + 31) / 32) * 32,
-};
-static_assert(sizeof(Blake2bState) <= MO_STATUS - MO_STATE, "the transcript state has 256 bytes");
-constexpr uint32_t kMoRoundInf = 1, kMoUInf = 2, kMoSInf = 4;  // kMoRoundInf is what k_ipa_transcript_round sets
-
-__device__ __forceinline__ void mo_st_words(uint32_t* __restrict__ p, const uint32_t (&w)[8]) {
-  uint4* o = reinterpret_cast<uint4*>(p);
-  o[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  o[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
+// the variable part of the call's device block (ipa_opening.hpp), staged by the host: points | remainders | r | evaluations
+constexpr size_t MO_VAR = OP_BYTES;
 
 // poly[j] -= sub[j], j < m
 __global__ void __launch_bounds__(64) k_mo_sub_low(uint32_t* __restrict__ poly, const uint32_t* __restrict__ sub, uint32_t m) {
@@ -73,58 +43,6 @@ __global__ void __launch_bounds__(64) k_mo_check_rem(const uint32_t* __restrict_
   uint32_t any = 0;
   for (int w = 0; w < 8; ++w) any |= rem[w];
   if (any) atomicMin(first_bad, set);
-}
-
-// Bgh19's order before the rounds: writes s, squeezes alpha (canonical to alpha_out), squeezes xi_0 into the slot the
-// session's h' = xi_0 h reads.  Two passes through the one absorbing site.
-__global__ void __launch_bounds__(64) k_mo_transcript_s(const uint8_t* __restrict__ s64, Blake2bState* __restrict__ st,
-                                                        uint8_t* __restrict__ proof32, uint32_t* __restrict__ alpha_out,
-                                                        uint32_t* __restrict__ xi0_out, uint32_t* __restrict__ status) {
-  __shared__ uint8_t msg[kTrPointBytes + 2 * kTrSqueezeBytes];
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  if (!tr_put_point(msg, s64, s64 + 32)) *status |= kMoSInf;
-  tr_put_squeeze(msg + kTrPointBytes);
-  tr_put_squeeze(msg + kTrPointBytes + kTrSqueezeBytes);
-  tr_compress_point(s64, s64 + 32, proof32);
-  const uint8_t* part = msg;
-  size_t part_len = kTrPointBytes + kTrSqueezeBytes;
-  uint32_t* out = alpha_out;
-#pragma unroll 1
-  for (int pass = 0; pass < 2; ++pass) {
-    b2b_update(*st, part, part_len);
-    uint32_t w[8];
-    (void)tr_challenge(*st, w);
-    mo_st_words(out, w);
-    part = msg + kTrPointBytes + kTrSqueezeBytes;
-    part_len = kTrSqueezeBytes;
-    out = xi0_out;
-  }
-}
-
-// ... and after them: writes c = the last coefficient, omega' = omega + alpha omega_bar, U = the last base; U also to u_out
-__global__ void __launch_bounds__(64) k_mo_transcript_finish(const uint8_t* __restrict__ u, const uint8_t* __restrict__ c,
-                                                             const uint32_t* __restrict__ omegas,
-                                                             const uint32_t* __restrict__ alpha, Blake2bState* __restrict__ st,
-                                                             uint8_t* __restrict__ proof128, uint8_t* __restrict__ u_out,
-                                                             uint32_t* __restrict__ status) {
-  __shared__ uint8_t msg[2 * kTrScalarBytes + kTrPointBytes];
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  tr_put_scalar(msg, c);
-  const Fr29 op = fr29_add(ld_fr(omegas), fr29_mul(ld_fr(alpha), ld_fr(omegas + 8)));
-  uint32_t w[8];
-  fr29_to_canonical(op, w);
-  uint8_t* sc = msg + kTrScalarBytes;
-  sc[0] = 0x02;
-  for (int i = 0; i < 32; ++i) {
-    const uint8_t b = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-    sc[1 + i] = b;
-    proof128[32 + i] = b;
-  }
-  if (!tr_put_point(msg + 2 * kTrScalarBytes, u, u + 32)) *status |= kMoUInf;
-  for (int i = 0; i < 32; ++i) proof128[i] = c[i];
-  tr_compress_point(u, u + 32, proof128 + 64);
-  for (int i = 0; i < 64; ++i) u_out[i] = u[i];
-  b2b_update(*st, msg, sizeof(msg));
 }
 
 namespace {
@@ -222,29 +140,11 @@ struct SetPlan {
   size_t m;
 };
 
-// device buffers of one call; freed when the call leaves, after the stream has drained
-struct Buffers {
-  hipStream_t stream;
-  std::vector<void*> all;
-  explicit Buffers(hipStream_t s) : stream(s) {}
-  int get(void** out, size_t bytes) {
-    SNARKV_TRY(device_malloc(out, bytes));
-    all.push_back(*out);
-    return SNARKV_OK;
-  }
-  ~Buffers() {
-    if (all.empty()) return;
-    (void)hipStreamSynchronize(stream);  // a failure may have left work in flight
-    for (void* b : all) (void)hipFree(b);
-  }
-};
-
-const char kInfinityText[] = "ipa_multiopen_create_proof: cannot write points at infinity to the transcript (%s)";
+const char kWho[] = "ipa_multiopen_create_proof";
 
 int multiopen_run(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const MoArgs& a, const std::vector<MultiopenSet>& sets, size_t need,
                   uint8_t* proof_out, uint8_t* xi_out32, uint8_t* u_out64) {
   const size_t n = a.n, S = sets.size();
-  const uint32_t k = dk->k;
   const bool validate = (ctx->flags & SNARKV_FLAG_VALIDATE) != 0;
   hipStream_t s = ctx->stream;
   SNARKV_WIRE_FORM(ctx);
@@ -298,15 +198,12 @@ int multiopen_run(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const MoArgs& a, con
     }
     at += m;
   }
-  const uint32_t none = 0xffffffffu, off02[2] = {0, 2}, off0n[2] = {0, (uint32_t)n};
-  memcpy(&stage[MO_STATUS + 4], &none, 4);
-  stage[MO_SC2F] = 1;
-  memcpy(&stage[MO_SC2F + 32], a.f_blind32, 32);
-  stage[MO_SC2S] = 1;
-  memcpy(&stage[MO_SC2S + 32], a.omega_bar32, 32);
-  memcpy(&stage[MO_PTS2 + 64], a.s64, 64);
-  memcpy(&stage[MO_OFF02], off02, sizeof(off02));
-  memcpy(&stage[MO_OFF0N], off0n, sizeof(off0n));
+  const uint32_t none = 0xffffffffu, off0n[2] = {0, (uint32_t)n};
+  memcpy(&stage[OP_STATUS + 4], &none, 4);
+  stage[OP_SC2F] = 1;
+  memcpy(&stage[OP_SC2F + 32], a.f_blind32, 32);
+  opening_stage_blinding(stage.data(), a.omega_bar32, a.s64);
+  memcpy(&stage[OP_OFF0N], off0n, sizeof(off0n));
 
   // ---- device buffers: the polynomials (host form), q_1..q_S | f, f_1..f_S, two work polynomials, p_bar ------------------
   Buffers bufs(s);
@@ -320,26 +217,21 @@ int multiopen_run(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const MoArgs& a, con
   uint8_t *mo = (uint8_t*)d_mo_, *d_q = (uint8_t*)d_q_, *d_f = (uint8_t*)d_f_, *d_t = (uint8_t*)d_t_, *d_pbar = (uint8_t*)d_pbar_;
   const uint8_t* d_polys = a.on_device ? (const uint8_t*)a.polys : (const uint8_t*)d_polys_;
   uint8_t* d_fpoly = d_q + 32 * n * S;
-  uint32_t* status = (uint32_t*)(mo + MO_STATUS);
-  SNARKV_HIP(hipMemcpyAsync(mo, stage.data(), MO_STAGED, hipMemcpyHostToDevice, s));
+  uint32_t* status = (uint32_t*)(mo + OP_STATUS);
+  SNARKV_HIP(hipMemcpyAsync(mo, stage.data(), OP_STAGED, hipMemcpyHostToDevice, s));
   SNARKV_HIP(hipMemcpyAsync(mo + MO_VAR, stage.data() + MO_VAR, mo_bytes - MO_VAR, hipMemcpyHostToDevice, s));
   if (!a.on_device) SNARKV_HIP(hipMemcpyAsync(d_polys_, a.polys, 32 * n * a.n_polys, hipMemcpyHostToDevice, s));
-  SNARKV_HIP(hipMemcpyAsync(d_pbar, a.pbar, 32 * n, a.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   if (validate) {
     const size_t step = (size_t)1 << 30, total = n * a.n_polys;
     int bad = 0;
     for (size_t i = 0; i < total && !bad; i += step)
-      SNARKV_TRY(count_bad(ctx, d_polys + 32 * i, std::min(step, total - i), (int*)(mo + MO_DELTA), &bad));
+      SNARKV_TRY(count_bad(ctx, d_polys + 32 * i, std::min(step, total - i), (int*)(mo + OP_DELTA), &bad));
     if (bad) {
       set_last_error("ipa_multiopen_create_proof: %d coefficients of the polynomials are not canonical", bad);
       return SNARKV_ERR_ENCODING;
     }
-    SNARKV_TRY(count_bad(ctx, d_pbar, n, (int*)(mo + MO_DELTA), &bad));
-    if (bad) {
-      set_last_error("ipa_multiopen_create_proof: %d of %zu scalars of p_bar are not canonical", bad, n);
-      return SNARKV_ERR_ENCODING;
-    }
   }
+  SNARKV_TRY(opening_upload_pbar(ctx, kWho, d_pbar, a.pbar, a.on_device, n, (int*)(mo + OP_DELTA)));
 
   // ---- per set: q, then f_i = (q - r) / prod (X - point) ------------------------------------------------------------------
   for (size_t i = 0; i < S; ++i) {
@@ -374,11 +266,11 @@ int multiopen_run(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const MoArgs& a, con
     }
     SNARKV_TRY(poly_enqueue_lincomb(ctx, d_f, n, idx.data(), sc.data(), S, d_fpoly));
   }
-  SNARKV_TRY(ipa_enqueue_commit(ctx, dk->d_points, d_fpoly, n, mo + MO_OFF0N, mo + MO_PTS2, mo + MO_SC2F, mo + MO_OFF02,
-                                mo + MO_COMMIT, true));
+  SNARKV_TRY(ipa_enqueue_commit(ctx, dk->d_points, d_fpoly, n, mo + OP_OFF0N, mo + OP_PTS2, mo + OP_SC2F, mo + OP_OFF02,
+                                mo + OP_BLIND, true));
   uint8_t f64[64];
   uint32_t first_bad = none;
-  SNARKV_HIP(hipMemcpyAsync(f64, mo + MO_COMMIT, 64, hipMemcpyDeviceToHost, s));
+  SNARKV_HIP(hipMemcpyAsync(f64, mo + OP_BLIND, 64, hipMemcpyDeviceToHost, s));
   SNARKV_HIP(hipMemcpyAsync(&first_bad, status + 1, 4, hipMemcpyDeviceToHost, s));
   SNARKV_HIP(hipStreamSynchronize(s));  // 1 of 3
   if (first_bad != none) {
@@ -386,16 +278,13 @@ int multiopen_run(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const MoArgs& a, con
     return SNARKV_ERR_ARG;
   }
   std::vector<uint8_t> proof(need);
-  if (!tr_common_point(ts, f64, f64 + 32)) {
-    set_last_error(kInfinityText, "f");
-    return SNARKV_ERR_ENCODING;
-  }
+  if (!tr_common_point(ts, f64, f64 + 32)) return opening_infinity_error(kWho, "f");
   tr_compress_point(f64, f64 + 32, &proof[0]);
   uint8_t x3b[32];
   (void)h_squeeze(ts, x3b);
   // ---- q_i(x_3) and f(x_3) -------------------------------------------------------------------------------------------------
-  SNARKV_HIP(hipMemcpyAsync(mo + MO_POINT, x3b, 32, hipMemcpyHostToDevice, s));
-  for (size_t i = 0; i <= S; ++i) SNARKV_TRY(poly_enqueue_eval(ctx, d_q + 32 * n * i, n, mo + MO_POINT, mo + var_ev + 32 * i));
+  SNARKV_HIP(hipMemcpyAsync(mo + OP_POINT, x3b, 32, hipMemcpyHostToDevice, s));
+  for (size_t i = 0; i <= S; ++i) SNARKV_TRY(poly_enqueue_eval(ctx, d_q + 32 * n * i, n, mo + OP_POINT, mo + var_ev + 32 * i));
   std::vector<uint8_t> evb(32 * (S + 1));
   SNARKV_HIP(hipMemcpyAsync(evb.data(), mo + var_ev, evb.size(), hipMemcpyDeviceToHost, s));
   SNARKV_HIP(hipStreamSynchronize(s));  // 2 of 3
@@ -424,64 +313,17 @@ int multiopen_run(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const MoArgs& a, con
     h_store(small, delta);
     h_store(small + 32, omega);
     memcpy(small + 64, a.omega_bar32, 32);
-    SNARKV_HIP(hipMemcpyAsync(mo + MO_DELTA, small, 32, hipMemcpyHostToDevice, s));
-    SNARKV_HIP(hipMemcpyAsync(mo + MO_OMEGA, small + 32, 64, hipMemcpyHostToDevice, s));
-    SNARKV_HIP(hipMemcpyAsync(mo + MO_STATE, &ts, sizeof(ts), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_mo_sub_low, dim3(1), dim3(64), 0, s, (uint32_t*)d_p, (const uint32_t*)(mo + MO_DELTA), 1u);
+    SNARKV_HIP(hipMemcpyAsync(mo + OP_DELTA, small, 32, hipMemcpyHostToDevice, s));
+    SNARKV_HIP(hipMemcpyAsync(mo + OP_OMEGA, small + 32, 64, hipMemcpyHostToDevice, s));
+    SNARKV_HIP(hipMemcpyAsync(mo + OP_STATE, &ts, sizeof(ts), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_mo_sub_low, dim3(1), dim3(64), 0, s, (uint32_t*)d_p, (const uint32_t*)(mo + OP_DELTA), 1u);
     SNARKV_HIP(hipGetLastError());
   }
   // ---- the zk opening of p at x_3, Bgh19's transcript order ----------------------------------------------------------------
   snarkv_ipa_prover* p = nullptr;
-  SNARKV_TRY(session_open(ctx, dk, d_p, true, n, x3b, a.h64, nullptr, "ipa_multiopen_create_proof", &p));
-  std::vector<uint8_t> host;
-  auto rounds = [&]() -> int {
-    uint8_t* sm = p->d_small;
-    Blake2bState* st = (Blake2bState*)(mo + MO_STATE);
-    uint8_t* dproof = mo + MO_PROOF;
-    SNARKV_TRY(session_fold_staging(p));  // every allocation before the first kernel
-    SNARKV_TRY(session_enqueue_powers(p));
-    const uint32_t blocks = (uint32_t)std::min<size_t>(kIpMaxBlocks, (n + kIpThreads - 1) / kIpThreads);
-    hipLaunchKernelGGL(k_ipa_eval_partials, dim3(blocks), dim3(kIpThreads), 0, s, (const uint32_t*)d_pbar, (const uint32_t*)p->d_zs,
-                       (uint32_t)n, (Fr29*)(mo + MO_PARTIALS));
-    hipLaunchKernelGGL(k_ipa_eval_sub, dim3(1), dim3(kIpThreads), 0, s, (const Fr29*)(mo + MO_PARTIALS), blocks, (uint32_t*)d_pbar);
-    SNARKV_HIP(hipGetLastError());
-    SNARKV_TRY(ipa_enqueue_commit(ctx, dk->d_points, d_pbar, n, mo + MO_OFF0N, mo + MO_PTS2, mo + MO_SC2S, mo + MO_OFF02,
-                                  mo + MO_COMMIT, true));
-    hipLaunchKernelGGL(k_mo_transcript_s, dim3(1), dim3(64), 0, s, (const uint8_t*)(mo + MO_COMMIT), st, dproof,
-                       (uint32_t*)(mo + MO_ALPHA), (uint32_t*)(sm + SM_COMB_S + 32), status);
-    hipLaunchKernelGGL(k_ipa_axpy, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (uint32_t*)p->d_coeffs,
-                       (const uint32_t*)d_pbar, (const uint32_t*)(mo + MO_ALPHA), (uint32_t)n);
-    SNARKV_HIP(hipGetLastError());
-    SNARKV_TRY(session_enqueue_hprime(p));
-    for (uint32_t i = 0; i < k; ++i) {
-      SNARKV_TRY(session_enqueue_round(p));
-      hipLaunchKernelGGL(k_ipa_transcript_round, dim3(1), dim3(64), 0, s, (const uint8_t*)(sm + SM_LR), (uint32_t*)(sm + SM_XI), st,
-                         dproof + 32 + 64 * i, (uint32_t*)(mo + MO_XI + 32 * i), status);
-      SNARKV_HIP(hipGetLastError());
-      SNARKV_TRY(session_enqueue_fold(p));
-      p->rounds += 1;
-    }
-    hipLaunchKernelGGL(k_mo_transcript_finish, dim3(1), dim3(64), 0, s, (const uint8_t*)p->d_bases, (const uint8_t*)p->d_coeffs,
-                       (const uint32_t*)(mo + MO_OMEGA), (const uint32_t*)(mo + MO_ALPHA), st, dproof + 32 + 64 * k, mo + MO_U, status);
-    SNARKV_HIP(hipGetLastError());
-    host.resize(MO_PROOF - MO_STATUS + 64 * (size_t)k + 128);
-    SNARKV_HIP(hipMemcpyAsync(host.data(), mo + MO_STATUS, host.size(), hipMemcpyDeviceToHost, s));
-    SNARKV_HIP(hipStreamSynchronize(s));  // 3 of 3
-    return SNARKV_OK;
-  };
-  const int rc = rounds();
-  if (rc == SNARKV_OK) session_free(p);
-  else session_close(p);  // a failure may have left work in flight
-  if (rc != SNARKV_OK) return rc;
-  uint32_t st_bits;
-  memcpy(&st_bits, host.data(), 4);
-  if (st_bits) {
-    set_last_error(kInfinityText, st_bits & kMoSInf ? "s" : (st_bits & kMoRoundInf ? "L or R of a round" : "U"));
-    return SNARKV_ERR_ENCODING;
-  }
-  memcpy(&proof[32 + 32 * S], &host[MO_PROOF - MO_STATUS], 64 * (size_t)k + 128);
-  memcpy(u_out64, &host[MO_U - MO_STATUS], 64);
-  memcpy(xi_out32, &host[MO_XI - MO_STATUS], 32 * (size_t)k);
+  SNARKV_TRY(session_open(ctx, dk, d_p, true, n, x3b, a.h64, nullptr, kWho, &p));
+  SNARKV_TRY(opening_prove(p, mo, d_pbar, TranscriptOrder::Bgh19, kWho, "s", &proof[32 + 32 * S], xi_out32, u_out64));
+  bufs.drained = true;
   memcpy(proof_out, proof.data(), need);
   return SNARKV_OK;
 }

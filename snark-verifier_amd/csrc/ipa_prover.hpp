@@ -1,7 +1,7 @@
-// Internal: the prover session of ipa_prover.hip as ipa_create.hip sees it -- the session object, the layout of its small
-// device buffer, the enqueue steps both the session calls (include/snarkv_ipa_prover.h) and the one-call proof
-// (include/snarkv_ipa_create.h) are made of, and the few device helpers their kernels share.  None of the enqueue steps
-// synchronises unless its comment says so.
+// Internal: the prover session of ipa_prover.hip as the units built on it see it -- the session object, the layout of its
+// small device buffer, the enqueue steps both the session calls (include/snarkv_ipa_prover.h) and the blinded opening
+// (ipa_opening.hpp) are made of, and the few device helpers their kernels share.  None of the enqueue steps synchronises
+// unless its comment says so.
 #pragma once
 #include "ctx.hpp"
 #include "fr29.h"
@@ -42,18 +42,6 @@ __device__ __forceinline__ Fr29 fr_inv(const Fr29& x) {
   }
   return acc;
 }
-#endif
-
-// kernels of ipa_create.hip that the multi-open prover (ipa_multiopen.hip) launches as they are
-struct Blake2bState;
-#if defined(__HIPCC__)
-__global__ void k_ipa_transcript_round(const uint8_t* __restrict__ lr, uint32_t* __restrict__ xi_pair, Blake2bState* __restrict__ st,
-                                       uint8_t* __restrict__ proof64, uint32_t* __restrict__ xi_out, uint32_t* __restrict__ status);
-__global__ void k_ipa_eval_partials(const uint32_t* __restrict__ pbar, const uint32_t* __restrict__ zs, uint32_t n,
-                                    Fr29* __restrict__ partials);
-__global__ void k_ipa_eval_sub(const Fr29* __restrict__ partials, uint32_t blocks, uint32_t* __restrict__ pbar);
-__global__ void k_ipa_axpy(uint32_t* __restrict__ coeffs, const uint32_t* __restrict__ pbar, const uint32_t* __restrict__ alpha_canon,
-                           uint32_t n);
 #endif
 
 // the inner-product kernels: threads per workgroup, and the cap on workgroups (= partials kept per sum)

@@ -7,6 +7,7 @@ This ctypes table is this module's own, as `ipa_prover`'s is: one table per head
 """
 import ctypes
 
+from ._bind import bind, is_pallas
 from ._lib import SnarkvError, _as_bytes
 
 _vp, _cp, _sz, _u32, _int = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
@@ -29,52 +30,15 @@ SIGNATURES.update(_CONTEXT_FREE)
 
 SHARED_WINDOWS = 32  # rows of the window table per base: table_bytes = SHARED_WINDOWS * 2^k * 64
 
-_BOUND = {}
-
-
-class _Api:
-    def __init__(self, lib, prefix):
-        self.lib, self.prefix = lib, prefix
-        free = ("pallas" if prefix == "snarkv_pallas_" else "bn254") + "_ipa_commit_batch"
-        for name, (res, args) in [(prefix + n, s) for n, s in _SHAPES.items()] + [(free, _CONTEXT_FREE[free])]:
-            fn = getattr(lib, name)  # AttributeError if the header and the library drift
-            fn.restype, fn.argtypes = res, args
-        self.commit_batch_default = getattr(lib, free)
-
-    def __getattr__(self, name):
-        return getattr(self.lib, self.prefix + name)
-
-    def check(self, rc):
-        if rc < 0:
-            err = self.lib.snarkv_pallas_last_error if self.prefix == "snarkv_pallas_" else self.lib.snarkv_last_error
-            raise SnarkvError(rc, (err() or b"").decode(errors="replace"))
-        return rc
-
-
 def api(pallas):
     """the functions of one library (`pallas`: the pasta build)"""
-    if pallas not in _BOUND:
-        if pallas:
-            from .pallas import load_library
-
-            _BOUND[pallas] = _Api(load_library(), "snarkv_pallas_")
-        else:
-            from ._lib import load_library
-
-            _BOUND[pallas] = _Api(load_library(), "snarkv_")
-    return _BOUND[pallas]
-
-
-def _is_pallas(ctx):
-    from .pallas import PallasContext
-
-    return isinstance(ctx, PallasContext)
+    return bind(_SHAPES, {"commit_batch_default": _CONTEXT_FREE}, pallas)
 
 
 def commit_batch(ctx, dk, polys, n):
     """m commitments in one call: `polys` = m x n canonical scalars (32 bytes LE each, vector after vector),
     1 <= n <= 2^k (the first n bases) -> m points, 64 bytes each, concatenated."""
-    a = api(_is_pallas(ctx))
+    a = api(is_pallas(ctx))
     p = _as_bytes(polys)
     if n and len(p) % (32 * n):
         raise SnarkvError(-2, "polys is not a whole number of %d-scalar vectors" % n)
@@ -86,7 +50,7 @@ def commit_batch(ctx, dk, polys, n):
 
 def commit_batch_dev(ctx, dk, d_polys, n, m, d_out, slices=0):
     """the same from and to device memory, enqueued; `slices` = workgroups per vector (0 = auto)"""
-    a = api(_is_pallas(ctx))
+    a = api(is_pallas(ctx))
     a.check(a.ipa_commit_batch_dev(ctx._h, dk._h, _vp(int(d_polys)), n, m, slices, _vp(int(d_out))))
 
 
@@ -101,7 +65,7 @@ def commit_batch_default(dk, polys, n, pallas):
 
 
 def dk_prepare(ctx, dk):
-    a = api(_is_pallas(ctx))
+    a = api(is_pallas(ctx))
     a.check(a.ipa_dk_prepare(ctx._h, dk._h))
 
 

@@ -11,6 +11,7 @@ This ctypes table is this module's own, as `ipa_batch`'s is: one table per heade
 import ctypes
 import hashlib
 
+from ._bind import bind, is_pallas
 from ._lib import SnarkvError, _as_bytes
 
 _vp, _cp, _sz, _u32, _int = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
@@ -35,46 +36,9 @@ FOLD_BLOCK_BITS = 3  # a lane of the fold kernel owns 2^3 consecutive coefficien
 R_BN254 = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 R_PALLAS = 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100000001
 
-_BOUND = {}
-
-
-class _Api:
-    def __init__(self, lib, prefix):
-        self.lib, self.prefix = lib, prefix
-        free = ("pallas" if prefix == "snarkv_pallas_" else "bn254") + "_ipa_decide_folded"
-        for name, (res, args) in [(prefix + n, s) for n, s in _SHAPES.items()] + [(free, _CONTEXT_FREE[free])]:
-            fn = getattr(lib, name)  # AttributeError if the header and the library drift
-            fn.restype, fn.argtypes = res, args
-        self.decide_folded_default = getattr(lib, free)
-
-    def __getattr__(self, name):
-        return getattr(self.lib, self.prefix + name)
-
-    def check(self, rc):
-        if rc < 0:
-            err = self.lib.snarkv_pallas_last_error if self.prefix == "snarkv_pallas_" else self.lib.snarkv_last_error
-            raise SnarkvError(rc, (err() or b"").decode(errors="replace"))
-        return rc
-
-
 def api(pallas):
     """the functions of one library (`pallas`: the pasta build)"""
-    if pallas not in _BOUND:
-        if pallas:
-            from .pallas import load_library
-
-            _BOUND[pallas] = _Api(load_library(), "snarkv_pallas_")
-        else:
-            from ._lib import load_library
-
-            _BOUND[pallas] = _Api(load_library(), "snarkv_")
-    return _BOUND[pallas]
-
-
-def _is_pallas(ctx):
-    from .pallas import PallasContext
-
-    return isinstance(ctx, PallasContext)
+    return bind(_SHAPES, {"decide_folded_default": _CONTEXT_FREE}, pallas)
 
 
 def _split(k, xi, u):
@@ -95,7 +59,7 @@ def _rho(rho):
 def decide_folded(ctx, dk, xi, u, rho):
     """True iff `sum rho^i U_i == <sum rho^i h_coeffs(xi_i), G>`: `xi` = m x k scalars (32 bytes LE each), `u` = m points
     (64 bytes each), `rho` = 32 bytes LE or an int.  An off-curve or non-canonical U is False, not an exception."""
-    a = api(_is_pallas(ctx))
+    a = api(is_pallas(ctx))
     xi, u, m = _split(dk.k, xi, u)
     ok = ctypes.c_int(0)
     a.check(a.ipa_decide_folded(ctx._h, dk._h, xi if xi else b"\x00", u if u else b"\x00", m, _rho(rho), ctypes.byref(ok)))
@@ -114,7 +78,7 @@ def decide_folded_default(dk, xi, u, rho, pallas):
 def fold_coeffs_dev(ctx, k, xi, rho, d_h, slices=0):
     """`sum rho^i h_coeffs(xi_i)` as 2^k canonical scalars at device address `d_h` (16-byte aligned), enqueued;
     `slices` = accumulator slices per coefficient block (0 = auto)"""
-    a = api(_is_pallas(ctx))
+    a = api(is_pallas(ctx))
     xi = _as_bytes(xi)
     if k < 1 or len(xi) % (32 * k):
         raise SnarkvError(-2, "xi is not a whole number of %d-scalar challenge vectors" % k)

@@ -10,8 +10,7 @@ This ctypes table is this module's own, as `ipa_create`'s is: one table per head
 """
 import ctypes
 
-from ._lib import SnarkvError
-from .ipa_create import _fe, _pt, _vec
+from ._bind import bind, fe as _fe, is_pallas, prove, pt as _pt, vec as _vec
 
 _vp, _cp, _sz, _int = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int
 _szp = ctypes.POINTER(ctypes.c_size_t)
@@ -33,49 +32,9 @@ _CONTEXT_FREE = {
 SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPES.items()}
 SIGNATURES.update(_CONTEXT_FREE)
 
-_BOUND = {}
-
-
-class _Api:
-    def __init__(self, lib, prefix):
-        self.lib, self.prefix = lib, prefix
-        free = ("pallas" if prefix == "snarkv_pallas_" else "bn254") + "_ipa_multiopen_create_proof"
-        for name, (res, args) in [(prefix + n, s) for n, s in _SHAPES.items()] + [(free, _CONTEXT_FREE[free])]:
-            fn = getattr(lib, name)  # AttributeError if the header and the library drift
-            fn.restype, fn.argtypes = res, args
-        self.create_proof_default = getattr(lib, free)
-
-    def __getattr__(self, name):
-        return getattr(self.lib, self.prefix + name)
-
-    def last_error(self):
-        err = self.lib.snarkv_pallas_last_error if self.prefix == "snarkv_pallas_" else self.lib.snarkv_last_error
-        return (err() or b"").decode(errors="replace")
-
-    def check(self, rc):
-        if rc < 0:
-            raise SnarkvError(rc, self.last_error())
-        return rc
-
-
 def api(pallas):
     """the functions of one library (`pallas`: the pasta build)"""
-    if pallas not in _BOUND:
-        if pallas:
-            from .pallas import load_library
-
-            _BOUND[pallas] = _Api(load_library(), "snarkv_pallas_")
-        else:
-            from ._lib import load_library
-
-            _BOUND[pallas] = _Api(load_library(), "snarkv_")
-    return _BOUND[pallas]
-
-
-def _is_pallas(ctx):
-    from .pallas import PallasContext
-
-    return isinstance(ctx, PallasContext)
+    return bind(_SHAPES, {"create_proof_default": _CONTEXT_FREE}, pallas)
 
 
 def proof_bytes(k, n_sets):
@@ -89,50 +48,30 @@ def pack_queries(queries):
     return polys, b"".join(_fe(q[1]) for q in queries), b"".join(_fe(q[2]) for q in queries), len(queries)
 
 
-def _outs(k, queries):
-    cap = proof_bytes(k, len(queries))  # never more sets than queries
-    return ctypes.create_string_buffer(cap), cap, ctypes.c_size_t(0), ctypes.create_string_buffer(32 * max(k, 1)), \
-        ctypes.create_string_buffer(64)
-
-
-def _finish(a, k, rc, proof, plen, xi, u):
-    a.check(rc)
-    xis = [int.from_bytes(xi.raw[32 * i:32 * i + 32], "little") for i in range(k)]
-    x, y = int.from_bytes(u.raw[:32], "little"), int.from_bytes(u.raw[32:], "little")
-    return proof.raw[:plen.value], (xis, (x, y))
+def _prove(a, fn, handles, dk, h, s, polys, n_polys, blinds, x, queries, f_blind, p_bar, omega_bar, absorbed):
+    """`polys` and `p_bar` as the call takes them: packed bytes or device addresses"""
+    qp, qs, qe, nq = pack_queries(queries)
+    cap = proof_bytes(dk.k, len(queries))  # never more sets than queries
+    return prove(a, fn, dk.k, cap, *handles, _pt(h), _pt(s), polys, 1 << dk.k, n_polys, _vec(blinds), _fe(x), qp, qs, qe, nq,
+                 _fe(f_blind), p_bar, _fe(omega_bar), bytes(absorbed) or None, len(absorbed))
 
 
 def create_proof(ctx, dk, h, s, polys, blinds, x, queries, f_blind, p_bar, omega_bar, absorbed=b""):
     """-> (proof bytes, (xi, U)).  `polys`: a list of coefficient lists (or of packed byte strings), n = 2^k each."""
-    a = api(_is_pallas(ctx))
-    pb = b"".join(_vec(p) for p in polys)
-    n = 1 << dk.k
-    qp, qs, qe, nq = pack_queries(queries)
-    proof, cap, plen, xi, u = _outs(dk.k, queries)
-    rc = a.ipa_multiopen_create_proof(ctx._h, dk._h, _pt(h), _pt(s), pb or b"\x00", n, len(polys), _vec(blinds) or b"\x00", _fe(x),
-                                      qp, qs or b"\x00", qe or b"\x00", nq, _fe(f_blind), _vec(p_bar), _fe(omega_bar),
-                                      bytes(absorbed) or None, len(absorbed), proof, cap, ctypes.byref(plen), xi, u)
-    return _finish(a, dk.k, rc, proof, plen, xi, u)
+    a = api(is_pallas(ctx))
+    return _prove(a, a.ipa_multiopen_create_proof, (ctx._h, dk._h), dk, h, s, b"".join(_vec(p) for p in polys) or b"\x00",
+                  len(polys), blinds, x, queries, f_blind, _vec(p_bar), omega_bar, absorbed)
 
 
 def create_proof_dev(ctx, dk, h, s, d_polys, n_polys, blinds, x, queries, f_blind, d_p_bar, omega_bar, absorbed=b""):
     """the same with the polynomials (n_polys x 2^k x 32 bytes, poly-major) and p_bar at device addresses"""
-    a = api(_is_pallas(ctx))
-    qp, qs, qe, nq = pack_queries(queries)
-    proof, cap, plen, xi, u = _outs(dk.k, queries)
-    rc = a.ipa_multiopen_create_proof_dev(ctx._h, dk._h, _pt(h), _pt(s), _vp(int(d_polys)), 1 << dk.k, n_polys, _vec(blinds), _fe(x),
-                                          qp, qs, qe, nq, _fe(f_blind), _vp(int(d_p_bar)), _fe(omega_bar),
-                                          bytes(absorbed) or None, len(absorbed), proof, cap, ctypes.byref(plen), xi, u)
-    return _finish(a, dk.k, rc, proof, plen, xi, u)
+    a = api(is_pallas(ctx))
+    return _prove(a, a.ipa_multiopen_create_proof_dev, (ctx._h, dk._h), dk, h, s, _vp(int(d_polys)), n_polys, blinds, x, queries,
+                  f_blind, _vp(int(d_p_bar)), omega_bar, absorbed)
 
 
 def create_proof_default(dk, h, s, polys, blinds, x, queries, f_blind, p_bar, omega_bar, absorbed=b"", pallas=False):
     """`bn254_ipa_multiopen_create_proof` / `pallas_ipa_multiopen_create_proof`: on the library's default context"""
     a = api(pallas)
-    pb = b"".join(_vec(p) for p in polys)
-    qp, qs, qe, nq = pack_queries(queries)
-    proof, cap, plen, xi, u = _outs(dk.k, queries)
-    rc = a.create_proof_default(dk._h, _pt(h), _pt(s), pb or b"\x00", 1 << dk.k, len(polys), _vec(blinds) or b"\x00", _fe(x), qp,
-                                qs or b"\x00", qe or b"\x00", nq, _fe(f_blind), _vec(p_bar), _fe(omega_bar),
-                                bytes(absorbed) or None, len(absorbed), proof, cap, ctypes.byref(plen), xi, u)
-    return _finish(a, dk.k, rc, proof, plen, xi, u)
+    return _prove(a, a.create_proof_default, (dk._h,), dk, h, s, b"".join(_vec(p) for p in polys) or b"\x00", len(polys),
+                  blinds, x, queries, f_blind, _vec(p_bar), omega_bar, absorbed)

@@ -13,7 +13,8 @@ This ctypes table is this module's own: the header is not snarkv_amd.h, whose ta
 """
 import ctypes
 
-from ._lib import SnarkvError, _as_bytes
+from ._bind import bind, fe as _fe, is_pallas
+from ._lib import _as_bytes
 
 _vp, _cp, _sz, _u32, _int = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
 
@@ -35,42 +36,12 @@ SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPE
 R_BN254 = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 R_PALLAS = 0x40000000000000000000000000000000224698FC0994A8DD8C46EB2100000001
 
-_BOUND = set()
-
-
-class _Api:
-    """The prover functions of one library, with its modulus and error text."""
-
-    def __init__(self, lib, prefix, r):
-        if prefix not in _BOUND:
-            for n, (res, args) in _SHAPES.items():
-                fn = getattr(lib, prefix + n)  # AttributeError if the header and the library drift
-                fn.restype, fn.argtypes = res, args
-            _BOUND.add(prefix)
-        self.lib, self.prefix, self.r = lib, prefix, r
-
-    def __getattr__(self, name):
-        return getattr(self.lib, self.prefix + name)
-
-    def check(self, rc):
-        if rc < 0:
-            err = self.lib.snarkv_pallas_last_error if self.prefix == "snarkv_pallas_" else self.lib.snarkv_last_error
-            raise SnarkvError(rc, (err() or b"").decode(errors="replace"))
-        return rc
-
-
 def _api(ctx):
-    from .pallas import PallasContext
-
-    if isinstance(ctx, PallasContext):
-        return _Api(ctx._lib, "snarkv_pallas_", R_PALLAS)
-    from ._lib import load_library
-
-    return _Api(load_library(), "snarkv_", R_BN254)
-
-
-def _fe(v):
-    return int(v).to_bytes(32, "little")
+    """the prover functions of the context's library, with its modulus as `.r`"""
+    pallas = is_pallas(ctx)
+    a = bind(_SHAPES, None, pallas)
+    a.r = R_PALLAS if pallas else R_BN254
+    return a
 
 
 def _pt(p):

@@ -38,11 +38,11 @@ def test_both_libraries_export_every_declared_name():
 
 def test_null_arguments_are_refused_without_a_device():
     import snark_verifier_amd as sv
-    from snark_verifier_amd import ipa_prover
+    from snark_verifier_amd import _bind, ipa_prover
     from snark_verifier_amd import pallas as PL
 
     for lib, prefix in ((sv.load_library(), "snarkv_"), (PL.load_library(), "snarkv_pallas_")):
-        api = ipa_prover._Api(lib, prefix, ipa_prover.R_BN254)
+        api = _bind.Api(lib, prefix, ipa_prover._SHAPES)
         b32, b64 = b"\x00" * 32, b"\x00" * 64
         out = ctypes.create_string_buffer(64)
         h = ctypes.c_void_p()
