@@ -42,6 +42,7 @@ from . import ipa_batch  # noqa: F401,E402  (many vectors against one resident I
 from . import ipa_fold  # noqa: F401,E402  (decide_all as one folded check: include/snarkv_ipa_fold.h)
 from . import ipa_create  # noqa: F401,E402  (Ipa::create_proof in one call, Blake2b transcript on the device: include/snarkv_ipa_create.h)
 from . import poly  # noqa: F401,E402  (resident polynomials: linear combination, evaluation, division: include/snarkv_poly.h)
+from . import ntt  # noqa: F401,E402  (forward, inverse and coset transforms of resident polynomials: include/snarkv_ntt.h)
 from . import ipa_multiopen  # noqa: F401,E402  (the Bgh19 multi-open prover in one call: include/snarkv_ipa_multiopen.h)
 
 __all__ = [
@@ -52,6 +53,7 @@ __all__ = [
     "ipa_fold",
     "ipa_create",
     "poly",
+    "ntt",
     "ipa_multiopen",
     "IpaProver",
     "Context",

@@ -79,6 +79,7 @@ enum Slot {
   SLOT_MGPU_RECV,
   SLOT_IPA_FOLD,     // the folded decide (ipa_fold.hip): challenges and powers in the Montgomery domain, partial vectors
   SLOT_POLY,         // the polynomial calls (poly.hip): the roots and totals of the scan's levels, a staged pass of terms
+  SLOT_NTT,          // the transforms (ntt.hip): the tables of powers, then the working buffer of the passes
   SLOT_COUNT
 };
 
@@ -122,6 +123,9 @@ struct snarkv_ctx {
   bool order_ev_ready;
   hipStream_t hi_stream[2];  // high-priority streams of the batch pipeline (the sorts) + their join events (many_ev)
   bool hi_ready;
+  // the transforms (ntt.hip): which (k, direction) the tables in SLOT_NTT were built for (0: none), and where the slot was then
+  void* ntt_tables;
+  uint32_t ntt_key;
 };
 
 struct snarkv_dk {

@@ -18,7 +18,7 @@ X = 4965661367192848881
 MONT_R = 1 << 256
 
 
-def generic_section(p, r, b, name):
+def generic_section(p, r, b, name, r_gen):
     def lim(v):
         return ", ".join("0x%08xu" % ((v >> (32 * i)) & 0xFFFFFFFF) for i in range(8))
 
@@ -46,6 +46,14 @@ def generic_section(p, r, b, name):
     print("#define SNARKV_FR29_NINV 0x%08x  // -r^-1 mod 2^29" % ((-pow(r, -1, 1 << 29)) % (1 << 29)))
     print("#define SNARKV_FR29_ONE_LIMBS { %s }  // 2^261 mod r" % lim29(r29 % r))
     print("#define SNARKV_FR29_R2_LIMBS { %s }  // 2^522 mod r" % lim29(r29 * r29 % r))
+    # the 2^S-th root of unity of the scalar field, halo2curves' F::ROOT_OF_UNITY = g^((r - 1) / 2^S) (ntt.hip: the domain
+    # generator of size 2^k is this one squared S - k times)
+    s_ = ((r - 1) & -(r - 1)).bit_length() - 1
+    root = pow(r_gen, (r - 1) >> s_, r)
+    assert pow(root, 1 << (s_ - 1), r) == r - 1
+    print("#define SNARKV_FR_TWO_ADICITY %d" % s_)
+    print("#define SNARKV_FR29_ROOT_OF_UNITY_LIMBS { %s }  // %d^((r - 1) / 2^%d) * 2^261 mod r" % (lim29(root * r29 % r), r_gen, s_))
+    print("#define SNARKV_FR29_ROOT_OF_UNITY_INV_LIMBS { %s }  // its inverse, * 2^261 mod r" % lim29(pow(root, -1, r) * r29 % r))
 
 
 def _cube_roots(m):
@@ -165,7 +173,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "pallas":
     print("// GENERATED by gen_consts.py pallas -- do not edit.  8x32-bit limbs little-endian; *_MONT in Montgomery")
     print("// form (R = 2^256); *29* in 9x29-bit limbs (R = 2^261).  No pairing constants: the pasta build has no KZG decider.")
     print("#pragma once")
-    generic_section(PP, PQ, 5, "pallas")
+    generic_section(PP, PQ, 5, "pallas", 5)
     glv_section(PP, PQ, (PP - 1, 2))
     sqrt_section(PP, 5)
     sys.exit(0)
@@ -202,7 +210,7 @@ XI = (9, 1)
 print("// GENERATED by gen_consts.py -- do not edit.  BN254 constants, 8x32-bit limbs,")
 print("// little-endian limb order; *_MONT values are in Montgomery form (R = 2^256).")
 print("#pragma once")
-generic_section(P, R, 3, "bn254")
+generic_section(P, R, 3, "bn254", 7)
 glv_section(P, R, (1, 2))
 print("// ---- BN254 only")
 print("#define BN254_P_LIMBS { %s }" % limbs(P))
