@@ -43,6 +43,7 @@ from . import ipa_fold  # noqa: F401,E402  (decide_all as one folded check: incl
 from . import ipa_create  # noqa: F401,E402  (Ipa::create_proof in one call, Blake2b transcript on the device: include/snarkv_ipa_create.h)
 from . import poly  # noqa: F401,E402  (resident polynomials: linear combination, evaluation, division: include/snarkv_poly.h)
 from . import ntt  # noqa: F401,E402  (forward, inverse and coset transforms of resident polynomials: include/snarkv_ntt.h)
+from . import poly_prod  # noqa: F401,E402  (column products: batch inversion, grand product, permutation Z: include/snarkv_poly_prod.h)
 from . import ipa_multiopen  # noqa: F401,E402  (the Bgh19 multi-open prover in one call: include/snarkv_ipa_multiopen.h)
 
 __all__ = [
@@ -54,6 +55,7 @@ __all__ = [
     "ipa_create",
     "poly",
     "ntt",
+    "poly_prod",
     "ipa_multiopen",
     "IpaProver",
     "Context",

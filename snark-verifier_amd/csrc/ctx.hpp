@@ -80,6 +80,7 @@ enum Slot {
   SLOT_IPA_FOLD,     // the folded decide (ipa_fold.hip): challenges and powers in the Montgomery domain, partial vectors
   SLOT_POLY,         // the polynomial calls (poly.hip): the roots and totals of the scan's levels, a staged pass of terms
   SLOT_NTT,          // the transforms (ntt.hip): the tables of powers, then the working buffer of the passes
+  SLOT_POLY_PROD,    // the column products (poly_prod.hip): a staged pass of affine terms, the totals of the scans' levels
   SLOT_COUNT
 };
 
