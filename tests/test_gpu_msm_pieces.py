@@ -1,11 +1,13 @@
 """GPU parity of the Pippenger piece schedule: a bucket of cnt entries is cut into ceil(cnt / L) pieces of at most L
 entries (L = 16 / 32 for one small MSM, 128 under the throughput hint), one k_accumulate lane per piece, and k_fixup
 stitches split buckets and redoes degenerate ones.  Every case compares affine bytes with the C oracle, or with the
-unsplit single call where the oracle would be too slow."""
+unsplit single call where the oracle would be too slow.  The second half plans its buckets (tests/msm_edge_util.py) to
+reach the fix-up's redo paths, the cap 16, the level-2 sort at its LDS cap, carry chains of the recoders and the tiles."""
 import pytest
 
 import bn254 as O
 import coracle as C
+import msm_edge_util as E
 
 pytestmark = pytest.mark.gpu
 
@@ -201,3 +203,130 @@ def test_bucket_sharded_grids_with_split_buckets(hint):
         assert bytes(out.cpu().numpy()) == _run(ctx, s, p, c)
     finally:
         ctx.close()
+
+
+# ---- planned buckets at the schedule's edges (tests/msm_edge_util.py; the inputs are checked in tests/test_msm_edge_util.py) ----
+BN = E.curve("bn254")
+FILL = [1000 + 7 * i for i in range(300)]  # about 300 ordinary buckets next to the planned ones
+
+
+def test_geometry_restated_in_the_helper_matches_the_library():
+    import snark_verifier_amd as sv
+
+    for n in (1, 300, 2000, 7168, 1 << 14, 132000, 1 << 18, 600000, 1 << 20, 3 << 20):
+        for c in (0, 2, 8, 13, 16, 17, 22):
+            assert sv.Context.bucket_geometry(n, c) == E.pip_plan(n, c)[:3], (n, c)
+
+
+def _big_bucket(L, kind):
+    """a bucket of 25 L + 1 entries (26 pieces at the cap L: k_fixup's cooperative list), 25 L + 2 where the plan needs an
+    even length"""
+    n = 25 * L + 1
+    if kind in ("dup", "neg"):
+        return (n, ("marks", [(n // 2, kind)]))
+    if kind == "same":
+        return (n, ("pm", n, 0))
+    if kind == "cancel":
+        return (n + 1, ("pm", (n + 1) // 2, (n + 1) // 2))
+    return (n, ("pm", (n + 1) // 2, n // 2))  # "one_left": a copies of P, a - 1 of -P
+
+
+@pytest.mark.parametrize("L", [32, 128])
+@pytest.mark.parametrize("kind", ["dup", "neg", "same", "cancel", "one_left"])
+def test_big_split_bucket_with_exceptional_points(L, kind):
+    """More than kBigPieces pieces in one bucket, and partials that are degenerate: with nothing but +-P in the bucket
+    every piece of two or more entries is, whatever order the sort leaves, so the workgroup's `any_bad` recomputation
+    from the entries is certain (L = 32: one MSM of a few thousand terms; L = 128: the hint)."""
+    big = _big_bucket(L, kind)
+    plan = E.plan_buckets(BN, [big, (L + 1, "distinct")], FILL)
+    assert E.pip_plan(plan.n, 16)[5] == 32 and E.pip_plan(plan.n, 16, True)[5] == 128
+    assert (big[0] + L - 1) // L > E.BIG_PIECES and plan.lengths[3] == big[0]
+    assert plan.expected() == C.msm_pippenger(plan.s, plan.p, 4)
+    _both_modes(plan.s, plan.p, c=16)
+
+
+@pytest.mark.parametrize("L", [32, 128])
+def test_small_split_buckets_of_one_point_and_its_negation(L):
+    """Split buckets of L + 2 and 2 L + 1 entries (2 and 3 pieces: the lane-per-bucket list) that hold only +-P: a piece
+    of such entries leaves a partial that reads as the stored identity without being one, and the stitch must redo the
+    bucket rather than skip it.  2 L + 1 copies of P: two such partials and a remainder of one clean entry."""
+    specs = E.pm_kinds(L + 2) + E.pm_kinds(2 * L + 1) + [(2 * L + 1, "distinct")]
+    plan = E.plan_buckets(BN, specs, FILL)
+    assert plan.expected() == C.msm_pippenger(plan.s, plan.p, 4)
+    _both_modes(plan.s, plan.p, c=16)
+
+
+def test_cap_16_bucket_lengths(gpu_ctx):
+    """n = 132 000 at c = 16: latency_run_length picks 16.  Whole buckets below and at the cap, split ones above it, and
+    24 / 25 full pieces + 1 on either side of kBigPieces, with distinct points and with +-P."""
+    n = 132000
+    assert E.pip_plan(n, 16)[5] == 16
+    specs = [(ln, "distinct") for ln in (15, 16, 17, 33, 16 * 24 + 1, 16 * 25 + 1)]
+    specs += E.pm_kinds(16 * 25 + 1) + E.pm_kinds(16 * 24) + E.pm_kinds(33) + E.pm_kinds(18)
+    plan = E.plan_buckets(BN, specs, E.fill_digits(n - sum(s[0] for s in specs), 1001, 30001))
+    assert plan.n == n
+    assert _run(gpu_ctx, plan.s, plan.p, 16) == C.msm_pippenger(plan.s, plan.p, 4) == plan.expected()
+
+
+@pytest.mark.parametrize("n", [7167, 7168, 7169])
+def test_level2_sort_at_the_lds_cap(n, gpu_ctx):
+    """every entry in level-1 key 0 of window 0 (1 <= d <= 1024 at c = 16): k_sort_level2's fast path up to kSortCap =
+    7 168 items, the global path from 7 169"""
+    assert E.pip_plan(n, 16)[3] == 10
+    plan = E.plan_buckets(BN, [], E.fill_digits(n, 1, 1023))
+    assert _run(gpu_ctx, plan.s, plan.p, 16) == C.msm_pippenger(plan.s, plan.p, 4)
+
+
+def test_level2_sort_both_paths_in_one_launch(gpu_ctx):
+    """key 0 one item above the cap (global path) next to key 1 one item below it (LDS path)"""
+    fill = list(E.fill_digits(7169, 1, 1023)) + list(E.fill_digits(7167, 1025, 1023))
+    assert E.pip_plan(len(fill), 16)[3] == 10
+    plan = E.plan_buckets(BN, [], fill)
+    assert _run(gpu_ctx, plan.s, plan.p, 16) == C.msm_pippenger(plan.s, plan.p, 4)
+
+
+def _crafted():
+    return [k for c in (13, 16) for k, _, _ in E.crafted_scalars(BN, c)]
+
+
+@pytest.mark.parametrize("c", [13, 16])
+def test_carry_chains_among_random_terms(c, gpu_ctx):
+    """windows whose bits equal B exactly, in runs: the carry into a window is decided further down, and the histogram's
+    recoder (for_each_digit) and the partition's (digit_of_window) must agree entry for entry"""
+    ks = _crafted()
+    assert 150 <= len(ks) <= 300
+    n = 2000 + len(ks)
+    s = bytearray(C.sample_scalars(0xCA + c, n))
+    for i, k in enumerate(ks):  # spread through the random terms
+        at = 7 + i * (n // len(ks))
+        s[32 * at:32 * at + 32] = O.fe_to_bytes(k)
+    p = C.sample_points(0xCB, n)
+    assert _run(gpu_ctx, bytes(s), p, c) == C.msm_pippenger(bytes(s), p, 4)
+
+
+@pytest.mark.parametrize("c", [13, 16])
+def test_carry_chains_one_term_each(c, gpu_ctx):
+    """every crafted scalar alone, as one-term MSMs of one batch call"""
+    import torch
+
+    ks = _crafted()
+    p = C.sample_points(0xCC, len(ks))
+    ds = _dev(b"".join(O.fe_to_bytes(k) for k in ks))
+    dp = _dev(p)
+    out = torch.zeros(64 * len(ks), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    gpu_ctx.msm_pippenger_many_dev([ds.data_ptr() + 32 * i for i in range(len(ks))],
+                                   [dp.data_ptr() + 64 * i for i in range(len(ks))], [1] * len(ks), out.data_ptr(), window_bits=c)
+    gpu_ctx.sync()
+    got = bytes(out.cpu().numpy())
+    for i, k in enumerate(ks):
+        assert got[64 * i:64 * i + 64] == C.g1_mul(p[64 * i:64 * i + 64], O.fe_to_bytes(k)), (i, hex(k))
+
+
+@pytest.mark.parametrize("n", [2047, 2048, 2049, 16379])
+def test_tile_partition(n, gpu_ctx):
+    """one tile less one, one tile, one tile and one, and 8 tiles with a ragged last one (a multiple of 8 tiles takes the
+    xcd_tile permutation)"""
+    assert (n + E.TILE - 1) // E.TILE == {2047: 1, 2048: 1, 2049: 2, 16379: 8}[n]
+    s, p = C.sample_scalars(0xD7, n), C.sample_points(0xD8, n)
+    assert _run(gpu_ctx, s, p) == C.msm_pippenger(s, p, 4)
