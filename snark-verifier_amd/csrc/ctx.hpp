@@ -81,6 +81,7 @@ enum Slot {
   SLOT_POLY,         // the polynomial calls (poly.hip): the roots and totals of the scan's levels, a staged pass of terms
   SLOT_NTT,          // the transforms (ntt.hip): the tables of powers, then the working buffer of the passes
   SLOT_POLY_PROD,    // the column products (poly_prod.hip): a staged pass of affine terms, the totals of the scans' levels
+  SLOT_QUOTIENT,     // the quotient (quotient.hip): the staged program and constants, the vanishing polynomial's table
   SLOT_COUNT
 };
 
@@ -234,6 +235,10 @@ int ipa_dk_table_prepare(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, bool* have);
 // encoding.  The table must be built.  slices = 0: chosen so that m x slices workgroups fill the machine.
 int launch_msm_shared(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_scalars, size_t n, size_t m, uint32_t slices,
                       void* d_out64s);
+// enqueue steps that another unit chains (quotient.hip), arguments taken as checked: the transform of snarkv_ntt_dev
+// (ntt.hip; shift = 8 canonical words or null) and the batch inversion of snarkv_poly_batch_invert_dev (poly_prod.hip)
+int ntt_enqueue(snarkv_ctx* ctx, const void* d_in, void* d_out, uint32_t k, size_t count, bool inverse, const uint32_t* shift);
+int prod_batch_invert_enqueue(snarkv_ctx* ctx, const void* d_in, size_t n, void* d_out);
 int launch_validate(snarkv_ctx* ctx, const void* d_scalars, const void* d_points, size_t n, int* bad_host);
 int launch_g2_prepare(snarkv_ctx* ctx, const void* d_g2x2_256, void* d_prep);
 int launch_decide(snarkv_ctx* ctx, const void* d_prep, const void* d_accs, size_t m, void* d_ok, void* d_gt);

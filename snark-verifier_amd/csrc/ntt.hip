@@ -164,6 +164,11 @@ int enqueue(snarkv_ctx* ctx, const void* d_in, void* d_out, uint32_t k, size_t c
 
 }  // namespace
 
+// the same step for the units that chain a transform (ctx.hpp)
+int ntt_enqueue(snarkv_ctx* ctx, const void* d_in, void* d_out, uint32_t k, size_t count, bool inverse, const uint32_t* shift) {
+  return enqueue(ctx, d_in, d_out, k, count, inverse, shift);
+}
+
 }  // namespace snarkv
 
 using namespace snarkv;

@@ -388,6 +388,11 @@ int prod_enqueue_grand_product(snarkv_ctx* ctx, const void* d_f, size_t n, const
 
 }  // namespace
 
+// the same step for the units that chain a batch inversion (ctx.hpp)
+int prod_batch_invert_enqueue(snarkv_ctx* ctx, const void* d_in, size_t n, void* d_out) {
+  return prod_enqueue_batch_invert(ctx, d_in, n, d_out);
+}
+
 }  // namespace snarkv
 
 using namespace snarkv;

@@ -1,0 +1,311 @@
+// The quotient polynomial on the extended coset (include/snarkv_quotient.h): zero-padding in front of the forward transform,
+// the gate program run at every row, the division by the vanishing polynomial, and the four in one call.  Same source for
+// both curves, as poly_prod.hip; the arithmetic and its bounds are in quotient.h.
+//   k_quot_pad     out[p][i] = coeffs[p][i] for i < n, zero above: the words as they stand
+//   k_quot_eval    one row per lane: the program and the constants are uniform over the launch and come through uniform
+//                  loads (an instruction is decoded once per wave, its operand kinds are wave-uniform branches); a column
+//                  read at a rotation is consecutive across the lanes, the wrap is in the index (quot_row)
+//   k_quot_table   the 2^e values of the vanishing polynomial on the coset, canonical words, for the batch inversion
+//   k_quot_div     out[i] = in[i] table[i mod 2^e]
+//
+// The register file.  16 registers of 9 limbs are indexed by the instruction, at run time, so they cannot live in VGPRs.
+// They are in private memory: `Fr29 regs[16]`, 576 bytes per lane, which the compiler lays out dword-interleaved over the
+// lanes of a wave, so a register read is 9 coalesced dword accesses at a wave-uniform offset and stays in the vector cache.
+// The alternative, LDS limb-major, takes 36 KiB per wave: four waves per CU, one per SIMD, and the multiplier chain of
+// fr29_mul is latency-bound at that occupancy (fr29.h).  Private memory leaves the occupancy to the VGPRs.  A register access
+// is 36 dword accesses per instruction next to the 162 64-bit multiply-adds of one product.  Neither choice has been
+// measured against the other; DESIGN.md 3j has the resource table and the record of this one.
+#include <string.h>
+#include <vector>
+#include "ctx.hpp"
+#include "ipa_prover.hpp"
+#include "quotient.h"
+#include "../../include/snarkv_ntt.h"
+#include "../../include/snarkv_quotient.h"
+
+namespace snarkv {
+
+constexpr uint32_t kQuotThreads = 256;
+constexpr size_t kQuotMaxCount = 65535;  // columns per transform launch (snarkv_ntt.h)
+
+// layout of the context's SLOT_QUOTIENT
+enum : size_t {
+  QS_PROG = 0,                                                          // the staged program
+  QS_CONSTS = QS_PROG + sizeof(snarkv_quot_instr) * SNARKV_QUOT_MAX_INSTR,  // the constants, Fr29 in the Montgomery domain
+  QS_TABLE = (QS_CONSTS + sizeof(Fr29) * SNARKV_QUOT_MAX_CONSTS + 255) & ~(size_t)255,  // the vanishing table, 32 bytes each
+  QS_END = QS_TABLE + 32 * ((size_t)1 << SNARKV_QUOT_MAX_E),
+};
+static_assert(sizeof(snarkv_quot_instr) == 16, "the instruction format of the header");
+
+struct QuotColsDev {
+  const uint32_t* __restrict__ p;
+  __device__ __forceinline__ Fr29 load(size_t index) const { return ld_fr(p + 8 * index); }
+};
+
+// count x 2^log_n out of count x 2^k; the grid's y is the polynomial
+__global__ void __launch_bounds__(kQuotThreads) k_quot_pad(const uint32_t* __restrict__ in, uint32_t k, uint32_t log_n,
+                                                           uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * kQuotThreads + threadIdx.x;
+  if (i >> log_n) return;
+  uint4 a = make_uint4(0, 0, 0, 0), b = a;
+  if (!(i >> k)) {
+    const uint4* src = reinterpret_cast<const uint4*>(in + 8 * (((size_t)blockIdx.y << k) + i));
+    a = src[0], b = src[1];
+  }
+  uint4* dst = reinterpret_cast<uint4*>(out + 8 * (((size_t)blockIdx.y << log_n) + i));
+  dst[0] = a;
+  dst[1] = b;
+}
+
+__global__ void __launch_bounds__(kQuotThreads) k_quot_eval(const uint32_t* __restrict__ cols, uint32_t log_n, uint32_t e,
+                                                            const snarkv_quot_instr* __restrict__ prog, uint32_t n_instr,
+                                                            const Fr29* __restrict__ consts, uint32_t* __restrict__ out) {
+  const uint32_t row = blockIdx.x * kQuotThreads + threadIdx.x;
+  if (row >> log_n) return;
+  const QuotColsDev c = {cols};
+  Fr29 regs[SNARKV_QUOT_REGS];
+#pragma unroll 1
+  for (uint32_t pc = 0; pc < n_instr; ++pc) quot_step(prog[pc], regs, consts, c, row, e, log_n);
+  st_fr(out + 8 * (size_t)row, regs[prog[n_instr - 1].dst & (SNARKV_QUOT_REGS - 1u)]);
+}
+
+__global__ void __launch_bounds__(kQuotThreads) k_quot_table(Fr29 s_to_n, Fr29 root, uint32_t count, uint32_t* __restrict__ out) {
+  const uint32_t j = blockIdx.x * kQuotThreads + threadIdx.x;
+  if (j < count) st_fr(out + 8 * (size_t)j, quot_vanishing_entry(s_to_n, root, j));
+}
+
+// `in` may be `out`: every element is read by the thread that writes it
+__global__ void __launch_bounds__(kQuotThreads) k_quot_div(const uint32_t* in, uint32_t log_n, const uint32_t* __restrict__ table,
+                                                           uint32_t mask, uint32_t* out) {
+  const uint32_t i = blockIdx.x * kQuotThreads + threadIdx.x;
+  if (i >> log_n) return;
+  st_fr(out + 8 * (size_t)i, fr29_mul(ld_fr(in + 8 * (size_t)i), ld_fr(table + 8 * (size_t)(i & mask))));
+}
+
+namespace {
+
+uint32_t blocks_of(uint32_t log_n) { return (uint32_t)((((size_t)1 << log_n) + kQuotThreads - 1) / kQuotThreads); }
+
+bool overlap(const void* a, size_t an, const void* b, size_t bn) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return an && bn && (x < y ? y - x < an : x - y < bn);
+}
+bool aligned16(const void* p) { return p && (uintptr_t)p % 16 == 0; }
+// the bytes of `count` columns of 2^(k + e) elements for the overlap checks, which come before the lengths': no wrap for an
+// absurd shape
+size_t ext_bytes(uint32_t k, uint32_t e, size_t count) {
+  const uint64_t lg = (uint64_t)k + e;
+  const size_t col = lg > 40 ? (size_t)1 << 45 : (size_t)32 << lg;
+  return count > ((size_t)1 << 62) / col ? (size_t)1 << 62 : col * count;
+}
+
+bool below_r(const uint8_t* s32) {
+  constexpr uint32_t rw[8] = SNARKV_FR_R_LIMBS;
+  uint32_t w[8];
+  memcpy(w, s32, 32);
+  for (int i = 7; i >= 0; --i)
+    if (w[i] != rw[i]) return w[i] < rw[i];
+  return false;
+}
+bool is_zero(const uint8_t* s32) {
+  for (int i = 0; i < 32; ++i)
+    if (s32[i]) return false;
+  return true;
+}
+bool bad_shift(const char* call, const uint8_t* s32) {
+  if (s32 && !is_zero(s32)) return false;
+  set_last_error("%s: a shift that is %s", call, s32 ? "zero" : "null");
+  return true;
+}
+
+int refuse_overlap(const char* call, const char* what) {
+  set_last_error("%s: overlap: %s", call, what);
+  return SNARKV_ERR_ARG;
+}
+
+int check_shape(uint32_t k, uint32_t e) {
+  return e > SNARKV_QUOT_MAX_E || (uint64_t)k + e > SNARKV_API(ntt_max_k)() ? SNARKV_ERR_LENGTH : SNARKV_OK;
+}
+
+// every program fault of the header; without columns (n_cols = 0) there is nothing to index: the call is empty
+int check_program(const char* call, const snarkv_quot_instr* prog, size_t n_instr, size_t n_consts, size_t n_cols) {
+  uint32_t written = 0;
+  for (size_t pc = 0; pc < n_instr; ++pc) {
+    const snarkv_quot_instr& in = prog[pc];
+    const char* fault = nullptr;
+    if (in.op > SNARKV_QUOT_FMA) fault = "an unknown op";
+    else if (in.zero != 0) fault = "the reserved field is not zero";
+    else if (in.op != SNARKV_QUOT_FMA && in.c != 0) fault = "c is not zero on a two-operand op";
+    else if (in.dst >= SNARKV_QUOT_REGS) fault = "the destination is no register";
+    const uint32_t words[3] = {in.a, in.b, in.c};
+    for (uint32_t o = 0; !fault && o < quot_operands(in.op); ++o) {
+      const uint32_t w = words[o], kind = quot_kind(w);
+      if (kind == kQuotKindReg) {
+        if (quot_index(w) >= SNARKV_QUOT_REGS) fault = "an operand names no register";
+        else if (!(written >> quot_index(w) & 1u)) fault = "a register is read before it is written";
+      } else if (kind == kQuotKindConst) {
+        if (quot_index(w) >= n_consts) fault = "a constant index beyond n_consts";
+      } else if (kind == kQuotKindCol) {
+        if (n_cols && quot_col(w) >= n_cols) fault = "a column index beyond n_cols";
+      } else {
+        fault = "an operand of kind 3";
+      }
+    }
+    if (fault) {
+      set_last_error("%s: instruction %zu: %s", call, pc, fault);
+      return SNARKV_ERR_ARG;
+    }
+    written |= 1u << in.dst;
+  }
+  return SNARKV_OK;
+}
+
+bool all_below_r(const uint8_t* s32, size_t count) {
+  for (size_t j = 0; j < count; ++j)
+    if (!below_r(s32 + 32 * j)) return false;
+  return true;
+}
+
+int check_program_lengths(size_t n_cols, size_t n_instr, size_t n_consts) {
+  return n_instr > SNARKV_QUOT_MAX_INSTR || n_consts > SNARKV_QUOT_MAX_CONSTS || n_cols > SNARKV_QUOT_MAX_COLS ? SNARKV_ERR_LENGTH
+                                                                                                                  : SNARKV_OK;
+}
+
+int slot_of(snarkv_ctx* ctx, uint8_t** scr) {
+  void* d;
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_QUOTIENT, QS_END, &d));
+  *scr = (uint8_t*)d;
+  return SNARKV_OK;
+}
+
+// The enqueue steps; arguments are taken as checked.  The slot has one size, so it does not move between the steps.
+
+int quot_enqueue_extend(snarkv_ctx* ctx, const void* d_coeffs, uint32_t k, uint32_t e, size_t count, const uint32_t* shift,
+                        void* d_out) {
+  const uint32_t log_n = k + e;
+  for (size_t p0 = 0; p0 < count; p0 += kQuotMaxCount) {  // the transform takes 65 535 polynomials per call
+    const size_t c = count - p0 < kQuotMaxCount ? count - p0 : kQuotMaxCount;
+    const uint8_t* in = (const uint8_t*)d_coeffs + ((p0 * 32) << k);
+    uint8_t* out = (uint8_t*)d_out + ((p0 * 32) << log_n);
+    hipLaunchKernelGGL(k_quot_pad, dim3(blocks_of(log_n), (uint32_t)c), dim3(kQuotThreads), 0, ctx->stream, (const uint32_t*)in, k,
+                       log_n, (uint32_t*)out);
+    SNARKV_HIP(hipGetLastError());
+    SNARKV_TRY(ntt_enqueue(ctx, out, out, log_n, c, false, shift));
+  }
+  return SNARKV_OK;
+}
+
+int quot_enqueue_eval(snarkv_ctx* ctx, const void* d_cols, uint32_t k, uint32_t e, const snarkv_quot_instr* prog, size_t n_instr,
+                      const uint8_t* consts32, size_t n_consts, void* d_out) {
+  uint8_t* scr;
+  SNARKV_TRY(slot_of(ctx, &scr));
+  std::vector<Fr29> consts(n_consts);
+  for (size_t j = 0; j < n_consts; ++j) {
+    uint32_t w[8];
+    memcpy(w, consts32 + 32 * j, 32);
+    consts[j] = fr29_from_canonical(w);
+  }
+  // host arrays in pageable memory: the copies have left them when hipMemcpyAsync returns
+  SNARKV_HIP(hipMemcpyAsync(scr + QS_PROG, prog, sizeof(snarkv_quot_instr) * n_instr, hipMemcpyHostToDevice, ctx->stream));
+  if (n_consts)
+    SNARKV_HIP(hipMemcpyAsync(scr + QS_CONSTS, consts.data(), sizeof(Fr29) * n_consts, hipMemcpyHostToDevice, ctx->stream));
+  const uint32_t log_n = k + e;
+  hipLaunchKernelGGL(k_quot_eval, dim3(blocks_of(log_n)), dim3(kQuotThreads), 0, ctx->stream, (const uint32_t*)d_cols, log_n, e,
+                     (const snarkv_quot_instr*)(scr + QS_PROG), (uint32_t)n_instr, (const Fr29*)(scr + QS_CONSTS),
+                     (uint32_t*)d_out);
+  SNARKV_HIP(hipGetLastError());
+  return SNARKV_OK;
+}
+
+int quot_enqueue_div(snarkv_ctx* ctx, const void* d_in, uint32_t k, uint32_t e, const uint32_t* shift, void* d_out) {
+  uint8_t* scr;
+  SNARKV_TRY(slot_of(ctx, &scr));
+  uint32_t* table = (uint32_t*)(scr + QS_TABLE);
+  const uint32_t entries = 1u << e, log_n = k + e;
+  hipLaunchKernelGGL(k_quot_table, dim3((entries + kQuotThreads - 1) / kQuotThreads), dim3(kQuotThreads), 0, ctx->stream,
+                     quot_shift_to_n(fr29_from_canonical(shift), k), quot_coset_root(e), entries, table);
+  SNARKV_HIP(hipGetLastError());
+  SNARKV_TRY(prod_batch_invert_enqueue(ctx, table, entries, table));  // the one field inversion of the call
+  hipLaunchKernelGGL(k_quot_div, dim3(blocks_of(log_n)), dim3(kQuotThreads), 0, ctx->stream, (const uint32_t*)d_in, log_n,
+                     (const uint32_t*)table, entries - 1u, (uint32_t*)d_out);
+  SNARKV_HIP(hipGetLastError());
+  return SNARKV_OK;
+}
+
+}  // namespace
+
+}  // namespace snarkv
+
+using namespace snarkv;
+
+extern "C" {
+
+int SNARKV_API(poly_extend_dev)(snarkv_ctx* ctx, const void* d_coeffs32, uint32_t k, uint32_t e, size_t count,
+                                const uint8_t* shift32, void* d_out32) {
+  if (!ctx || !aligned16(d_coeffs32) || !aligned16(d_out32) || bad_shift("poly_extend", shift32)) return SNARKV_ERR_ARG;
+  if (overlap(d_out32, ext_bytes(k, e, count), d_coeffs32, ext_bytes(k, 0, count)))
+    return refuse_overlap("poly_extend", "out is disjoint from the coefficients");
+  if (!below_r(shift32)) return SNARKV_ERR_ENCODING;
+  if (count == 0) return SNARKV_ERR_EMPTY;
+  SNARKV_TRY(check_shape(k, e));
+  if (count > kQuotMaxCount) return SNARKV_ERR_LENGTH;
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  uint32_t shift[8];
+  memcpy(shift, shift32, 32);
+  return quot_enqueue_extend(ctx, d_coeffs32, k, e, count, shift, d_out32);
+}
+
+int SNARKV_API(quotient_eval_dev)(snarkv_ctx* ctx, const void* d_cols32, uint32_t k, uint32_t e, size_t n_cols,
+                                  const snarkv_quot_instr* prog, size_t n_instr, const uint8_t* consts32, size_t n_consts,
+                                  void* d_out32) {
+  if (!ctx || !aligned16(d_cols32) || !aligned16(d_out32) || !prog || (n_consts && !consts32)) return SNARKV_ERR_ARG;
+  SNARKV_TRY(check_program("quotient_eval", prog, n_instr, n_consts, n_cols));
+  if (overlap(d_out32, ext_bytes(k, e, 1), d_cols32, ext_bytes(k, e, n_cols)))
+    return refuse_overlap("quotient_eval", "out lies in no part of the columns");
+  if (!all_below_r(consts32, n_consts)) return SNARKV_ERR_ENCODING;
+  if (n_cols == 0 || n_instr == 0) return SNARKV_ERR_EMPTY;
+  SNARKV_TRY(check_shape(k, e));
+  SNARKV_TRY(check_program_lengths(n_cols, n_instr, n_consts));
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  return quot_enqueue_eval(ctx, d_cols32, k, e, prog, n_instr, consts32, n_consts, d_out32);
+}
+
+int SNARKV_API(poly_div_vanishing_dev)(snarkv_ctx* ctx, const void* d_in32, uint32_t k, uint32_t e, const uint8_t* shift32,
+                                       void* d_out32) {
+  if (!ctx || !aligned16(d_in32) || !aligned16(d_out32) || bad_shift("poly_div_vanishing", shift32)) return SNARKV_ERR_ARG;
+  if (d_in32 != d_out32 && overlap(d_out32, ext_bytes(k, e, 1), d_in32, ext_bytes(k, e, 1)))
+    return refuse_overlap("poly_div_vanishing", "out is the input itself or disjoint from it");
+  if (!below_r(shift32)) return SNARKV_ERR_ENCODING;
+  SNARKV_TRY(check_shape(k, e));
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  uint32_t shift[8];
+  memcpy(shift, shift32, 32);
+  return quot_enqueue_div(ctx, d_in32, k, e, shift, d_out32);
+}
+
+int SNARKV_API(quotient_dev)(snarkv_ctx* ctx, const void* d_coeffs32, uint32_t k, uint32_t e, size_t n_cols,
+                             const snarkv_quot_instr* prog, size_t n_instr, const uint8_t* consts32, size_t n_consts,
+                             const uint8_t* shift32, const uint8_t* shift_inv32, void* d_work32, void* d_h32) {
+  if (!ctx || !aligned16(d_coeffs32) || !aligned16(d_work32) || !aligned16(d_h32) || !prog || (n_consts && !consts32))
+    return SNARKV_ERR_ARG;
+  if (bad_shift("quotient", shift32) || bad_shift("quotient", shift_inv32)) return SNARKV_ERR_ARG;
+  SNARKV_TRY(check_program("quotient", prog, n_instr, n_consts, n_cols));
+  const size_t coeffs = ext_bytes(k, 0, n_cols), work = ext_bytes(k, e, n_cols), h = ext_bytes(k, e, 1);
+  if (overlap(d_work32, work, d_coeffs32, coeffs) || overlap(d_h32, h, d_coeffs32, coeffs) || overlap(d_h32, h, d_work32, work))
+    return refuse_overlap("quotient", "work, h and the coefficients are pairwise disjoint");
+  if (!all_below_r(consts32, n_consts) || !below_r(shift32) || !below_r(shift_inv32)) return SNARKV_ERR_ENCODING;
+  if (n_cols == 0 || n_instr == 0) return SNARKV_ERR_EMPTY;
+  SNARKV_TRY(check_shape(k, e));
+  SNARKV_TRY(check_program_lengths(n_cols, n_instr, n_consts));
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  uint32_t shift[8], shift_inv[8];
+  memcpy(shift, shift32, 32);
+  memcpy(shift_inv, shift_inv32, 32);
+  // the three public calls and the inverse transform, back to back
+  SNARKV_TRY(quot_enqueue_extend(ctx, d_coeffs32, k, e, n_cols, shift, d_work32));
+  SNARKV_TRY(quot_enqueue_eval(ctx, d_work32, k, e, prog, n_instr, consts32, n_consts, d_h32));
+  SNARKV_TRY(quot_enqueue_div(ctx, d_h32, k, e, shift, d_h32));
+  return ntt_enqueue(ctx, d_h32, d_h32, k + e, 1, true, shift_inv);
+}
+
+}  // extern "C"
