@@ -45,6 +45,7 @@ from . import poly  # noqa: F401,E402  (resident polynomials: linear combination
 from . import ntt  # noqa: F401,E402  (forward, inverse and coset transforms of resident polynomials: include/snarkv_ntt.h)
 from . import poly_prod  # noqa: F401,E402  (column products: batch inversion, grand product, permutation Z: include/snarkv_poly_prod.h)
 from . import quotient  # noqa: F401,E402  (the quotient on the extended coset: extension, gate program, vanishing division: include/snarkv_quotient.h)
+from . import lookup  # noqa: F401,E402  (the lookup argument: sort, permuted columns, product Z: include/snarkv_lookup.h)
 from . import ipa_multiopen  # noqa: F401,E402  (the Bgh19 multi-open prover in one call: include/snarkv_ipa_multiopen.h)
 
 __all__ = [
@@ -58,6 +59,7 @@ __all__ = [
     "ntt",
     "poly_prod",
     "quotient",
+    "lookup",
     "ipa_multiopen",
     "IpaProver",
     "Context",

@@ -15,7 +15,7 @@ BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsnarkv_amd.so")
 UNITS = ["ctx", "msm_api", "capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "ipa_prover", "mgpu",
          "decompress", "msm_shared", "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen", "ntt",
-         "poly_prod", "quotient"]
+         "poly_prod", "quotient", "lookup"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
@@ -35,6 +35,7 @@ def _deps():
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ntt.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_poly_prod.h"))
     hdrs.append(os.path.join(HERE, "..", "include", "snarkv_quotient.h"))
+    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_lookup.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
 
@@ -67,6 +68,7 @@ def build(verbose=False):
         devtest += [ex.submit(build_hosttest_ntt, c) for c in ("bn254", "pallas")]
         devtest += [ex.submit(build_hosttest_poly_prod, c) for c in ("bn254", "pallas")]
         devtest += [ex.submit(build_hosttest_quotient, c) for c in ("bn254", "pallas")]
+        devtest += [ex.submit(build_hosttest_lookup, c) for c in ("bn254", "pallas")]
         res = list(ex.map(lambda j: _compile(j[0], verbose, j[1], j[2]), jobs))
         for d in devtest:
             d.result()
@@ -87,7 +89,7 @@ def _link(lib, res, extra):
 
 # The pasta build of the curve-generic units (csrc/pallas.hip explains the flags, csrc/ctx.hpp the policy they select).
 PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover", "decompress_pallas", "msm_shared",
-                "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen", "ntt", "poly_prod", "quotient"]
+                "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen", "ntt", "poly_prod", "quotient", "lookup"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
 
@@ -177,6 +179,21 @@ def build_hosttest_quotient(curve):
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)
         raise RuntimeError("host build failed: hosttest_quotient.cpp (%s)" % curve)
+    return out
+
+
+# The lookup argument's comparison, merge path, tiled sort and permute rule (csrc/lookup.h) for the host
+# (tests/hosttest/hosttest_lookup.cpp), one library per curve.
+def build_hosttest_lookup(curve):
+    out = os.path.join(HOSTTEST_DIR, "libhosttest_lookup_%s.so" % curve)
+    src = os.path.join(HOSTTEST_DIR, "hosttest_lookup.cpp")
+    if os.path.exists(out) and os.path.getmtime(out) >= max(_deps(), os.path.getmtime(src)):
+        return out
+    flags = ["-DSNARKV_CURVE_PALLAS"] if curve == "pallas" else []
+    r = subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC"] + flags + ["-o", out, src], capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout + r.stderr)
+        raise RuntimeError("host build failed: hosttest_lookup.cpp (%s)" % curve)
     return out
 
 

@@ -82,6 +82,7 @@ enum Slot {
   SLOT_NTT,          // the transforms (ntt.hip): the tables of powers, then the working buffer of the passes
   SLOT_POLY_PROD,    // the column products (poly_prod.hip): a staged pass of affine terms, the totals of the scans' levels
   SLOT_QUOTIENT,     // the quotient (quotient.hip): the staged program and constants, the vanishing polynomial's table
+  SLOT_LOOKUP,       // the lookup argument (lookup.hip): the sort's partition points, the flags and the totals of the count scans
   SLOT_COUNT
 };
 
@@ -239,6 +240,12 @@ int launch_msm_shared(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_sc
 // (ntt.hip; shift = 8 canonical words or null) and the batch inversion of snarkv_poly_batch_invert_dev (poly_prod.hip)
 int ntt_enqueue(snarkv_ctx* ctx, const void* d_in, void* d_out, uint32_t k, size_t count, bool inverse, const uint32_t* shift);
 int prod_batch_invert_enqueue(snarkv_ctx* ctx, const void* d_in, size_t n, void* d_out);
+// ... and, for the lookup product (lookup.hip), the steps of snarkv_poly_mul_dev, snarkv_poly_prod_affine_dev and
+// snarkv_poly_grand_product_dev
+int prod_mul_enqueue(snarkv_ctx* ctx, const void* d_a, const void* d_b, size_t n, void* d_out);
+int prod_affine_enqueue(snarkv_ctx* ctx, const void* d_polys, size_t n, const uint32_t* idx_a, const uint32_t* idx_b,
+                        const uint8_t* betas32, const uint8_t* gammas32, size_t count, void* d_out);
+int prod_grand_product_enqueue(snarkv_ctx* ctx, const void* d_f, size_t n, const void* d_start, void* d_out, void* d_total);
 int launch_validate(snarkv_ctx* ctx, const void* d_scalars, const void* d_points, size_t n, int* bad_host);
 int launch_g2_prepare(snarkv_ctx* ctx, const void* d_g2x2_256, void* d_prep);
 int launch_decide(snarkv_ctx* ctx, const void* d_prep, const void* d_accs, size_t m, void* d_ok, void* d_gt);

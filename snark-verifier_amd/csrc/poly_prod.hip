@@ -392,6 +392,17 @@ int prod_enqueue_grand_product(snarkv_ctx* ctx, const void* d_f, size_t n, const
 int prod_batch_invert_enqueue(snarkv_ctx* ctx, const void* d_in, size_t n, void* d_out) {
   return prod_enqueue_batch_invert(ctx, d_in, n, d_out);
 }
+// ... and for the unit that chains all four (lookup.hip)
+int prod_mul_enqueue(snarkv_ctx* ctx, const void* d_a, const void* d_b, size_t n, void* d_out) {
+  return prod_enqueue_mul(ctx, d_a, d_b, n, d_out);
+}
+int prod_affine_enqueue(snarkv_ctx* ctx, const void* d_polys, size_t n, const uint32_t* idx_a, const uint32_t* idx_b,
+                        const uint8_t* betas32, const uint8_t* gammas32, size_t count, void* d_out) {
+  return prod_enqueue_affine(ctx, d_polys, n, idx_a, idx_b, betas32, gammas32, count, d_out);
+}
+int prod_grand_product_enqueue(snarkv_ctx* ctx, const void* d_f, size_t n, const void* d_start, void* d_out, void* d_total) {
+  return prod_enqueue_grand_product(ctx, d_f, n, d_start, d_out, d_total);
+}
 
 }  // namespace snarkv
 

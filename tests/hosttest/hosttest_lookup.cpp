@@ -1,0 +1,214 @@
+// Host build of the lookup argument's shared logic (snark-verifier_amd/csrc/lookup.h, the SNARKV_HD source the device
+// compiles), driven the way lookup.hip drives it, with tiles and scan blocks small enough that every border is hit: the tile
+// sorted by rounds of lk_tile_dest (all places computed, then all keys moved, as the barrier between them orders it), the
+// merge passes chunk by chunk with the partition points of lk_merge_path, the staged ranges and the lanes' own diagonals and
+// serial merges, the ping-pong between out and work chosen by the parity of the passes; the flags, the count scans over
+// levels with carries, the compaction of the leftovers and the gather.  One library per curve (-DSNARKV_CURVE_PALLAS),
+// built by snark-verifier_amd/build.py.  Test infrastructure only.
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+#include <vector>
+#include "../../snark-verifier_amd/csrc/lookup.h"
+
+using namespace snarkv;
+
+namespace {
+
+struct Keys {  // a getter over keys in memory, 8 words each
+  const uint32_t* p;
+  LkKey operator()(uint32_t i) const {
+    LkKey k;
+    memcpy(k.w, p + 8 * (size_t)i, 32);
+    return k;
+  }
+};
+void put(uint32_t* p, size_t i, const LkKey& k) { memcpy(p + 8 * i, k.w, 32); }
+
+// k_lk_tile_sort
+void tile_sort(const uint32_t* in, uint32_t n, uint32_t tile, uint32_t* out) {
+  for (uint32_t base = 0; base < n; base += tile) {
+    const uint32_t len = n - base < tile ? n - base : tile;
+    std::vector<uint32_t> sh(8 * (size_t)tile, 0xCCCCCCCCu);
+    for (uint32_t i = 0; i < len; ++i) put(sh.data(), i, lk_canon(Keys{in}(base + i).w));
+    const Keys t = {sh.data()};
+    for (uint32_t run = 1; run < len; run *= 2) {
+      std::vector<LkKey> key(len);
+      std::vector<uint32_t> dest(len);
+      for (uint32_t i = 0; i < len; ++i) key[i] = t(i), dest[i] = lk_tile_dest(t, len, run, i, key[i]);
+      for (uint32_t i = 0; i < len; ++i) put(sh.data(), dest[i], key[i]);
+    }
+    for (uint32_t i = 0; i < len; ++i) put(out, (size_t)base + i, t(i));
+  }
+}
+
+// k_lk_partition and k_lk_merge: `tile` outputs per chunk, `lane_e` per lane
+void merge_pass(const uint32_t* src, uint32_t n, uint32_t run, uint32_t tile, uint32_t lane_e, uint32_t* dst) {
+  const uint32_t chunks = (n + tile - 1) / tile;
+  std::vector<uint32_t> part(chunks);
+  for (uint32_t c = 0; c < chunks; ++c) {
+    const LkMergeGeom g = lk_merge_geom(n, run, tile, c);
+    part[c] = lk_merge_path(Keys{src + 8 * (size_t)g.a0}, g.na, Keys{src + 8 * (size_t)g.b0}, g.nb, g.diag);
+  }
+  for (uint32_t c = 0; c < chunks; ++c) {
+    const LkMergeGeom g = lk_merge_geom(n, run, tile, c);
+    const uint32_t start = c * tile, total = g.na + g.nb, count = total - g.diag < tile ? total - g.diag : tile;
+    const uint32_t a_lo = part[c], a_hi = g.diag + count == total ? g.na : part[c + 1];
+    const uint32_t b_lo = g.diag - a_lo, b_hi = g.diag + count - a_hi;
+    const uint32_t ca = a_hi - a_lo, cb = b_hi - b_lo;
+    std::vector<uint32_t> sh(8 * (size_t)tile, 0xCCCCCCCCu);
+    const Keys ga = {src + 8 * ((size_t)g.a0 + a_lo)}, gb = {src + 8 * ((size_t)g.b0 + b_lo)};
+    for (uint32_t i = 0; i < count; ++i) put(sh.data(), i, i < ca ? ga(i) : gb(i - ca));
+    const Keys a = {sh.data()}, b = {sh.data() + 8 * (size_t)ca};
+    for (uint32_t d0 = 0; d0 < count; d0 += lane_e) {  // one lane
+      const uint32_t d1 = d0 + lane_e < count ? d0 + lane_e : count;
+      uint32_t ai = lk_merge_path(a, ca, b, cb, d0), bi = d0 - ai;
+      for (uint32_t d = d0; d < d1; ++d) {
+        const bool has_a = ai < ca, has_b = bi < cb;
+        const LkKey ka = a(has_a ? ai : 0u), kb = has_b ? b(bi) : ka;
+        const bool take = lk_take_a(has_a, has_b, ka, kb);
+        put(dst, (size_t)start + d, take ? ka : kb);
+        ai += take ? 1u : 0u;
+        bi += take ? 0u : 1u;
+      }
+    }
+  }
+}
+
+// sort_enqueue; `in` may be `out`
+void sort(const uint32_t* in, uint32_t n, uint32_t tile, uint32_t lane_e, uint32_t* work, uint32_t* out) {
+  uint32_t* cur = lk_passes(n, tile) % 2 ? work : out;
+  tile_sort(in, n, tile, cur);
+  for (uint64_t run = tile; run < n; run *= 2) {
+    uint32_t* other = cur == out ? work : out;
+    merge_pass(cur, n, (uint32_t)run, tile, lane_e, other);
+    cur = other;
+  }
+}
+
+// lk_wg_scan: the inclusive scan of one count per lane
+template <uint32_t T>
+void wg_scan(std::vector<LkCount>& s) {
+  typedef ProdBlock<T, 1> S;
+  for (uint32_t step = 0; step < S::steps(); ++step) {
+    const std::vector<LkCount> prev = s;
+    for (uint32_t lane = 0; lane < T; ++lane)
+      if (S::has_left(lane, step)) s[lane] = lk_add(prev[lane], prev[lane - S::distance(step)]);
+  }
+}
+
+// one block of k_lk_up / k_lk_down / k_lk_place: the counts of the block -> each element's exclusive prefix and the total
+template <uint32_t T, uint32_t E>
+LkCount block_scan(const LkCount* in, uint32_t b, uint32_t n, std::vector<LkCount>* prefix) {
+  typedef ProdBlock<T, E> B;
+  const uint32_t len = B::block_len(b, n);
+  std::vector<LkCount> lane_total(T);
+  std::vector<LkCount> p(T * E);
+  for (uint32_t lane = 0; lane < T; ++lane) {
+    LkCount x[E];
+    for (uint32_t j = 0; j < E; ++j) {
+      x[j].rep = 0, x[j].left = 0;
+      if (B::has(lane, j, len)) x[j] = in[B::index(b, lane, j)];
+    }
+    lk_lane_prefix<E>(x, &p[lane * E], lane_total[lane]);
+  }
+  wg_scan<T>(lane_total);
+  prefix->assign(T * E, LkCount{0, 0});
+  for (uint32_t lane = 0; lane < T; ++lane)
+    for (uint32_t j = 0; j < E; ++j) {
+      LkCount before = {0, 0};
+      if (lane) before = lane_total[lane - 1];
+      (*prefix)[lane * E + j] = lk_add(before, p[lane * E + j]);
+    }
+  return lane_total[T - 1];
+}
+
+// permute_enqueue after the two sorts: a = A', s = the sorted table
+template <uint32_t T, uint32_t E>
+void permute(const uint32_t* a, const uint32_t* s, uint32_t u, uint32_t* leftovers, uint32_t* perm_table, uint32_t* status) {
+  typedef ProdBlock<T, E> B;
+  const Keys ga = {a}, gs = {s};
+  std::vector<uint8_t> flags(u);
+  std::vector<LkCount> count(u);
+  for (uint32_t i = 0; i < u; ++i) flags[i] = (uint8_t)lk_flags(ga, gs, u, i), count[i] = lk_count_of(flags[i]);
+  // the levels: seq[0] = the totals of the blocks of rows, ... until one entry
+  std::vector<std::vector<LkCount>> seq;
+  std::vector<LkCount> prefix;
+  {
+    std::vector<LkCount> t(B::blocks(u));
+    for (uint32_t b = 0; b < t.size(); ++b) t[b] = block_scan<T, E>(count.data(), b, u, &prefix);
+    seq.push_back(t);
+  }
+  while (seq.back().size() > 1) {
+    const std::vector<LkCount>& lo = seq.back();
+    std::vector<LkCount> t(B::blocks((uint32_t)lo.size()));
+    for (uint32_t b = 0; b < t.size(); ++b) t[b] = block_scan<T, E>(lo.data(), b, (uint32_t)lo.size(), &prefix);
+    seq.push_back(t);
+  }
+  LkCount grand = {0, 0};
+  for (size_t l = seq.size(); l-- > 0;) {  // k_lk_down
+    const bool top = l + 1 == seq.size();
+    std::vector<LkCount> scanned(seq[l].size());
+    for (uint32_t b = 0; b < B::blocks((uint32_t)seq[l].size()); ++b) {
+      const LkCount total = block_scan<T, E>(seq[l].data(), b, (uint32_t)seq[l].size(), &prefix);
+      for (uint32_t e = 0; e < B::block_len(b, (uint32_t)seq[l].size()); ++e)
+        scanned[b * B::B + e] = top ? prefix[e] : lk_add(prefix[e], seq[l + 1][b]);
+      if (top) grand = total, lk_status(total, u, status);
+    }
+    seq[l] = scanned;
+  }
+  for (int gather = 0; gather < 2; ++gather)  // k_lk_place<false>, then k_lk_place<true>
+    for (uint32_t b = 0; b < B::blocks(u); ++b) {
+      block_scan<T, E>(count.data(), b, u, &prefix);
+      for (uint32_t e = 0; e < B::block_len(b, u); ++e) {
+        const uint32_t i = b * B::B + e;
+        const LkCount at = lk_add(prefix[e], seq[0][b]);
+        if (gather) put(perm_table, i, count[i].rep ? Keys{leftovers}(lk_leftover_of(grand.rep, at.rep)) : ga(i));
+        else if (count[i].left) put(leftovers, at.left, gs(i));
+      }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* hl_curve() {
+#if defined(SNARKV_CURVE_PALLAS)
+  return "pallas";
+#else
+  return "bn254";
+#endif
+}
+
+int hl_less(const uint32_t* a, const uint32_t* b) { return lk_less(Keys{a}(0), Keys{b}(0)) ? 1 : 0; }
+int hl_equal(const uint32_t* a, const uint32_t* b) { return lk_equal(Keys{a}(0), Keys{b}(0)) ? 1 : 0; }
+void hl_canon(const uint32_t* in, uint32_t* out) { put(out, 0, lk_canon(in)); }
+
+uint32_t hl_merge_path(const uint32_t* a, uint32_t na, const uint32_t* b, uint32_t nb, uint32_t diag) {
+  return lk_merge_path(Keys{a}, na, Keys{b}, nb, diag);
+}
+uint32_t hl_passes(uint32_t n, uint32_t tile) { return lk_passes(n, tile); }
+
+// in, work, out: n x 8 words; in may be out
+void hl_sort(const uint32_t* in, uint32_t n, uint32_t tile, uint32_t lane_e, uint32_t* work, uint32_t* out) {
+  sort(in, n, tile, lane_e, work, out);
+}
+
+// input, table, perm_input, perm_table: u x 8 words; work: 2u x 8 words; status: 4 words.  block: 2, 3, 4 or 8 rows per
+// block of the scans (lanes x elements: 2 x 1, 3 x 1, 2 x 2, 4 x 2).  -> 0, or -1 for another block size
+int hl_permute(const uint32_t* input, const uint32_t* table, uint32_t u, uint32_t tile, uint32_t lane_e, uint32_t block,
+               uint32_t* work, uint32_t* perm_input, uint32_t* perm_table, uint32_t* status) {
+  uint32_t* sorted_table = work;
+  uint32_t* leftovers = work + 8 * (size_t)u;
+  sort(input, u, tile, lane_e, leftovers, perm_input);
+  sort(table, u, tile, lane_e, perm_table, sorted_table);
+  if (block == 2) permute<2, 1>(perm_input, sorted_table, u, leftovers, perm_table, status);
+  else if (block == 3) permute<3, 1>(perm_input, sorted_table, u, leftovers, perm_table, status);
+  else if (block == 4) permute<2, 2>(perm_input, sorted_table, u, leftovers, perm_table, status);
+  else if (block == 8) permute<4, 2>(perm_input, sorted_table, u, leftovers, perm_table, status);
+  else return -1;
+  return 0;
+}
+
+}  // extern "C"
