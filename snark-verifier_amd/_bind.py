@@ -1,5 +1,6 @@
-"""What the ctypes modules of the IPA headers (`ipa_prover`, `ipa_batch`, `ipa_fold`, `ipa_create`, `ipa_multiopen`) share:
-the binder of a module's own tables to a library, and the argument encoders and output buffers of the one-call provers.
+"""What the ctypes modules of the IPA headers (`ipa_prover`, `ipa_batch`, `ipa_fold`, `ipa_create`, `ipa_multiopen`) and of
+the resident-polynomial headers (`poly`, `ntt`, `poly_prod`, `quotient`, `lookup`) share: the binder of a module's own tables
+to a library, the argument encoders, and the output buffers of the one-call provers.
 The tables stay with their modules, one per header; this module knows no function name.
 """
 import ctypes
@@ -78,6 +79,28 @@ def vec(v):
     if v is None or isinstance(v, (bytes, bytearray)):
         return v
     return b"".join(fe(int(c)) for c in v)
+
+
+def addr(p):
+    """a device address: an int or anything with `data_ptr()`, None stays None"""
+    if p is None:
+        return None
+    return ctypes.c_void_p(int(p.data_ptr() if hasattr(p, "data_ptr") else p))
+
+
+def u32s(idx):
+    """an index array; an empty list still gives an address"""
+    return (ctypes.c_uint32 * max(len(idx), 1))(*idx)
+
+
+def scalars(vals):
+    """scalars back to back; an empty list still gives an address"""
+    return b"".join(fe(v) for v in vals) or b"\x00"
+
+
+def signatures(shapes):
+    """a module's table under the names of both libraries"""
+    return {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in shapes.items()}
 
 
 def prove(a, fn, k, cap, *args):

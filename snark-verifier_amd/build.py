@@ -21,21 +21,14 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", 
 FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
 
 
+# the public headers the device units include (include/; the host mirror's are in _host_stale)
+DEVICE_HEADERS = ("amd", "pallas", "pallas_decompress", "ipa_prover", "ipa_batch", "ipa_fold", "ipa_create", "poly", "ipa_multiopen",
+                  "ntt", "poly_prod", "quotient", "lookup")
+
+
 def _deps():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp", ".inc"))]
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_amd.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_pallas.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_pallas_decompress.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_prover.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_batch.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_fold.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_create.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_poly.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ipa_multiopen.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_ntt.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_poly_prod.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_quotient.h"))
-    hdrs.append(os.path.join(HERE, "..", "include", "snarkv_lookup.h"))
+    hdrs += [os.path.join(HERE, "..", "include", "snarkv_%s.h" % h) for h in DEVICE_HEADERS]
     return max(os.path.getmtime(h) for h in hdrs)
 
 
@@ -63,12 +56,7 @@ def build(verbose=False):
     jobs = [(u, (), "") for u in UNITS] + [(u, tuple(PALLAS_FLAGS), "_pallas") for u in PALLAS_UNITS]
     with ThreadPoolExecutor(max_workers=min(len(jobs) + len(DEVTEST_FLAVOURS), os.cpu_count() or 4)) as ex:
         devtest = [ex.submit(build_devtest, f) for f in DEVTEST_FLAVOURS]  # the test-only device units ride in the same pool
-        devtest += [ex.submit(build_hosttest_curve, c) for c in ("bn254", "pallas")]
-        devtest += [ex.submit(build_hosttest_poly, c) for c in ("bn254", "pallas")]
-        devtest += [ex.submit(build_hosttest_ntt, c) for c in ("bn254", "pallas")]
-        devtest += [ex.submit(build_hosttest_poly_prod, c) for c in ("bn254", "pallas")]
-        devtest += [ex.submit(build_hosttest_quotient, c) for c in ("bn254", "pallas")]
-        devtest += [ex.submit(build_hosttest_lookup, c) for c in ("bn254", "pallas")]
+        devtest += [ex.submit(build_hosttest, n, c) for n in HOSTTESTS for c in ("bn254", "pallas")]
         res = list(ex.map(lambda j: _compile(j[0], verbose, j[1], j[2]), jobs))
         for d in devtest:
             d.result()
@@ -106,95 +94,39 @@ def devtest_sources():
     return [os.path.join(DEVTEST_DIR, "devtest.hip"), os.path.join(DEVTEST_DIR, "..", "hosttest", "curve_ops.h")]
 
 
-# The same operations for the host (tests/hosttest/hosttest_curve.cpp: the plain-C bodies, plus the lane-by-lane emulation of
-# the decider's rounds and the dumps of its generated programs), one library per curve, next to its source.
+# Host builds of the SNARKV_HD sources (tests/hosttest/hosttest_<name>.cpp), one library per curve, next to their source.
+#   curve      the field and group operations of devtest.hip as plain C, the decider's rounds lane by lane
+#   poly       the blocked scan of the polynomial division (csrc/poly_scan.h), the multi-open prover's query-set grouping
+#   ntt        the transform (csrc/ntt_plan.h, csrc/ntt_tile.h)
+#   poly_prod  the column products (csrc/poly_prod.h)
+#   quotient   the gate program and the vanishing table (csrc/quotient.h)
+#   lookup     the comparison, merge path, tiled sort and permute rule (csrc/lookup.h)
+#   args       the entry points' shared argument checks (csrc/poly_args.hpp)
 HOSTTEST_DIR = os.path.join(HERE, "..", "tests", "hosttest")
+HOSTTESTS = ("curve", "poly", "ntt", "poly_prod", "quotient", "lookup", "args")
+HOSTTEST_EXCEPTIONS = {"curve": ("libhosttest_%s.so", ("curve_ops.h",))}  # the others: libhosttest_<name>_<curve>.so, one source
 
 
-def build_hosttest_curve(curve):
-    out = os.path.join(HOSTTEST_DIR, "libhosttest_%s.so" % curve)
-    srcs = [os.path.join(HOSTTEST_DIR, f) for f in ("hosttest_curve.cpp", "curve_ops.h")]
+def build_hosttest(name, curve):
+    stem, more = HOSTTEST_EXCEPTIONS.get(name, ("libhosttest_" + name + "_%s.so", ()))
+    out = os.path.join(HOSTTEST_DIR, stem % curve)
+    srcs = [os.path.join(HOSTTEST_DIR, f) for f in ("hosttest_%s.cpp" % name,) + more]
     if os.path.exists(out) and os.path.getmtime(out) >= max([_deps()] + [os.path.getmtime(f) for f in srcs]):
         return out
     flags = ["-DSNARKV_CURVE_PALLAS"] if curve == "pallas" else []
     r = subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC"] + flags + ["-o", out, srcs[0]], capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout + r.stderr)
-        raise RuntimeError("host build failed: hosttest_curve.cpp (%s)" % curve)
+        raise RuntimeError("host build failed: hosttest_%s.cpp (%s)" % (name, curve))
     return out
 
 
-# The blocked scan of the polynomial division (csrc/poly_scan.h) and the multi-open prover's query-set grouping
-# (csrc/ipa_multiopen_sets.h) for the host (tests/hosttest/hosttest_poly.cpp), one library per curve.
-def build_hosttest_poly(curve):
-    out = os.path.join(HOSTTEST_DIR, "libhosttest_poly_%s.so" % curve)
-    src = os.path.join(HOSTTEST_DIR, "hosttest_poly.cpp")
-    if os.path.exists(out) and os.path.getmtime(out) >= max(_deps(), os.path.getmtime(src)):
-        return out
-    flags = ["-DSNARKV_CURVE_PALLAS"] if curve == "pallas" else []
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC"] + flags + ["-o", out, src], capture_output=True, text=True)
-    if r.returncode != 0:
-        sys.stderr.write(r.stdout + r.stderr)
-        raise RuntimeError("host build failed: hosttest_poly.cpp (%s)" % curve)
-    return out
-
-
-# The transform (csrc/ntt_plan.h, csrc/ntt_tile.h) for the host (tests/hosttest/hosttest_ntt.cpp), one library per curve.
-def build_hosttest_ntt(curve):
-    out = os.path.join(HOSTTEST_DIR, "libhosttest_ntt_%s.so" % curve)
-    src = os.path.join(HOSTTEST_DIR, "hosttest_ntt.cpp")
-    if os.path.exists(out) and os.path.getmtime(out) >= max(_deps(), os.path.getmtime(src)):
-        return out
-    flags = ["-DSNARKV_CURVE_PALLAS"] if curve == "pallas" else []
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC"] + flags + ["-o", out, src], capture_output=True, text=True)
-    if r.returncode != 0:
-        sys.stderr.write(r.stdout + r.stderr)
-        raise RuntimeError("host build failed: hosttest_ntt.cpp (%s)" % curve)
-    return out
-
-
-# The column products (csrc/poly_prod.h) for the host (tests/hosttest/hosttest_poly_prod.cpp), one library per curve.
-def build_hosttest_poly_prod(curve):
-    out = os.path.join(HOSTTEST_DIR, "libhosttest_poly_prod_%s.so" % curve)
-    src = os.path.join(HOSTTEST_DIR, "hosttest_poly_prod.cpp")
-    if os.path.exists(out) and os.path.getmtime(out) >= max(_deps(), os.path.getmtime(src)):
-        return out
-    flags = ["-DSNARKV_CURVE_PALLAS"] if curve == "pallas" else []
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC"] + flags + ["-o", out, src], capture_output=True, text=True)
-    if r.returncode != 0:
-        sys.stderr.write(r.stdout + r.stderr)
-        raise RuntimeError("host build failed: hosttest_poly_prod.cpp (%s)" % curve)
-    return out
-
-
-# The quotient's gate program and vanishing table (csrc/quotient.h) for the host (tests/hosttest/hosttest_quotient.cpp), one
-# library per curve.
-def build_hosttest_quotient(curve):
-    out = os.path.join(HOSTTEST_DIR, "libhosttest_quotient_%s.so" % curve)
-    src = os.path.join(HOSTTEST_DIR, "hosttest_quotient.cpp")
-    if os.path.exists(out) and os.path.getmtime(out) >= max(_deps(), os.path.getmtime(src)):
-        return out
-    flags = ["-DSNARKV_CURVE_PALLAS"] if curve == "pallas" else []
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC"] + flags + ["-o", out, src], capture_output=True, text=True)
-    if r.returncode != 0:
-        sys.stderr.write(r.stdout + r.stderr)
-        raise RuntimeError("host build failed: hosttest_quotient.cpp (%s)" % curve)
-    return out
-
-
-# The lookup argument's comparison, merge path, tiled sort and permute rule (csrc/lookup.h) for the host
-# (tests/hosttest/hosttest_lookup.cpp), one library per curve.
-def build_hosttest_lookup(curve):
-    out = os.path.join(HOSTTEST_DIR, "libhosttest_lookup_%s.so" % curve)
-    src = os.path.join(HOSTTEST_DIR, "hosttest_lookup.cpp")
-    if os.path.exists(out) and os.path.getmtime(out) >= max(_deps(), os.path.getmtime(src)):
-        return out
-    flags = ["-DSNARKV_CURVE_PALLAS"] if curve == "pallas" else []
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC"] + flags + ["-o", out, src], capture_output=True, text=True)
-    if r.returncode != 0:
-        sys.stderr.write(r.stdout + r.stderr)
-        raise RuntimeError("host build failed: hosttest_lookup.cpp (%s)" % curve)
-    return out
+def __getattr__(attr):
+    """`build_hosttest_<name>(curve)` is `build_hosttest(name, curve)`: the spelling that callers outside this tree know"""
+    name = attr[len("build_hosttest_"):]
+    if attr.startswith("build_hosttest_") and name in HOSTTESTS:
+        return lambda curve: build_hosttest(name, curve)
+    raise AttributeError("module %r has no attribute %r" % (__name__, attr))
 
 
 def devtest_lib(flavour):

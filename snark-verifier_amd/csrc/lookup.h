@@ -147,6 +147,9 @@ SNARKV_HD LkCount lk_add(const LkCount& a, const LkCount& b) {
   c.rep = a.rep + b.rep, c.left = a.left + b.left;
   return c;
 }
+struct LkAdd {  // as the step of poly_prod.h's wg_scan
+  SNARKV_HD LkCount operator()(const LkCount& a, const LkCount& b) const { return lk_add(a, b); }
+};
 // status[0..3] from the totals: every distinct input value is one first row; each one the table holds uses up one table
 // element, so the leftovers exceed the repeated rows by the number of distinct input values the table lacks
 SNARKV_HD void lk_status(const LkCount& total, uint32_t u, uint32_t* status) {

@@ -26,6 +26,7 @@
 #include <string.h>
 #include "ctx.hpp"
 #include "ipa_prover.hpp"
+#include "poly_args.hpp"
 #include "lookup.h"
 #include "../../include/snarkv_lookup.h"
 #include "../../include/snarkv_poly_prod.h"
@@ -154,24 +155,9 @@ __global__ void __launch_bounds__(kLkThreads) k_lk_merge(const uint32_t* __restr
   }
 }
 
-// The inclusive scan of one count per lane over the workgroup: two buffers, one barrier per step, as poly_prod.hip's.
-__device__ __forceinline__ LkCount lk_wg_scan(LkCount (&sh)[2][kLkThreads], LkCount s, uint32_t lane) {
-  typedef ProdBlock<kLkThreads, 1> S;
-  __syncthreads();
-#pragma unroll 1
-  for (uint32_t step = 0; step < S::steps(); ++step) {
-    sh[step & 1u][lane] = s;
-    __syncthreads();
-    if (S::has_left(lane, step)) s = lk_add(s, sh[step & 1u][lane - S::distance(step)]);
-  }
-  return s;
-}
-// ... -> the exclusive scan of the lane, the block's total through `total`
+// the exclusive scan of one count per lane over the workgroup (poly_prod.h's wg_scan), the block's total through `total`
 __device__ __forceinline__ LkCount lk_wg_exclusive(LkCount (&sh)[2][kLkThreads], const LkCount& mine, uint32_t lane, LkCount* total) {
-  const LkCount s = lk_wg_scan(sh, mine, lane);
-  __syncthreads();
-  sh[0][lane] = s;
-  __syncthreads();
+  wg_publish(sh, wg_scan<LkAdd, false>(sh, mine, lane), lane);
   LkCount before;
   before.rep = 0, before.left = 0;
   if (lane) before = sh[0][lane - 1];
@@ -194,7 +180,7 @@ __global__ void __launch_bounds__(kLkThreads) k_lk_flag(const uint32_t* __restri
       flags[i] = (uint8_t)f;
       mine = lk_add(mine, lk_count_of(f));
     }
-  const LkCount sum = lk_wg_scan(sh, mine, lane);
+  const LkCount sum = wg_scan<LkAdd, false>(sh, mine, lane);
   if (lane == kLkThreads - 1) totals[b] = sum;
 }
 
@@ -212,7 +198,7 @@ __global__ void __launch_bounds__(kLkThreads) k_lk_up(const LkCount* __restrict_
   LkCount x[kLkLane], p[kLkLane], mine;
   lk_load_counts(in, b, lane, len, x);
   lk_lane_prefix<kLkLane>(x, p, mine);
-  const LkCount sum = lk_wg_scan(sh, mine, lane);
+  const LkCount sum = wg_scan<LkAdd, false>(sh, mine, lane);
   if (lane == kLkThreads - 1) totals[b] = sum;
 }
 
@@ -296,27 +282,6 @@ Layout layout_of(size_t n, size_t rows) {
   return l;
 }
 
-bool overlap(const void* a, size_t an, const void* b, size_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return an && bn && (x < y ? y - x < an : x - y < bn);
-}
-bool aligned16(const void* p) { return p && (uintptr_t)p % 16 == 0; }
-// the bytes of n elements for the overlap checks, which come before the length's: no wrap for an absurd n
-size_t bytes_of(size_t n) { return n > ((size_t)1 << 40) ? (size_t)1 << 45 : 32 * n; }
-int check_len(size_t n) { return n == 0 ? SNARKV_ERR_EMPTY : (n > kLkMaxLen ? SNARKV_ERR_LENGTH : SNARKV_OK); }
-bool below_r(const uint8_t* s32) {
-  constexpr uint32_t rw[8] = SNARKV_FR_R_LIMBS;
-  uint32_t w[8];
-  memcpy(w, s32, 32);
-  for (int i = 7; i >= 0; --i)
-    if (w[i] != rw[i]) return w[i] < rw[i];
-  return false;
-}
-int refuse_overlap(const char* call, const char* what) {
-  set_last_error("%s: overlap: %s", call, what);
-  return SNARKV_ERR_ARG;
-}
-
 // The enqueue steps; arguments are taken as checked.
 
 int sort_enqueue(snarkv_ctx* ctx, const void* d_in, size_t n, void* d_work, void* d_out) {
@@ -387,11 +352,11 @@ extern "C" {
 int SNARKV_API(poly_sort_dev)(snarkv_ctx* ctx, const void* d_in32, size_t n, void* d_work32, void* d_out32) {
   if (!ctx || !aligned16(d_in32) || !aligned16(d_work32) || !aligned16(d_out32)) return SNARKV_ERR_ARG;
   const size_t bytes = bytes_of(n);
-  if (d_out32 != d_in32 && overlap(d_out32, bytes, d_in32, bytes))
+  if (partial_overlap(d_out32, d_in32, bytes))
     return refuse_overlap("poly_sort", "out is the input itself or disjoint from it");
   if (overlap(d_work32, bytes, d_in32, bytes) || overlap(d_work32, bytes, d_out32, bytes))
     return refuse_overlap("poly_sort", "work is disjoint from the input and from out");
-  SNARKV_TRY(check_len(n));
+  SNARKV_TRY(check_len(n, kLkMaxLen));
   SNARKV_HIP(hipSetDevice(ctx->device));
   return sort_enqueue(ctx, d_in32, n, d_work32, d_out32);
 }
@@ -410,7 +375,7 @@ int SNARKV_API(lookup_permute_dev)(snarkv_ctx* ctx, const void* d_input32, const
         return refuse_overlap("lookup_permute", "the input, the table, work and the two outputs are pairwise disjoint");
   for (int i = 2; i < 5; ++i)
     if (overlap(d_status, 16, bufs[i], size[i])) return refuse_overlap("lookup_permute", "the status lies in memory the call writes");
-  SNARKV_TRY(check_len(u));
+  SNARKV_TRY(check_len(u, kLkMaxLen));
   SNARKV_HIP(hipSetDevice(ctx->device));
   return permute_enqueue(ctx, d_input32, d_table32, u, d_work32, d_perm_input32, d_perm_table32, d_status);
 }
@@ -422,21 +387,11 @@ int SNARKV_API(lookup_product_dev)(snarkv_ctx* ctx, const void* d_polys32, size_
   if ((d_start32 && !aligned16(d_start32)) || (d_total32 && !aligned16(d_total32))) return SNARKV_ERR_ARG;
   const size_t bytes = bytes_of(n), total_bytes = d_total32 ? 32 : 0;
   const uint32_t num_idx[2] = {idx_input, idx_table}, den_idx[2] = {idx_perm_input, idx_perm_table};
+  const uint32_t* idx[4] = {num_idx, num_idx + 1, den_idx, den_idx + 1};
+  const bool none_ok[4] = {false, false, false, false};
   const void* outs[3] = {d_work32, d_z32, d_total32};
   const size_t out_bytes[3] = {2 * bytes, bytes, total_bytes};
-  if (n_polys)  // without columns there is nothing to index: the call is empty
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t i = j < 2 ? num_idx[j] : den_idx[j - 2];
-      if (i >= n_polys) {
-        set_last_error("lookup_product: index %u, there are %zu columns", i, n_polys);
-        return SNARKV_ERR_ARG;
-      }
-      for (int o = 0; o < 3; ++o)
-        if (overlap(outs[o], out_bytes[o], (const uint8_t*)d_polys32 + bytes * i, bytes)) {
-          set_last_error("lookup_product: overlap: a buffer the call writes and column %u", i);
-          return SNARKV_ERR_ARG;
-        }
-    }
+  SNARKV_TRY(check_columns("lookup_product", d_polys32, n, n_polys, idx, 4, none_ok, 1, outs, out_bytes, 3));
   if (overlap(d_work32, 2 * bytes, d_z32, bytes) || overlap(d_total32, total_bytes, d_work32, 2 * bytes) ||
       overlap(d_total32, total_bytes, d_z32, bytes))
     return refuse_overlap("lookup_product", "work, z and the total are disjoint");
@@ -445,7 +400,7 @@ int SNARKV_API(lookup_product_dev)(snarkv_ctx* ctx, const void* d_polys32, size_
     return refuse_overlap("lookup_product", "the start value lies in memory the call writes");
   if (!below_r(beta32) || !below_r(gamma32)) return SNARKV_ERR_ENCODING;
   if (n_polys == 0) return SNARKV_ERR_EMPTY;
-  SNARKV_TRY(check_len(n));
+  SNARKV_TRY(check_len(n, kLkMaxLen));
   SNARKV_HIP(hipSetDevice(ctx->device));
   // (A + beta)(S + gamma): two affine terms without a beta part, the challenges as their constants
   const uint32_t none[2] = {SNARKV_POLY_NONE, SNARKV_POLY_NONE};

@@ -13,6 +13,7 @@
 // Values cross passes as canonical words.
 #include <string.h>
 #include "ctx.hpp"
+#include "poly_args.hpp"
 #include "ntt_plan.h"
 #include "ntt_tile.h"
 #include "../../include/snarkv_ntt.h"
@@ -111,17 +112,9 @@ void table(snarkv_ctx* ctx, const Fr29& base, uint32_t pre, uint32_t count, cons
   hipLaunchKernelGGL(k_ntt_table, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, base, pre, count, scale, (Fr29*)out);
 }
 
-bool aligned16(const void* p) { return p && (uintptr_t)p % 16 == 0; }
+}  // namespace
 
-// 32 bytes little-endian against r: -1 below, 0 equal, 1 above
-int cmp_r(const uint32_t w[8]) {
-  constexpr uint32_t rw[8] = SNARKV_FR_R_LIMBS;
-  for (int i = 7; i >= 0; --i)
-    if (w[i] != rw[i]) return w[i] < rw[i] ? -1 : 1;
-  return 0;
-}
-
-int enqueue(snarkv_ctx* ctx, const void* d_in, void* d_out, uint32_t k, size_t count, bool inverse, const uint32_t* shift) {
+int ntt_enqueue(snarkv_ctx* ctx, const void* d_in, void* d_out, uint32_t k, size_t count, bool inverse, const uint32_t* shift) {
   const Plan plan(k);
   const Layout l = layout_of(plan, count);
   void* d_scr;
@@ -162,13 +155,6 @@ int enqueue(snarkv_ctx* ctx, const void* d_in, void* d_out, uint32_t k, size_t c
   return SNARKV_OK;
 }
 
-}  // namespace
-
-// the same step for the units that chain a transform (ctx.hpp)
-int ntt_enqueue(snarkv_ctx* ctx, const void* d_in, void* d_out, uint32_t k, size_t count, bool inverse, const uint32_t* shift) {
-  return enqueue(ctx, d_in, d_out, k, count, inverse, shift);
-}
-
 }  // namespace snarkv
 
 using namespace snarkv;
@@ -185,21 +171,15 @@ int SNARKV_API(ntt_dev)(snarkv_ctx* ctx, const void* d_in32, void* d_out32, uint
   if (k > kNttMaxK || count > kNttMaxCount) return SNARKV_ERR_LENGTH;
   uint32_t shift[8];
   if (shift32) {
-    memcpy(shift, shift32, 32);
-    bool zero = true;
-    for (int i = 0; i < 8; ++i) zero = zero && shift[i] == 0;
-    if (zero) {
+    if (is_zero32(shift32)) {
       set_last_error("ntt: a shift of zero");
       return SNARKV_ERR_ARG;
     }
-    if (cmp_r(shift) >= 0) return SNARKV_ERR_ENCODING;
+    if (!below_r(shift32)) return SNARKV_ERR_ENCODING;
+    memcpy(shift, shift32, 32);
   }
-  const size_t bytes = (count << k) * 32;
-  const uintptr_t a = (uintptr_t)d_in32, b = (uintptr_t)d_out32;
-  if (a != b && a < b + bytes && b < a + bytes) {
-    set_last_error("ntt: in and out overlap in part; they are the same buffer or disjoint");
-    return SNARKV_ERR_ARG;
-  }
+  if (partial_overlap(d_in32, d_out32, (count << k) * 32))
+    return refuse_overlap("ntt", "in and out are the same buffer or disjoint");
   // a buffer the runtime knows to live on another device (what it does not know is the caller's to answer for)
   hipPointerAttribute_t attr;
   if (hipPointerGetAttributes(&attr, d_in32) == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device != ctx->device) {
@@ -208,7 +188,7 @@ int SNARKV_API(ntt_dev)(snarkv_ctx* ctx, const void* d_in32, void* d_out32, uint
   }
   (void)hipGetLastError();  // an address the runtime does not know leaves an error behind
   SNARKV_HIP(hipSetDevice(ctx->device));
-  return enqueue(ctx, d_in32, d_out32, k, count, direction == SNARKV_NTT_INVERSE, shift32 ? shift : nullptr);
+  return ntt_enqueue(ctx, d_in32, d_out32, k, count, direction == SNARKV_NTT_INVERSE, shift32 ? shift : nullptr);
 }
 
 }  // extern "C"

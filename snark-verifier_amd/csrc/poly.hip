@@ -11,6 +11,7 @@
 #include <string.h>
 #include <algorithm>
 #include "poly.hpp"
+#include "poly_args.hpp"
 #include "ipa_prover.hpp"
 #include "poly_scan.h"
 #include "../../include/snarkv_poly.h"
@@ -183,13 +184,6 @@ int scan_levels(snarkv_ctx* ctx, const void* d_coeffs, size_t n, const void* d_r
   return SNARKV_OK;
 }
 
-bool overlap(const void* a, size_t an, const void* b, size_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return an && bn && x < y + bn && y < x + an;
-}
-bool aligned16(const void* p) { return p && (uintptr_t)p % 16 == 0; }
-int check_len(size_t n) { return n == 0 ? SNARKV_ERR_EMPTY : (n > kPolyMaxLen ? SNARKV_ERR_LENGTH : SNARKV_OK); }
-
 }  // namespace
 
 int poly_enqueue_eval(snarkv_ctx* ctx, const void* d_coeffs, size_t n, const void* d_point, void* d_out) {
@@ -227,25 +221,19 @@ extern "C" {
 int SNARKV_API(poly_lincomb_dev)(snarkv_ctx* ctx, const void* d_polys32, size_t n, size_t n_polys, const uint32_t* idx,
                                  const uint8_t* scalars32, size_t count, void* d_out32) {
   if (!ctx || !idx || !scalars32 || !aligned16(d_polys32) || !aligned16(d_out32)) return SNARKV_ERR_ARG;
-  SNARKV_TRY(check_len(n));
+  SNARKV_TRY(check_len(n, kPolyMaxLen));
   if (count == 0 || n_polys == 0) return SNARKV_ERR_EMPTY;
-  for (size_t j = 0; j < count; ++j) {
-    if (idx[j] >= n_polys) {
-      set_last_error("poly_lincomb: index %u at %zu, there are %zu polynomials", idx[j], j, n_polys);
-      return SNARKV_ERR_ARG;
-    }
-    if (overlap(d_out32, 32 * n, (const uint8_t*)d_polys32 + 32 * n * idx[j], 32 * n)) {
-      set_last_error("poly_lincomb: out overlaps polynomial %u", idx[j]);
-      return SNARKV_ERR_ARG;
-    }
-  }
+  const bool none_ok = false;
+  const void* const out = d_out32;
+  const size_t out_bytes = 32 * n;
+  SNARKV_TRY(check_columns("poly_lincomb", d_polys32, n, n_polys, &idx, 1, &none_ok, count, &out, &out_bytes, 1));
   SNARKV_HIP(hipSetDevice(ctx->device));
   return poly_enqueue_lincomb(ctx, d_polys32, n, idx, scalars32, count, d_out32);
 }
 
 int SNARKV_API(poly_eval_dev)(snarkv_ctx* ctx, const void* d_coeffs32, size_t n, const void* d_point32, void* d_out32) {
   if (!ctx || !aligned16(d_coeffs32) || !aligned16(d_point32) || !aligned16(d_out32)) return SNARKV_ERR_ARG;
-  SNARKV_TRY(check_len(n));
+  SNARKV_TRY(check_len(n, kPolyMaxLen));
   SNARKV_HIP(hipSetDevice(ctx->device));
   return poly_enqueue_eval(ctx, d_coeffs32, n, d_point32, d_out32);
 }
@@ -253,7 +241,7 @@ int SNARKV_API(poly_eval_dev)(snarkv_ctx* ctx, const void* d_coeffs32, size_t n,
 int SNARKV_API(poly_div_linear_dev)(snarkv_ctx* ctx, const void* d_coeffs32, size_t n, const void* d_root32, void* d_quot32,
                                     void* d_rem32) {
   if (!ctx || !aligned16(d_coeffs32) || !aligned16(d_root32) || !aligned16(d_rem32)) return SNARKV_ERR_ARG;
-  SNARKV_TRY(check_len(n));
+  SNARKV_TRY(check_len(n, kPolyMaxLen));
   if (n > 1 && !aligned16(d_quot32)) return SNARKV_ERR_ARG;
   const size_t qn = 32 * (n - 1);
   if (overlap(d_quot32, qn, d_coeffs32, 32 * n) || overlap(d_rem32, 32, d_coeffs32, 32 * n) || overlap(d_rem32, 32, d_quot32, qn) ||

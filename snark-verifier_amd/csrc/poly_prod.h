@@ -84,6 +84,35 @@ SNARKV_HD void prod_lane_others(const Fr29* x, Fr29* m, Fr29& total) {
 
 // one step of the workgroup scan
 SNARKV_HD Fr29 prod_scan_step(const Fr29& s, const Fr29& other) { return fr29_mul(s, other); }
+struct ProdStep {
+  SNARKV_HD Fr29 operator()(const Fr29& s, const Fr29& other) const { return prod_scan_step(s, other); }
+};
+
+#if defined(__HIPCC__)
+// The inclusive scan of one value per lane over the workgroup, to the left (prefix) or to the right (suffix), for the kernels
+// of poly_prod.hip (Fr29, ProdStep) and of lookup.hip (its counts and their sum): two buffers, one barrier per step, as
+// k_poly_scan.  The barrier in front lets the caller have read `sh` just before.  STEP: a type whose call combines two values.
+template <typename STEP, bool RIGHT, uint32_t T, typename V>
+__device__ __forceinline__ V wg_scan(V (&sh)[2][T], V s, uint32_t lane) {
+  typedef ProdBlock<T, 1> S;
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t step = 0; step < S::steps(); ++step) {
+    sh[step & 1u][lane] = s;
+    __syncthreads();
+    if (RIGHT ? S::has_right(lane, step) : S::has_left(lane, step))
+      s = STEP()(s, sh[step & 1u][RIGHT ? lane + S::distance(step) : lane - S::distance(step)]);
+  }
+  return s;
+}
+// the scanned values into sh[0]: the neighbour's is the exclusive scan of a lane, the last (first) lane's the block's total
+template <uint32_t T, typename V>
+__device__ __forceinline__ void wg_publish(V (&sh)[2][T], const V& s, uint32_t lane) {
+  __syncthreads();
+  sh[0][lane] = s;
+  __syncthreads();
+}
+#endif
 
 // grand product, top down: `before` = the carry of the block times the totals of the lanes to the left
 template <uint32_t E>

@@ -15,6 +15,7 @@
 #include <vector>
 #include "ctx.hpp"
 #include "ipa_prover.hpp"
+#include "poly_args.hpp"
 #include "poly_prod.h"
 #include "../../include/snarkv_poly_prod.h"
 
@@ -38,29 +39,6 @@ enum : size_t {
 };
 static_assert(PP_IDX_B - PP_IDX_A >= 4 * kProdAffineTerms && PP_GAMMA - PP_BETA >= 32 * kProdAffineTerms &&
               PP_LEVELS - PP_GAMMA >= 32 * kProdAffineTerms, "the staged pass fits its places");
-
-// The inclusive scan of one value per lane over the workgroup, to the left (prefix) or to the right (suffix): two buffers,
-// one barrier per step, as k_poly_scan.  The barrier in front lets the caller have read `sh` just before.
-template <uint32_t T, bool RIGHT>
-__device__ __forceinline__ Fr29 wg_scan(Fr29 (&sh)[2][T], Fr29 s, uint32_t lane) {
-  typedef ProdBlock<T, 1> S;
-  __syncthreads();
-#pragma unroll 1
-  for (uint32_t step = 0; step < S::steps(); ++step) {
-    sh[step & 1u][lane] = s;
-    __syncthreads();
-    if (RIGHT ? S::has_right(lane, step) : S::has_left(lane, step))
-      s = prod_scan_step(s, sh[step & 1u][RIGHT ? lane + S::distance(step) : lane - S::distance(step)]);
-  }
-  return s;
-}
-// the scanned values into sh[0]: the neighbour's is the exclusive scan of a lane, the last (first) lane's the block's total
-template <uint32_t T>
-__device__ __forceinline__ void wg_publish(Fr29 (&sh)[2][T], const Fr29& s, uint32_t lane) {
-  __syncthreads();
-  sh[0][lane] = s;
-  __syncthreads();
-}
 
 // the E elements of lane `lane` of block b; one where the sequence has ended
 template <uint32_t T, uint32_t E>
@@ -95,7 +73,7 @@ __global__ void __launch_bounds__(T) k_prod_up(const uint32_t* __restrict__ in, 
   load_lane<T, E>(in, b, lane, len, x);
   if (NZ) zeros_to_one<E>(x, zero);
   prod_lane_prefix<E>(x, p, total);
-  const Fr29 s = wg_scan<T, false>(sh, total, lane);
+  const Fr29 s = wg_scan<ProdStep, false>(sh, total, lane);
   if (lane == T - 1) st_fr(totals + 8 * (size_t)b, s);
 }
 
@@ -110,8 +88,8 @@ __global__ void __launch_bounds__(T) k_prod_down(const uint32_t* in, uint32_t n,
   load_lane<T, E>(in, b, lane, len, x);
   const Fr29 carry = carries ? ld_fr(carries + 8 * (size_t)b * stride) : fr29_one();
   prod_lane_prefix<E>(x, p, total);
-  const Fr29 s = wg_scan<T, false>(sh, total, lane);
-  wg_publish<T>(sh, s, lane);
+  const Fr29 s = wg_scan<ProdStep, false>(sh, total, lane);
+  wg_publish(sh, s, lane);
   const Fr29 before = lane ? fr29_mul(carry, sh[0][lane - 1]) : carry;
   prod_lane_outputs<E>(before, p, x);
   store_lane<T, E>(out, b, lane, len, x);
@@ -135,14 +113,14 @@ __global__ void __launch_bounds__(T) k_inv_down(const uint32_t* in, uint32_t n, 
     for (uint32_t j = 0; j < E; ++j) zero[j] = false;
   }
   prod_lane_others<E>(x, m, total);
-  const Fr29 left = wg_scan<T, false>(sh, total, lane);
-  wg_publish<T>(sh, left, lane);
+  const Fr29 left = wg_scan<ProdStep, false>(sh, total, lane);
+  wg_publish(sh, left, lane);
   Fr29 around = lane ? sh[0][lane - 1] : fr29_one();
   if (TOP) {
     if (lane == T - 1) w_top = prod_inv(left);  // the block's total, never zero
   }
-  const Fr29 right = wg_scan<T, true>(sh, total, lane);
-  wg_publish<T>(sh, right, lane);  // its barriers also publish w_top
+  const Fr29 right = wg_scan<ProdStep, true>(sh, total, lane);
+  wg_publish(sh, right, lane);  // its barriers also publish w_top
   if (lane + 1 < T) around = fr29_mul(around, sh[0][lane + 1]);
   around = fr29_mul(around, TOP ? w_top : ld_fr(w + 8 * (size_t)b));
   prod_lane_inverses<E>(around, m, zero, x);
@@ -254,71 +232,19 @@ void sweep_up(snarkv_ctx* ctx, const Scratch& s, const void* d_in, bool nz) {
   }
 }
 
-bool overlap(const void* a, size_t an, const void* b, size_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return an && bn && (x < y ? y - x < an : x - y < bn);
-}
-// ... other than being the same buffer
-bool partial_overlap(const void* a, const void* b, size_t bytes) { return a != b && overlap(a, bytes, b, bytes); }
-bool aligned16(const void* p) { return p && (uintptr_t)p % 16 == 0; }
-// the bytes of n elements for the overlap checks, which come before the length's: no wrap for an absurd n
-size_t bytes_of(size_t n) { return n > ((size_t)1 << 40) ? (size_t)1 << 45 : 32 * n; }
-int check_len(size_t n) { return n == 0 ? SNARKV_ERR_EMPTY : (n > kProdMaxLen ? SNARKV_ERR_LENGTH : SNARKV_OK); }
-
-// 32 bytes little-endian of host memory: canonical?
-bool below_r(const uint8_t* s32) {
-  constexpr uint32_t rw[8] = SNARKV_FR_R_LIMBS;
-  uint32_t w[8];
-  memcpy(w, s32, 32);
-  for (int i = 7; i >= 0; --i)
-    if (w[i] != rw[i]) return w[i] < rw[i];
-  return false;
-}
-bool all_below_r(const uint8_t* s32, size_t count) {
-  for (size_t j = 0; j < count; ++j)
-    if (!below_r(s32 + 32 * j)) return false;
-  return true;
-}
-
-int refuse_overlap(const char* call, const char* what) {
-  set_last_error("%s: overlap: %s", call, what);
-  return SNARKV_ERR_ARG;
-}
-
-// the index and overlap checks of a call that reads the columns idx[0][j], idx[1][j], ... (SNARKV_POLY_NONE allowed where
-// `none_ok`) and writes `n_outs` buffers.  Without columns (n_polys = 0) there is nothing to index: the call is empty.
-int check_columns(const char* call, const void* d_polys, size_t n, size_t n_polys, const uint32_t* const* idx, size_t n_idx,
-                  const bool* none_ok, size_t count, const void* const* outs, const size_t* out_bytes, size_t n_outs) {
-  if (n_polys == 0) return SNARKV_OK;
-  const size_t col = bytes_of(n);
-  for (size_t a = 0; a < n_idx; ++a)
-    for (size_t j = 0; j < count; ++j) {
-      const uint32_t i = idx[a][j];
-      if (i == SNARKV_POLY_NONE && none_ok[a]) continue;
-      if (i >= n_polys) {
-        set_last_error("%s: index %u at %zu, there are %zu columns", call, i, j, n_polys);
-        return SNARKV_ERR_ARG;
-      }
-      for (size_t o = 0; o < n_outs; ++o)
-        if (overlap(outs[o], out_bytes[o], (const uint8_t*)d_polys + col * i, col)) {
-          set_last_error("%s: overlap: a buffer the call writes and column %u", call, i);
-          return SNARKV_ERR_ARG;
-        }
-    }
-  return SNARKV_OK;
-}
+}  // namespace
 
 // The enqueue steps; arguments are taken as checked.  Every step reserves the scratch of its own n: inside perm_product the
 // first reservation is the largest, so the slot does not move between the steps.
 
-int prod_enqueue_mul(snarkv_ctx* ctx, const void* d_a, const void* d_b, size_t n, void* d_out) {
+int prod_mul_enqueue(snarkv_ctx* ctx, const void* d_a, const void* d_b, size_t n, void* d_out) {
   hipLaunchKernelGGL(k_prod_mul, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)d_a,
                      (const uint32_t*)d_b, (uint32_t)n, (uint32_t*)d_out);
   SNARKV_HIP(hipGetLastError());
   return SNARKV_OK;
 }
 
-int prod_enqueue_affine(snarkv_ctx* ctx, const void* d_polys, size_t n, const uint32_t* idx_a, const uint32_t* idx_b,
+int prod_affine_enqueue(snarkv_ctx* ctx, const void* d_polys, size_t n, const uint32_t* idx_a, const uint32_t* idx_b,
                         const uint8_t* betas32, const uint8_t* gammas32, size_t count, void* d_out) {
   Scratch s;
   SNARKV_TRY(scratch_of(ctx, n, &s));
@@ -338,7 +264,7 @@ int prod_enqueue_affine(snarkv_ctx* ctx, const void* d_polys, size_t n, const ui
   return SNARKV_OK;
 }
 
-int prod_enqueue_batch_invert(snarkv_ctx* ctx, const void* d_in, size_t n, void* d_out) {
+int prod_batch_invert_enqueue(snarkv_ctx* ctx, const void* d_in, size_t n, void* d_out) {
   Scratch s;
   SNARKV_TRY(scratch_of(ctx, n, &s));
   sweep_up(ctx, s, d_in, true);
@@ -365,7 +291,7 @@ int prod_enqueue_batch_invert(snarkv_ctx* ctx, const void* d_in, size_t n, void*
   return SNARKV_OK;
 }
 
-int prod_enqueue_grand_product(snarkv_ctx* ctx, const void* d_f, size_t n, const void* d_start, void* d_out, void* d_total) {
+int prod_grand_product_enqueue(snarkv_ctx* ctx, const void* d_f, size_t n, const void* d_start, void* d_out, void* d_total) {
   Scratch s;
   SNARKV_TRY(scratch_of(ctx, n, &s));
   sweep_up(ctx, s, d_f, false);
@@ -386,24 +312,6 @@ int prod_enqueue_grand_product(snarkv_ctx* ctx, const void* d_f, size_t n, const
   return SNARKV_OK;
 }
 
-}  // namespace
-
-// the same step for the units that chain a batch inversion (ctx.hpp)
-int prod_batch_invert_enqueue(snarkv_ctx* ctx, const void* d_in, size_t n, void* d_out) {
-  return prod_enqueue_batch_invert(ctx, d_in, n, d_out);
-}
-// ... and for the unit that chains all four (lookup.hip)
-int prod_mul_enqueue(snarkv_ctx* ctx, const void* d_a, const void* d_b, size_t n, void* d_out) {
-  return prod_enqueue_mul(ctx, d_a, d_b, n, d_out);
-}
-int prod_affine_enqueue(snarkv_ctx* ctx, const void* d_polys, size_t n, const uint32_t* idx_a, const uint32_t* idx_b,
-                        const uint8_t* betas32, const uint8_t* gammas32, size_t count, void* d_out) {
-  return prod_enqueue_affine(ctx, d_polys, n, idx_a, idx_b, betas32, gammas32, count, d_out);
-}
-int prod_grand_product_enqueue(snarkv_ctx* ctx, const void* d_f, size_t n, const void* d_start, void* d_out, void* d_total) {
-  return prod_enqueue_grand_product(ctx, d_f, n, d_start, d_out, d_total);
-}
-
 }  // namespace snarkv
 
 using namespace snarkv;
@@ -414,9 +322,9 @@ int SNARKV_API(poly_mul_dev)(snarkv_ctx* ctx, const void* d_a32, const void* d_b
   if (!ctx || !aligned16(d_a32) || !aligned16(d_b32) || !aligned16(d_out32)) return SNARKV_ERR_ARG;
   if (partial_overlap(d_out32, d_a32, bytes_of(n)) || partial_overlap(d_out32, d_b32, bytes_of(n)))
     return refuse_overlap("poly_mul", "out is an operand itself or disjoint from it");
-  SNARKV_TRY(check_len(n));
+  SNARKV_TRY(check_len(n, kProdMaxLen));
   SNARKV_HIP(hipSetDevice(ctx->device));
-  return prod_enqueue_mul(ctx, d_a32, d_b32, n, d_out32);
+  return prod_mul_enqueue(ctx, d_a32, d_b32, n, d_out32);
 }
 
 int SNARKV_API(poly_prod_affine_dev)(snarkv_ctx* ctx, const void* d_polys32, size_t n, size_t n_polys, const uint32_t* idx_a,
@@ -430,18 +338,18 @@ int SNARKV_API(poly_prod_affine_dev)(snarkv_ctx* ctx, const void* d_polys32, siz
   SNARKV_TRY(check_columns("poly_prod_affine", d_polys32, n, n_polys, idx, 2, none_ok, count, outs, out_bytes, 1));
   if (!all_below_r(betas32, count) || !all_below_r(gammas32, count)) return SNARKV_ERR_ENCODING;
   if (count == 0 || n_polys == 0) return SNARKV_ERR_EMPTY;
-  SNARKV_TRY(check_len(n));
+  SNARKV_TRY(check_len(n, kProdMaxLen));
   SNARKV_HIP(hipSetDevice(ctx->device));
-  return prod_enqueue_affine(ctx, d_polys32, n, idx_a, idx_b, betas32, gammas32, count, d_out32);
+  return prod_affine_enqueue(ctx, d_polys32, n, idx_a, idx_b, betas32, gammas32, count, d_out32);
 }
 
 int SNARKV_API(poly_batch_invert_dev)(snarkv_ctx* ctx, const void* d_in32, size_t n, void* d_out32) {
   if (!ctx || !aligned16(d_in32) || !aligned16(d_out32)) return SNARKV_ERR_ARG;
   if (partial_overlap(d_out32, d_in32, bytes_of(n)))
     return refuse_overlap("poly_batch_invert", "out is the input itself or disjoint from it");
-  SNARKV_TRY(check_len(n));
+  SNARKV_TRY(check_len(n, kProdMaxLen));
   SNARKV_HIP(hipSetDevice(ctx->device));
-  return prod_enqueue_batch_invert(ctx, d_in32, n, d_out32);
+  return prod_batch_invert_enqueue(ctx, d_in32, n, d_out32);
 }
 
 int SNARKV_API(poly_grand_product_dev)(snarkv_ctx* ctx, const void* d_f32, size_t n, const void* d_start32, void* d_out32,
@@ -454,9 +362,9 @@ int SNARKV_API(poly_grand_product_dev)(snarkv_ctx* ctx, const void* d_f32, size_
     return refuse_overlap("poly_grand_product", "the total lies in the factors or in out");
   if (d_start32 && (overlap(d_start32, 32, d_out32, bytes) || (d_total32 && overlap(d_start32, 32, d_total32, 32))))
     return refuse_overlap("poly_grand_product", "the start value lies in memory the call writes");
-  SNARKV_TRY(check_len(n));
+  SNARKV_TRY(check_len(n, kProdMaxLen));
   SNARKV_HIP(hipSetDevice(ctx->device));
-  return prod_enqueue_grand_product(ctx, d_f32, n, d_start32, d_out32, d_total32);
+  return prod_grand_product_enqueue(ctx, d_f32, n, d_start32, d_out32, d_total32);
 }
 
 int SNARKV_API(poly_perm_product_dev)(snarkv_ctx* ctx, const void* d_polys32, size_t n, size_t n_polys, const uint32_t* idx_v,
@@ -481,7 +389,7 @@ int SNARKV_API(poly_perm_product_dev)(snarkv_ctx* ctx, const void* d_polys32, si
     return refuse_overlap("poly_perm_product", "the start value lies in memory the call writes");
   if (!below_r(beta32) || !below_r(gamma32)) return SNARKV_ERR_ENCODING;
   if (count == 0 || n_polys == 0) return SNARKV_ERR_EMPTY;
-  SNARKV_TRY(check_len(n));
+  SNARKV_TRY(check_len(n, kProdMaxLen));
   SNARKV_HIP(hipSetDevice(ctx->device));
   std::vector<uint8_t> betas(32 * count), gammas(32 * count);
   for (size_t j = 0; j < count; ++j) {
@@ -491,11 +399,11 @@ int SNARKV_API(poly_perm_product_dev)(snarkv_ctx* ctx, const void* d_polys32, si
   uint8_t* num = (uint8_t*)d_work32;
   uint8_t* den = num + 32 * n;
   // the four public calls, back to back
-  SNARKV_TRY(prod_enqueue_affine(ctx, d_polys32, n, idx_v, idx_id, betas.data(), gammas.data(), count, num));
-  SNARKV_TRY(prod_enqueue_affine(ctx, d_polys32, n, idx_v, idx_sigma, betas.data(), gammas.data(), count, den));
-  SNARKV_TRY(prod_enqueue_batch_invert(ctx, den, n, den));
-  SNARKV_TRY(prod_enqueue_mul(ctx, num, den, n, num));
-  return prod_enqueue_grand_product(ctx, num, n, d_start32, d_z32, d_total32);
+  SNARKV_TRY(prod_affine_enqueue(ctx, d_polys32, n, idx_v, idx_id, betas.data(), gammas.data(), count, num));
+  SNARKV_TRY(prod_affine_enqueue(ctx, d_polys32, n, idx_v, idx_sigma, betas.data(), gammas.data(), count, den));
+  SNARKV_TRY(prod_batch_invert_enqueue(ctx, den, n, den));
+  SNARKV_TRY(prod_mul_enqueue(ctx, num, den, n, num));
+  return prod_grand_product_enqueue(ctx, num, n, d_start32, d_z32, d_total32);
 }
 
 }  // extern "C"

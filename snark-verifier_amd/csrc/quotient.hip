@@ -19,6 +19,7 @@
 #include <vector>
 #include "ctx.hpp"
 #include "ipa_prover.hpp"
+#include "poly_args.hpp"
 #include "quotient.h"
 #include "../../include/snarkv_ntt.h"
 #include "../../include/snarkv_quotient.h"
@@ -86,11 +87,6 @@ namespace {
 
 uint32_t blocks_of(uint32_t log_n) { return (uint32_t)((((size_t)1 << log_n) + kQuotThreads - 1) / kQuotThreads); }
 
-bool overlap(const void* a, size_t an, const void* b, size_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return an && bn && (x < y ? y - x < an : x - y < bn);
-}
-bool aligned16(const void* p) { return p && (uintptr_t)p % 16 == 0; }
 // the bytes of `count` columns of 2^(k + e) elements for the overlap checks, which come before the lengths': no wrap for an
 // absurd shape
 size_t ext_bytes(uint32_t k, uint32_t e, size_t count) {
@@ -99,28 +95,10 @@ size_t ext_bytes(uint32_t k, uint32_t e, size_t count) {
   return count > ((size_t)1 << 62) / col ? (size_t)1 << 62 : col * count;
 }
 
-bool below_r(const uint8_t* s32) {
-  constexpr uint32_t rw[8] = SNARKV_FR_R_LIMBS;
-  uint32_t w[8];
-  memcpy(w, s32, 32);
-  for (int i = 7; i >= 0; --i)
-    if (w[i] != rw[i]) return w[i] < rw[i];
-  return false;
-}
-bool is_zero(const uint8_t* s32) {
-  for (int i = 0; i < 32; ++i)
-    if (s32[i]) return false;
-  return true;
-}
 bool bad_shift(const char* call, const uint8_t* s32) {
-  if (s32 && !is_zero(s32)) return false;
+  if (s32 && !is_zero32(s32)) return false;
   set_last_error("%s: a shift that is %s", call, s32 ? "zero" : "null");
   return true;
-}
-
-int refuse_overlap(const char* call, const char* what) {
-  set_last_error("%s: overlap: %s", call, what);
-  return SNARKV_ERR_ARG;
 }
 
 int check_shape(uint32_t k, uint32_t e) {
@@ -158,12 +136,6 @@ int check_program(const char* call, const snarkv_quot_instr* prog, size_t n_inst
     written |= 1u << in.dst;
   }
   return SNARKV_OK;
-}
-
-bool all_below_r(const uint8_t* s32, size_t count) {
-  for (size_t j = 0; j < count; ++j)
-    if (!below_r(s32 + 32 * j)) return false;
-  return true;
 }
 
 int check_program_lengths(size_t n_cols, size_t n_instr, size_t n_consts) {
@@ -273,7 +245,7 @@ int SNARKV_API(quotient_eval_dev)(snarkv_ctx* ctx, const void* d_cols32, uint32_
 int SNARKV_API(poly_div_vanishing_dev)(snarkv_ctx* ctx, const void* d_in32, uint32_t k, uint32_t e, const uint8_t* shift32,
                                        void* d_out32) {
   if (!ctx || !aligned16(d_in32) || !aligned16(d_out32) || bad_shift("poly_div_vanishing", shift32)) return SNARKV_ERR_ARG;
-  if (d_in32 != d_out32 && overlap(d_out32, ext_bytes(k, e, 1), d_in32, ext_bytes(k, e, 1)))
+  if (partial_overlap(d_out32, d_in32, ext_bytes(k, e, 1)))
     return refuse_overlap("poly_div_vanishing", "out is the input itself or disjoint from it");
   if (!below_r(shift32)) return SNARKV_ERR_ENCODING;
   SNARKV_TRY(check_shape(k, e));

@@ -7,7 +7,7 @@ This ctypes table is this module's own, as `ipa_prover`'s is: one table per head
 """
 import ctypes
 
-from ._bind import bind, is_pallas
+from ._bind import bind, is_pallas, signatures
 from ._lib import SnarkvError, _as_bytes
 
 _vp, _cp, _sz, _u32, _int = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
@@ -25,7 +25,7 @@ _CONTEXT_FREE = {
     "pallas_ipa_commit_batch": (_int, [_vp, _cp, _sz, _sz, _vp]),
 }
 # every function include/snarkv_ipa_batch.h declares
-SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPES.items()}
+SIGNATURES = signatures(_SHAPES)
 SIGNATURES.update(_CONTEXT_FREE)
 
 SHARED_WINDOWS = 32  # rows of the window table per base: table_bytes = SHARED_WINDOWS * 2^k * 64

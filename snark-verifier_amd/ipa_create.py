@@ -11,7 +11,7 @@ This ctypes table is this module's own, as `ipa_fold`'s is: one table per header
 """
 import ctypes
 
-from ._bind import bind, fe as _fe, is_pallas, prove, pt as _pt, vec as _vec
+from ._bind import bind, fe as _fe, is_pallas, prove, pt as _pt, signatures, vec as _vec
 
 _vp, _cp, _sz, _int = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int
 _szp = ctypes.POINTER(ctypes.c_size_t)
@@ -28,7 +28,7 @@ _CONTEXT_FREE = {
     "pallas_ipa_create_proof": (_int, [_vp, _cp, _cp, _cp, _sz, _cp, _cp, _cp, _cp] + _TAIL),
 }
 # every function include/snarkv_ipa_create.h declares
-SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPES.items()}
+SIGNATURES = signatures(_SHAPES)
 SIGNATURES.update(_CONTEXT_FREE)
 
 def api(pallas):

@@ -11,7 +11,7 @@ This ctypes table is this module's own, as `ipa_batch`'s is: one table per heade
 import ctypes
 import hashlib
 
-from ._bind import bind, is_pallas
+from ._bind import bind, is_pallas, signatures
 from ._lib import SnarkvError, _as_bytes
 
 _vp, _cp, _sz, _u32, _int = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
@@ -28,7 +28,7 @@ _CONTEXT_FREE = {
     "pallas_ipa_decide_folded": (_int, [_vp, _cp, _cp, _sz, _cp, _ip]),
 }
 # every function include/snarkv_ipa_fold.h declares
-SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPES.items()}
+SIGNATURES = signatures(_SHAPES)
 SIGNATURES.update(_CONTEXT_FREE)
 
 FOLD_BLOCK_BITS = 3  # a lane of the fold kernel owns 2^3 consecutive coefficients (csrc/ipa_fold.h kFoldT)

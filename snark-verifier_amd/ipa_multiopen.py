@@ -10,7 +10,7 @@ This ctypes table is this module's own, as `ipa_create`'s is: one table per head
 """
 import ctypes
 
-from ._bind import bind, fe as _fe, is_pallas, prove, pt as _pt, vec as _vec
+from ._bind import bind, fe as _fe, is_pallas, prove, pt as _pt, signatures, u32s, vec as _vec
 
 _vp, _cp, _sz, _int = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int
 _szp = ctypes.POINTER(ctypes.c_size_t)
@@ -29,7 +29,7 @@ _CONTEXT_FREE = {
     "pallas_ipa_multiopen_create_proof": (_int, [_vp, _cp, _cp, _cp, _sz, _sz] + _QUERIES + [_cp] + _TAIL),
 }
 # every function include/snarkv_ipa_multiopen.h declares
-SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPES.items()}
+SIGNATURES = signatures(_SHAPES)
 SIGNATURES.update(_CONTEXT_FREE)
 
 def api(pallas):
@@ -44,8 +44,7 @@ def proof_bytes(k, n_sets):
 
 def pack_queries(queries):
     """[(poly, shift, eval)] -> the three parallel arrays of the C call: (u32 array, shifts, evaluations, count)"""
-    polys = (ctypes.c_uint32 * max(len(queries), 1))(*[q[0] for q in queries])
-    return polys, b"".join(_fe(q[1]) for q in queries), b"".join(_fe(q[2]) for q in queries), len(queries)
+    return u32s([q[0] for q in queries]), b"".join(_fe(q[1]) for q in queries), b"".join(_fe(q[2]) for q in queries), len(queries)
 
 
 def _prove(a, fn, handles, dk, h, s, polys, n_polys, blinds, x, queries, f_blind, p_bar, omega_bar, absorbed):

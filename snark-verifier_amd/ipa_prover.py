@@ -13,7 +13,7 @@ This ctypes table is this module's own: the header is not snarkv_amd.h, whose ta
 """
 import ctypes
 
-from ._bind import bind, fe as _fe, is_pallas
+from ._bind import bind, fe as _fe, is_pallas, signatures
 from ._lib import _as_bytes
 
 _vp, _cp, _sz, _u32, _int = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
@@ -30,7 +30,7 @@ _SHAPES = {
     "ipa_as_combine_dev": (_int, [_vp, _cp, _sz, _u32, _cp, _cp, _vp]),
 }
 # every function include/snarkv_ipa_prover.h declares, for both libraries
-SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPES.items()}
+SIGNATURES = signatures(_SHAPES)
 
 # scalar field orders: BN254 r and pallas q (include/snarkv_pallas.h)
 R_BN254 = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001

@@ -10,7 +10,7 @@ This ctypes table is this module's own, as `poly_prod`'s and `quotient`'s are: o
 """
 import ctypes
 
-from ._bind import bind, fe as _fe, is_pallas
+from ._bind import addr as _addr, bind, fe as _fe, is_pallas, signatures
 
 _vp, _cp, _sz, _int, _u32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32
 
@@ -26,18 +26,12 @@ _SHAPES = {
     "lookup_product_dev": (_int, [_vp, _vp, _sz, _sz, _u32, _u32, _u32, _u32, _cp, _cp, _vp, _vp, _vp, _vp]),
 }
 # every function include/snarkv_lookup.h declares
-SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPES.items()}
+SIGNATURES = signatures(_SHAPES)
 
 
 def api(pallas):
     """the functions of one library (`pallas`: the pasta build)"""
     return bind(_SHAPES, None, pallas)
-
-
-def _addr(p):
-    if p is None:
-        return None
-    return _vp(int(p.data_ptr() if hasattr(p, "data_ptr") else p))
 
 
 def sort_dev(ctx, d_in, n, d_work, d_out):

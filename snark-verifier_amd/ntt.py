@@ -11,7 +11,7 @@ This ctypes table is this module's own, as `poly`'s is: one table per header.
 """
 import ctypes
 
-from ._bind import bind, fe as _fe, is_pallas
+from ._bind import addr as _addr, bind, fe as _fe, is_pallas, signatures
 
 _vp, _cp, _sz, _int, _u32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32
 
@@ -27,16 +27,12 @@ _SHAPES = {
     "ntt_max_k": (_u32, []),
 }
 # every function include/snarkv_ntt.h declares
-SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPES.items()}
+SIGNATURES = signatures(_SHAPES)
 
 
 def api(pallas):
     """the functions of one library (`pallas`: the pasta build)"""
     return bind(_SHAPES, None, pallas)
-
-
-def _addr(p):
-    return _vp(int(p.data_ptr() if hasattr(p, "data_ptr") else p))
 
 
 def passes(k):

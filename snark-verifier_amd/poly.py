@@ -9,7 +9,7 @@ This ctypes table is this module's own, as `ipa_create`'s is: one table per head
 """
 import ctypes
 
-from ._lib import SnarkvError
+from ._bind import addr as _addr, bind, is_pallas, scalars as _scalars, signatures, u32s as _u32s
 
 _vp, _cp, _sz, _int = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -25,69 +25,27 @@ _SHAPES = {
     "poly_div_linear_dev": (_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
 }
 # every function include/snarkv_poly.h declares
-SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPES.items()}
-
-_BOUND = {}
-
-
-class _Api:
-    def __init__(self, lib, prefix):
-        self.lib, self.prefix = lib, prefix
-        for n, (res, args) in _SHAPES.items():
-            fn = getattr(lib, prefix + n)  # AttributeError if the header and the library drift
-            fn.restype, fn.argtypes = res, args
-
-    def __getattr__(self, name):
-        return getattr(self.lib, self.prefix + name)
-
-    def check(self, rc):
-        if rc < 0:
-            err = self.lib.snarkv_pallas_last_error if self.prefix == "snarkv_pallas_" else self.lib.snarkv_last_error
-            raise SnarkvError(rc, (err() or b"").decode(errors="replace"))
-        return rc
+SIGNATURES = signatures(_SHAPES)
 
 
 def api(pallas):
     """the functions of one library (`pallas`: the pasta build)"""
-    if pallas not in _BOUND:
-        if pallas:
-            from .pallas import load_library
-
-            _BOUND[pallas] = _Api(load_library(), "snarkv_pallas_")
-        else:
-            from ._lib import load_library
-
-            _BOUND[pallas] = _Api(load_library(), "snarkv_")
-    return _BOUND[pallas]
-
-
-def _is_pallas(ctx):
-    from .pallas import PallasContext
-
-    return isinstance(ctx, PallasContext)
-
-
-def _addr(p):
-    if p is None:
-        return None
-    return _vp(int(p.data_ptr() if hasattr(p, "data_ptr") else p))
+    return bind(_SHAPES, None, pallas)
 
 
 def lincomb_dev(ctx, d_polys, n, n_polys, idx, scalars, d_out):
     """out = sum_j scalars[j] * polys[idx[j]] over a poly-major array of `n_polys` polynomials of n coefficients"""
-    a = api(_is_pallas(ctx))
-    sc = b"".join(int(s).to_bytes(32, "little") if isinstance(s, int) else bytes(s) for s in scalars)
-    arr = (ctypes.c_uint32 * max(len(idx), 1))(*idx)
-    a.check(a.poly_lincomb_dev(ctx._h, _addr(d_polys), n, n_polys, arr, sc or b"\x00", len(idx), _addr(d_out)))
+    a = api(is_pallas(ctx))
+    a.check(a.poly_lincomb_dev(ctx._h, _addr(d_polys), n, n_polys, _u32s(idx), _scalars(scalars), len(idx), _addr(d_out)))
 
 
 def eval_dev(ctx, d_coeffs, n, d_point, d_out):
     """out = p(point); point and out are 32 bytes of device memory each"""
-    a = api(_is_pallas(ctx))
+    a = api(is_pallas(ctx))
     a.check(a.poly_eval_dev(ctx._h, _addr(d_coeffs), n, _addr(d_point), _addr(d_out)))
 
 
 def div_linear_dev(ctx, d_coeffs, n, d_root, d_quot, d_rem):
     """p = (X - root) quot + rem: n - 1 coefficients to d_quot (which may not overlap d_coeffs), 32 bytes to d_rem"""
-    a = api(_is_pallas(ctx))
+    a = api(is_pallas(ctx))
     a.check(a.poly_div_linear_dev(ctx._h, _addr(d_coeffs), n, _addr(d_root), _addr(d_quot), _addr(d_rem)))

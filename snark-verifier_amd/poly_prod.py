@@ -10,7 +10,7 @@ This ctypes table is this module's own, as `poly`'s and `ntt`'s are: one table p
 """
 import ctypes
 
-from ._bind import bind, fe as _fe, is_pallas
+from ._bind import addr as _addr, bind, fe as _fe, is_pallas, scalars as _scalars, signatures, u32s as _idx
 
 _vp, _cp, _sz, _int = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -29,26 +29,12 @@ _SHAPES = {
     "poly_perm_product_dev": (_int, [_vp, _vp, _sz, _sz, _u32p, _u32p, _u32p, _sz, _cp, _cp, _vp, _vp, _vp, _vp]),
 }
 # every function include/snarkv_poly_prod.h declares
-SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPES.items()}
+SIGNATURES = signatures(_SHAPES)
 
 
 def api(pallas):
     """the functions of one library (`pallas`: the pasta build)"""
     return bind(_SHAPES, None, pallas)
-
-
-def _addr(p):
-    if p is None:
-        return None
-    return _vp(int(p.data_ptr() if hasattr(p, "data_ptr") else p))
-
-
-def _idx(idx):
-    return (ctypes.c_uint32 * max(len(idx), 1))(*idx)
-
-
-def _scalars(vals):
-    return b"".join(_fe(v) for v in vals) or b"\x00"
 
 
 def mul_dev(ctx, d_a, d_b, n, d_out):

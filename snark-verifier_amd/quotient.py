@@ -12,7 +12,7 @@ This ctypes table is this module's own, as `poly_prod`'s and `ntt`'s are: one ta
 import ctypes
 import struct
 
-from ._bind import bind, fe as _fe, is_pallas
+from ._bind import addr as _addr, bind, fe as _fe, is_pallas, signatures
 
 _vp, _cp, _sz, _int, _u32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32
 
@@ -29,7 +29,7 @@ _SHAPES = {
     "quotient_dev": (_int, [_vp, _vp, _u32, _u32, _sz, _cp, _sz, _cp, _sz, _cp, _cp, _vp, _vp]),
 }
 # every function include/snarkv_quotient.h declares
-SIGNATURES = {p + n: s for p in ("snarkv_", "snarkv_pallas_") for n, s in _SHAPES.items()}
+SIGNATURES = signatures(_SHAPES)
 
 
 def api(pallas):
@@ -95,10 +95,6 @@ class Program:
     def packed(self):
         """the instructions as the bytes of a snarkv_quot_instr array"""
         return b"".join(pack_instr(*i) for i in self.instrs)
-
-
-def _addr(p):
-    return _vp(int(p.data_ptr() if hasattr(p, "data_ptr") else p))
 
 
 def _program(prog):

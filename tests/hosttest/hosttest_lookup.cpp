@@ -86,7 +86,7 @@ void sort(const uint32_t* in, uint32_t n, uint32_t tile, uint32_t lane_e, uint32
   }
 }
 
-// lk_wg_scan: the inclusive scan of one count per lane
+// wg_scan with LkAdd: the inclusive scan of one count per lane
 template <uint32_t T>
 void wg_scan(std::vector<LkCount>& s) {
   typedef ProdBlock<T, 1> S;

@@ -119,7 +119,7 @@ class Curve:
         spec = importlib.util.spec_from_file_location("_snarkv_build", os.path.join(ROOT, "snark-verifier_amd", "build.py"))
         b = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(b)
-        lib = ctypes.CDLL(b.build_hosttest_curve(self.name))
+        lib = ctypes.CDLL(b.build_hosttest("curve", self.name))
         lib.hc_curve.restype = ctypes.c_char_p
         assert lib.hc_curve() == self.name.encode()
         return lib

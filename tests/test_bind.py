@@ -1,5 +1,5 @@
-"""CPU: the binder the IPA ctypes modules share (snark_verifier_amd._bind), against a stand-in library object: no device,
-no library build."""
+"""CPU: the binder and the argument encoders the ctypes modules share (snark_verifier_amd._bind), against a stand-in library
+object: no device, no library build."""
 import ctypes
 
 import pytest
@@ -59,3 +59,26 @@ def test_check_raises_with_the_library_text():
     assert api.check(0) == 0 and api.check(3) == 3 and api.last_error() == "thing: no"
     with pytest.raises(SnarkvError, match="thing: no"):
         api.check(-2)
+
+
+def test_the_encoders_of_addresses_indices_and_scalars():
+    from snark_verifier_amd import _bind
+
+    class _Tensor:
+        def data_ptr(self):
+            return 0x7000
+
+    assert _bind.addr(None) is None
+    a, t = _bind.addr(0x1230), _bind.addr(_Tensor())
+    assert isinstance(a, ctypes.c_void_p) and a.value == 0x1230 and isinstance(t, ctypes.c_void_p) and t.value == 0x7000
+    assert len(_bind.u32s([])) == 1 and list(_bind.u32s([7, 0xFFFFFFFF])) == [7, 0xFFFFFFFF]
+    assert len(_bind.scalars([])) > 0
+    assert _bind.scalars([1, b"\x02" + b"\x00" * 31]) == b"\x01" + b"\x00" * 31 + b"\x02" + b"\x00" * 31
+
+
+def test_signatures_lists_a_table_under_both_prefixes():
+    from snark_verifier_amd import _bind
+
+    sig = _bind.signatures(SHAPES)
+    assert sorted(sig) == ["snarkv_pallas_thing_make", "snarkv_pallas_thing_size", "snarkv_thing_make", "snarkv_thing_size"]
+    assert sig["snarkv_thing_make"] is SHAPES["thing_make"] and sig["snarkv_pallas_thing_size"] is SHAPES["thing_size"]

@@ -9,13 +9,10 @@ import subprocess
 
 import pytest
 
+import abi_util as AU
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "include")
-
-
-def _declared(header, pattern):
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(INC, header)).read(), flags=re.S)
-    return sorted(set(re.findall(pattern, txt)))
 
 
 @pytest.fixture(scope="module")
@@ -36,15 +33,13 @@ def host_lib():
 
 @pytest.mark.parametrize("header", ["snarkv_pallas_decompress.h", "snarkv_host_pallas.h"])
 def test_new_headers_are_strict_c99(header):
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c",
-                        os.path.join(INC, header)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    AU.assert_strict_c99(header)
 
 
 def test_pallas_library_exports_the_decompression_entry_points():
     from snark_verifier_amd import pallas as PL
 
-    declared = _declared("snarkv_pallas_decompress.h", r"\b((?:snarkv_)?pallas_[a-z0-9_]+)\s*\(")
+    declared = AU.declared(os.path.join(INC, "snarkv_pallas_decompress.h"), r"\b((?:snarkv_)?pallas_[a-z0-9_]+)\s*\(")
     assert declared == ["pallas_g1_decompress", "snarkv_pallas_ctx_set_flags", "snarkv_pallas_g1_decompress"]
     lib = PL.load_library()
     for name in declared:
@@ -56,7 +51,7 @@ def test_pallas_library_exports_the_decompression_entry_points():
 def test_host_pallas_library_exports_exactly_the_declared_names(host_lib):
     from snark_verifier_amd import host_api_pallas as HP
 
-    declared = _declared("snarkv_host_pallas.h", r"\b(snarkv_host_pallas_[a-z0-9_]+)\s*\(")
+    declared = AU.declared(os.path.join(INC, "snarkv_host_pallas.h"), r"\b(snarkv_host_pallas_[a-z0-9_]+)\s*\(")
     assert len(declared) == 11
     for name in declared:
         assert hasattr(host_lib, name), name

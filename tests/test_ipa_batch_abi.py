@@ -4,35 +4,28 @@ snark_verifier_amd.ipa_batch lists exactly those names, the Python wrappers exis
 the documented codes before any device work."""
 import ctypes
 import os
-import re
-import subprocess
+
+import abi_util as AU
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "include")
 HDR = os.path.join(INC, "snarkv_ipa_batch.h")
 
 
-def _declared():
-    txt = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b((?:snarkv|bn254|pallas)_[a-z0-9_]+)\s*\(", txt)))
-
-
 def test_headers_are_strict_c99():
     for h in ("snarkv_ipa_batch.h", "snarkv_ipa_prover.h", "snarkv_amd.h", "snarkv_pallas.h"):
-        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c",
-                            os.path.join(INC, h)], capture_output=True, text=True)
-        assert r.returncode == 0, h + ": " + r.stderr
+        AU.assert_strict_c99(h)
 
 
 def test_both_libraries_export_every_declared_name():
     import snark_verifier_amd as sv
-    from snark_verifier_amd import _lib, ipa_batch, ipa_prover
+    from snark_verifier_amd import ipa_batch
     from snark_verifier_amd import pallas as PL
 
-    declared = _declared()
+    declared = AU.declared(HDR)
     assert len(declared) == 10
     assert sorted(ipa_batch.SIGNATURES) == declared
-    assert not set(declared) & (set(_lib._SIGNATURES) | set(ipa_prover.SIGNATURES))  # the other tables stay as they are
+    assert not set(declared) & AU.other_tables(ipa_batch)  # the other tables stay as they are
     bn, pa = sv.load_library(), PL.load_library()
     for name in declared:
         assert hasattr(pa if "pallas" in name else bn, name), name
@@ -50,17 +43,6 @@ def test_python_wrappers_exist():
     assert ipa_batch.SHARED_WINDOWS == 32
 
 
-class _FakeKey(ctypes.Structure):
-    """the head of the deciding key (csrc/ctx.hpp: device, k, points, first, count), enough for the argument checks
-    that come before any device work; the calls below never get past them"""
-    _fields_ = [("device", ctypes.c_int), ("k", ctypes.c_uint32), ("d_points", ctypes.c_void_p), ("first", ctypes.c_size_t),
-                ("count", ctypes.c_size_t), ("rest", ctypes.c_uint8 * 256)]
-
-
-class _FakeCtx(ctypes.Structure):
-    _fields_ = [("device", ctypes.c_int), ("rest", ctypes.c_uint8 * 8192)]
-
-
 def test_bad_arguments_are_refused_without_a_device():
     import snark_verifier_amd as sv
     from snark_verifier_amd import ipa_batch
@@ -72,13 +54,13 @@ def test_bad_arguments_are_refused_without_a_device():
         assert a.ipa_commit_batch_dev(None, None, None, 1, 1, 0, None) == sv.SNARKV_ERR_ARG
         assert a.ipa_dk_prepare(None, None) == sv.SNARKV_ERR_ARG
         assert a.ipa_dk_table_bytes(None) == 0
-        ctx = _FakeCtx(device=0)
-        whole, shard = _FakeKey(device=0, k=3, first=0, count=8), _FakeKey(device=0, k=3, first=4, count=4)
+        ctx = AU.FakeCtx(device=0)
+        whole, shard = AU.FakeKey(device=0, k=3, first=0, count=8), AU.FakeKey(device=0, k=3, first=4, count=4)
         pc, pw, ps = ctypes.addressof(ctx), ctypes.addressof(whole), ctypes.addressof(shard)
         assert a.ipa_commit_batch(pc, pw, b32, 0, 1, out) == sv.SNARKV_ERR_EMPTY    # n = 0
         assert a.ipa_commit_batch(pc, pw, b32, 1, 0, out) == sv.SNARKV_ERR_EMPTY    # m = 0
         assert a.ipa_commit_batch(pc, pw, b32, 9, 1, out) == sv.SNARKV_ERR_LENGTH   # n > count
         assert a.ipa_commit_batch(pc, ps, b32, 1, 1, out) == sv.SNARKV_ERR_LENGTH   # a shard
         assert a.ipa_commit_batch_dev(pc, ps, pc, 1, 1, 0, pc) == sv.SNARKV_ERR_LENGTH
-        other = _FakeCtx(device=1)
+        other = AU.FakeCtx(device=1)
         assert a.ipa_commit_batch(ctypes.addressof(other), pw, b32, 1, 1, out) == sv.SNARKV_ERR_ARG  # key of another device

@@ -4,7 +4,6 @@ exactly those names and shares none with the other tables, the Python wrappers e
 documented codes before any device work, and the host library exports exactly its declared names."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -14,30 +13,24 @@ HDR = os.path.join(INC, "snarkv_ipa_create.h")
 HOST_HDR = os.path.join(INC, "snarkv_host_pallas_prove.h")
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
-
-def _declared(path, pattern=r"\b((?:snarkv|bn254|pallas)_[a-z0-9_]+)\s*\("):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(pattern, txt)))
+import abi_util as AU  # noqa: E402
 
 
 def test_headers_are_strict_c99():
     for h in (HDR, HOST_HDR):
-        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", h],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+        AU.assert_strict_c99(h)
 
 
 def test_both_libraries_export_every_declared_name():
     import snark_verifier_amd as sv
-    from snark_verifier_amd import _lib, ipa_batch, ipa_create, ipa_fold, ipa_prover
+    from snark_verifier_amd import ipa_create
     from snark_verifier_amd import pallas as PL
 
-    declared = _declared(HDR)
+    declared = AU.declared(HDR)
     assert declared == ["bn254_ipa_create_proof", "pallas_ipa_create_proof", "snarkv_ipa_create_proof",
                         "snarkv_ipa_create_proof_dev", "snarkv_pallas_ipa_create_proof", "snarkv_pallas_ipa_create_proof_dev"]
     assert sorted(ipa_create.SIGNATURES) == declared
-    others = set(_lib._SIGNATURES) | set(ipa_prover.SIGNATURES) | set(ipa_batch.SIGNATURES) | set(ipa_fold.SIGNATURES)
-    assert not set(declared) & others
+    assert not set(declared) & AU.other_tables(ipa_create)
     bn, pa = sv.load_library(), PL.load_library()
     for name in declared:
         assert hasattr(pa if "pallas" in name else bn, name), name
@@ -57,17 +50,6 @@ def test_python_wrappers_exist():
     assert callable(HP.ipa_create_proof) and callable(HP.load_prove_library)
 
 
-class _FakeKey(ctypes.Structure):
-    """the head of the deciding key (csrc/ctx.hpp: device, k, points, first, count), enough for the argument checks
-    that come before any device work; the calls below never get past them"""
-    _fields_ = [("device", ctypes.c_int), ("k", ctypes.c_uint32), ("d_points", ctypes.c_void_p), ("first", ctypes.c_size_t),
-                ("count", ctypes.c_size_t), ("rest", ctypes.c_uint8 * 256)]
-
-
-class _FakeCtx(ctypes.Structure):
-    _fields_ = [("device", ctypes.c_int), ("rest", ctypes.c_uint8 * 8192)]
-
-
 def test_bad_arguments_are_refused_without_a_device():
     import snark_verifier_amd as sv
     from snark_verifier_amd import ipa_create
@@ -77,8 +59,8 @@ def test_bad_arguments_are_refused_without_a_device():
         b32, b64, coeffs = b"\x00" * 32, b"\x01" * 64, b"\x00" * (32 * 8)
         proof, xi, u = ctypes.create_string_buffer(b"\xaa" * 512, 512), ctypes.create_string_buffer(96), ctypes.create_string_buffer(64)
         plen = ctypes.c_size_t(7)
-        ctx = _FakeCtx(device=0)
-        whole, shard = _FakeKey(device=0, k=3, first=0, count=8), _FakeKey(device=0, k=3, first=4, count=4)
+        ctx = AU.FakeCtx(device=0)
+        whole, shard = AU.FakeKey(device=0, k=3, first=0, count=8), AU.FakeKey(device=0, k=3, first=4, count=4)
         pc, pw, ps = ctypes.addressof(ctx), ctypes.addressof(whole), ctypes.addressof(shard)
 
         def call(fn=a.ipa_create_proof, c=pc, dk=pw, h=b64, s=None, p=coeffs, n=8, z=b32, om=None, pbar=None, omb=None, ab=None,
@@ -103,7 +85,7 @@ def test_bad_arguments_are_refused_without_a_device():
         # the key and n: a shard, n that is not the key's 2^k, a context on another device
         assert call(dk=ps) == sv.SNARKV_ERR_LENGTH and plen.value == 0
         assert call(n=4) == sv.SNARKV_ERR_LENGTH
-        other = _FakeCtx(device=1)
+        other = AU.FakeCtx(device=1)
         assert call(c=ctypes.addressof(other)) == sv.SNARKV_ERR_ARG
 
 
@@ -121,7 +103,7 @@ def test_the_host_library_of_the_one_call_proof():
     lists them apart from the other two tables, and argument errors come back as codes without a device"""
     from snark_verifier_amd import host_api_pallas as HP
 
-    declared = _declared(HOST_HDR, r"\b(snarkv_host_pallas_[a-z0-9_]+)\s*\(")
+    declared = AU.declared(HOST_HDR, r"\b(snarkv_host_pallas_[a-z0-9_]+)\s*\(")
     assert declared == ["snarkv_host_pallas_ipa_create_proof", "snarkv_host_pallas_prove_last_error"]
     assert sorted(HP._PROVE_SIGNATURES) == declared
     assert not set(declared) & (set(HP._SIGNATURES) | set(HP._FOLD_SIGNATURES))

@@ -6,7 +6,6 @@ import ctypes
 import hashlib
 import os
 import random
-import re
 import subprocess
 import sys
 
@@ -17,28 +16,23 @@ INC = os.path.join(ROOT, "include")
 HDR = os.path.join(INC, "snarkv_ipa_fold.h")
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
-
-def _declared():
-    txt = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b((?:snarkv|bn254|pallas)_[a-z0-9_]+)\s*\(", txt)))
+import abi_util as AU  # noqa: E402
 
 
 def test_header_is_strict_c99():
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", HDR],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    AU.assert_strict_c99(HDR)
 
 
 def test_both_libraries_export_every_declared_name():
     import snark_verifier_amd as sv
-    from snark_verifier_amd import _lib, ipa_batch, ipa_fold, ipa_prover
+    from snark_verifier_amd import ipa_fold
     from snark_verifier_amd import pallas as PL
 
-    declared = _declared()
+    declared = AU.declared(HDR)
     assert declared == ["bn254_ipa_decide_folded", "pallas_ipa_decide_folded", "snarkv_ipa_decide_folded",
                         "snarkv_ipa_fold_coeffs_dev", "snarkv_pallas_ipa_decide_folded", "snarkv_pallas_ipa_fold_coeffs_dev"]
     assert sorted(ipa_fold.SIGNATURES) == declared
-    assert not set(declared) & (set(_lib._SIGNATURES) | set(ipa_prover.SIGNATURES) | set(ipa_batch.SIGNATURES))
+    assert not set(declared) & AU.other_tables(ipa_fold)
     bn, pa = sv.load_library(), PL.load_library()
     for name in declared:
         assert hasattr(pa if "pallas" in name else bn, name), name
@@ -55,17 +49,6 @@ def test_python_wrappers_exist():
     assert callable(sv.ipa_fold.fold_challenge) and callable(sv.ipa_fold.decide_folded_default)
 
 
-class _FakeKey(ctypes.Structure):
-    """the head of the deciding key (csrc/ctx.hpp: device, k, points, first, count), enough for the argument checks
-    that come before any device work; the calls below never get past them"""
-    _fields_ = [("device", ctypes.c_int), ("k", ctypes.c_uint32), ("d_points", ctypes.c_void_p), ("first", ctypes.c_size_t),
-                ("count", ctypes.c_size_t), ("rest", ctypes.c_uint8 * 256)]
-
-
-class _FakeCtx(ctypes.Structure):
-    _fields_ = [("device", ctypes.c_int), ("rest", ctypes.c_uint8 * 8192)]
-
-
 def test_bad_arguments_are_refused_without_a_device():
     import snark_verifier_amd as sv
     from snark_verifier_amd import ipa_fold
@@ -75,14 +58,14 @@ def test_bad_arguments_are_refused_without_a_device():
         ok, b32, b64 = ctypes.c_int(7), b"\x00" * 32, b"\x00" * 64
         assert a.ipa_decide_folded(None, None, b32, b64, 1, b32, ctypes.byref(ok)) == sv.SNARKV_ERR_ARG
         assert a.ipa_fold_coeffs_dev(None, 3, b32, 1, b32, 0, None) == sv.SNARKV_ERR_ARG
-        ctx = _FakeCtx(device=0)
-        whole, shard = _FakeKey(device=0, k=3, first=0, count=8), _FakeKey(device=0, k=3, first=4, count=4)
+        ctx = AU.FakeCtx(device=0)
+        whole, shard = AU.FakeKey(device=0, k=3, first=0, count=8), AU.FakeKey(device=0, k=3, first=4, count=4)
         pc, pw, ps = ctypes.addressof(ctx), ctypes.addressof(whole), ctypes.addressof(shard)
         assert a.ipa_decide_folded(pc, pw, b32, b64, 1, b32, None) == sv.SNARKV_ERR_ARG       # nowhere to put the verdict
         assert a.ipa_decide_folded(pc, pw, b32, b64, 0, b32, ctypes.byref(ok)) == sv.SNARKV_ERR_EMPTY   # m = 0
         assert ok.value == 0                                                                   # never left as it was
         assert a.ipa_decide_folded(pc, ps, b32, b64, 1, b32, ctypes.byref(ok)) == sv.SNARKV_ERR_LENGTH  # a shard
-        other = _FakeCtx(device=1)
+        other = AU.FakeCtx(device=1)
         assert a.ipa_decide_folded(ctypes.addressof(other), pw, b32, b64, 1, b32, ctypes.byref(ok)) == sv.SNARKV_ERR_ARG
         assert a.ipa_fold_coeffs_dev(pc, 3, b32, 0, b32, 0, pc) == sv.SNARKV_ERR_EMPTY         # m = 0
         assert a.ipa_fold_coeffs_dev(pc, 0, b32, 1, b32, 0, pc) == sv.SNARKV_ERR_LENGTH        # k = 0
@@ -105,11 +88,8 @@ def test_the_host_library_of_the_folded_decide():
     from snark_verifier_amd import host_api_pallas as HP
 
     hdr = os.path.join(INC, "snarkv_host_pallas_fold.h")
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", hdr],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    txt = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(snarkv_host_pallas_[a-z0-9_]+)\s*\(", txt)))
+    AU.assert_strict_c99(hdr)
+    declared = AU.declared(hdr, r"\b(snarkv_host_pallas_[a-z0-9_]+)\s*\(")
     assert declared == ["snarkv_host_pallas_fold_last_error", "snarkv_host_pallas_ipa_decide_all_folded",
                         "snarkv_host_pallas_ipa_fold_challenge", "snarkv_host_pallas_plonk_verify_folded"]
     assert sorted(HP._FOLD_SIGNATURES) == declared and not set(declared) & set(HP._SIGNATURES)

@@ -7,8 +7,6 @@ oracle/kzg.py::bdfg21_query_sets: set order, polynomial order, evaluation order.
 import ctypes
 import os
 import random
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -20,34 +18,26 @@ MO_HDR = os.path.join(INC, "snarkv_ipa_multiopen.h")
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-
-def _declared(path):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b((?:snarkv|bn254|pallas)_[a-z0-9_]+)\s*\(", txt)))
+import abi_util as AU  # noqa: E402
 
 
 def test_headers_are_strict_c99():
     for h in (POLY_HDR, MO_HDR):
-        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", h],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
+        AU.assert_strict_c99(h)
 
 
 def test_both_libraries_export_every_declared_name_and_the_tables_list_them():
     import snark_verifier_amd as sv
-    from snark_verifier_amd import _lib, ipa_batch, ipa_create, ipa_fold, ipa_multiopen, ipa_prover, poly
+    from snark_verifier_amd import ipa_multiopen, poly
     from snark_verifier_amd import pallas as PL
 
     want_poly = sorted(p + n for p in ("snarkv_", "snarkv_pallas_") for n in ("poly_lincomb_dev", "poly_eval_dev", "poly_div_linear_dev"))
     want_mo = sorted(["bn254_ipa_multiopen_create_proof", "pallas_ipa_multiopen_create_proof", "snarkv_ipa_multiopen_create_proof",
                       "snarkv_ipa_multiopen_create_proof_dev", "snarkv_pallas_ipa_multiopen_create_proof",
                       "snarkv_pallas_ipa_multiopen_create_proof_dev"])
-    assert _declared(POLY_HDR) == want_poly == sorted(poly.SIGNATURES)
-    assert _declared(MO_HDR) == want_mo == sorted(ipa_multiopen.SIGNATURES)
-    others = set(_lib._SIGNATURES) | set(ipa_prover.SIGNATURES) | set(ipa_batch.SIGNATURES) | set(ipa_fold.SIGNATURES) | \
-        set(ipa_create.SIGNATURES)
-    assert not (set(want_poly) | set(want_mo)) & others
-    assert not set(want_poly) & set(want_mo)
+    assert AU.declared(POLY_HDR) == want_poly == sorted(poly.SIGNATURES)
+    assert AU.declared(MO_HDR) == want_mo == sorted(ipa_multiopen.SIGNATURES)
+    assert not set(want_poly) & AU.other_tables(poly) and not set(want_mo) & AU.other_tables(ipa_multiopen)
     bn, pa = sv.load_library(), PL.load_library()
     for name in want_poly + want_mo:
         assert hasattr(pa if "pallas" in name else bn, name), name
@@ -59,17 +49,6 @@ def test_both_libraries_export_every_declared_name_and_the_tables_list_them():
     assert sv.ipa_multiopen.proof_bytes(10, 3) == 64 * 10 + 32 * 3 + 160
 
 
-class _FakeKey(ctypes.Structure):
-    """the head of the deciding key (csrc/ctx.hpp: device, k, points, first, count), enough for the argument checks
-    that come before any device work; the calls below never get past them"""
-    _fields_ = [("device", ctypes.c_int), ("k", ctypes.c_uint32), ("d_points", ctypes.c_void_p), ("first", ctypes.c_size_t),
-                ("count", ctypes.c_size_t), ("rest", ctypes.c_uint8 * 256)]
-
-
-class _FakeCtx(ctypes.Structure):
-    _fields_ = [("device", ctypes.c_int), ("rest", ctypes.c_uint8 * 8192)]
-
-
 def test_multiopen_refuses_bad_arguments_without_a_device():
     import snark_verifier_amd as sv
     from snark_verifier_amd import ipa_multiopen as MO
@@ -79,8 +58,8 @@ def test_multiopen_refuses_bad_arguments_without_a_device():
         b32, b64, polys = b"\x00" * 32, b"\x01" * 64, b"\x00" * (32 * 8 * 2)
         proof, xi, u = ctypes.create_string_buffer(b"\xaa" * 512, 512), ctypes.create_string_buffer(96), ctypes.create_string_buffer(64)
         plen = ctypes.c_size_t(7)
-        ctx = _FakeCtx(device=0)
-        whole, shard = _FakeKey(device=0, k=3, first=0, count=8), _FakeKey(device=0, k=3, first=4, count=4)
+        ctx = AU.FakeCtx(device=0)
+        whole, shard = AU.FakeKey(device=0, k=3, first=0, count=8), AU.FakeKey(device=0, k=3, first=4, count=4)
         pc, pw, ps = ctypes.addressof(ctx), ctypes.addressof(whole), ctypes.addressof(shard)
         one = (1).to_bytes(32, "little")
         two = (2).to_bytes(32, "little")
@@ -99,7 +78,7 @@ def test_multiopen_refuses_bad_arguments_without_a_device():
         # the key and n: a shard, n that is not the key's 2^k, a context on another device
         assert call(dk=ps) == sv.SNARKV_ERR_LENGTH and plen.value == 0
         assert call(n=4) == sv.SNARKV_ERR_LENGTH
-        other = _FakeCtx(device=1)
+        other = AU.FakeCtx(device=1)
         assert call(c=ctypes.addressof(other)) == sv.SNARKV_ERR_ARG
         # nothing to open
         assert call(npolys=0) == sv.SNARKV_ERR_EMPTY and call(nq=0) == sv.SNARKV_ERR_EMPTY
@@ -119,7 +98,7 @@ def test_poly_calls_refuse_bad_arguments_without_a_device():
 
     for pallas in (False, True):
         a = P.api(pallas)
-        ctx = _FakeCtx(device=0)
+        ctx = AU.FakeCtx(device=0)
         pc = ctypes.addressof(ctx)
         base = 0x10000  # device addresses are only compared here, never followed
         idx = (ctypes.c_uint32 * 2)(0, 1)

@@ -4,33 +4,26 @@ exactly those names (and none of snarkv_amd.h's), and null arguments are refused
 work."""
 import ctypes
 import os
-import re
-import subprocess
+
+import abi_util as AU
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "snarkv_ipa_prover.h")
 
 
-def _declared():
-    txt = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(snarkv_[a-z0-9_]+)\s*\(", txt)))
-
-
 def test_header_is_strict_c99():
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", HDR],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    AU.assert_strict_c99(HDR)
 
 
 def test_both_libraries_export_every_declared_name():
     import snark_verifier_amd as sv
-    from snark_verifier_amd import _lib, ipa_prover
+    from snark_verifier_amd import ipa_prover
     from snark_verifier_amd import pallas as PL
 
-    declared = _declared()
+    declared = AU.declared(HDR, r"\b(snarkv_[a-z0-9_]+)\s*\(")
     assert len(declared) == 16
     assert sorted(ipa_prover.SIGNATURES) == declared
-    assert not set(declared) & set(_lib._SIGNATURES)  # snarkv_amd.h's table stays as it is
+    assert not set(declared) & AU.other_tables(ipa_prover)  # the other tables stay as they are
     bn, pa = sv.load_library(), PL.load_library()
     for name in declared:
         assert hasattr(bn if not name.startswith("snarkv_pallas_") else pa, name), name

@@ -5,7 +5,6 @@ the header's order, each overlap on its own, without a device (the argument chec
 fake struct)."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -14,6 +13,7 @@ INC = os.path.join(ROOT, "include")
 HDR = os.path.join(INC, "snarkv_lookup.h")
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
+import abi_util as AU  # noqa: E402
 import bn254 as BN  # noqa: E402
 import pallas as PA  # noqa: E402
 
@@ -21,32 +21,21 @@ FIELD = {"bn254": BN.R, "pallas": PA.R}
 CALLS = ["poly_sort_dev", "lookup_permute_dev", "lookup_product_dev"]
 
 
-def _declared(path):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b((?:snarkv|bn254|pallas)_[a-z0-9_]+)\s*\(", txt)))
-
-
 def test_header_is_strict_c99():
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", HDR],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    AU.assert_strict_c99(HDR)
 
 
 def test_both_libraries_export_the_declared_names_and_the_table_lists_them():
     import snark_verifier_amd as sv
-    from snark_verifier_amd import _lib, ipa_batch, ipa_create, ipa_fold, ipa_multiopen, ipa_prover, lookup, ntt, poly, poly_prod
+    from snark_verifier_amd import lookup
     from snark_verifier_amd import pallas as PL
-    from snark_verifier_amd import quotient
 
     want = sorted(p + c for p in ("snarkv_", "snarkv_pallas_") for c in CALLS)
-    assert _declared(HDR) == want == sorted(lookup.SIGNATURES)
-    others = set(_lib._SIGNATURES) | set(ipa_prover.SIGNATURES) | set(ipa_batch.SIGNATURES) | set(ipa_fold.SIGNATURES) | \
-        set(ipa_create.SIGNATURES) | set(poly.SIGNATURES) | set(ipa_multiopen.SIGNATURES) | set(ntt.SIGNATURES) | \
-        set(poly_prod.SIGNATURES) | set(quotient.SIGNATURES)
-    assert not set(want) & others
+    assert AU.declared(HDR) == want == sorted(lookup.SIGNATURES)
+    assert not set(want) & AU.other_tables(lookup)
     for hdr in os.listdir(INC):  # no other header declares them
         if hdr != "snarkv_lookup.h":
-            assert not set(want) & set(_declared(os.path.join(INC, hdr))), hdr
+            assert not set(want) & set(AU.declared(os.path.join(INC, hdr))), hdr
     bn, pa = sv.load_library(), PL.load_library()
     for name in want:
         assert hasattr(pa if "pallas" in name else bn, name), name
@@ -71,11 +60,6 @@ def test_the_sizes_of_the_header_are_the_modules(tmp_path):
     assert L.SCAN_LEVEL_BLOCK == 1024 and L.STATUS_BYTES == 16
 
 
-class _FakeCtx(ctypes.Structure):
-    """the head of the context (csrc/ctx.hpp: device first), enough for the checks that come before any device work"""
-    _fields_ = [("device", ctypes.c_int), ("rest", ctypes.c_uint8 * 8192)]
-
-
 def test_every_refusal_comes_without_a_device():
     """(a correct call is never made here: a fake context must not reach the runtime)"""
     import snark_verifier_amd as sv
@@ -85,7 +69,7 @@ def test_every_refusal_comes_without_a_device():
     for pallas, curve in ((False, "bn254"), (True, "pallas")):
         a = L.api(pallas)
         r = FIELD[curve]
-        ctx = _FakeCtx(device=0)
+        ctx = AU.FakeCtx(device=0)
         pc = ctypes.addressof(ctx)
         fe = lambda v: int(v).to_bytes(32, "little")  # noqa: E731
         n = 100

@@ -29,7 +29,7 @@ def host_lib(curve):
         spec = importlib.util.spec_from_file_location("_snarkv_build", os.path.join(ROOT, "snark-verifier_amd", "build.py"))
         b = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(b)
-        lib = ctypes.CDLL(b.build_hosttest_lookup(curve))
+        lib = ctypes.CDLL(b.build_hosttest("lookup", curve))
         lib.hl_curve.restype = ctypes.c_char_p
         for fn in (lib.hl_less, lib.hl_equal, lib.hl_permute):
             fn.restype = ctypes.c_int

@@ -5,7 +5,6 @@ call; the context is a fake struct), and the generated root of unity is the orac
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,30 +12,22 @@ INC = os.path.join(ROOT, "include")
 HDR = os.path.join(INC, "snarkv_ntt.h")
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import abi_util as AU  # noqa: E402
 import ntt_util as U  # noqa: E402
 
 
-def _declared(path):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b((?:snarkv|bn254|pallas)_[a-z0-9_]+)\s*\(", txt)))
-
-
 def test_header_is_strict_c99():
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", HDR],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    AU.assert_strict_c99(HDR)
 
 
 def test_both_libraries_export_the_declared_names_and_the_table_lists_them():
     import snark_verifier_amd as sv
-    from snark_verifier_amd import _lib, ipa_batch, ipa_create, ipa_fold, ipa_multiopen, ipa_prover, ntt, poly
+    from snark_verifier_amd import ntt
     from snark_verifier_amd import pallas as PL
 
     want = sorted(["snarkv_ntt_dev", "snarkv_ntt_max_k", "snarkv_pallas_ntt_dev", "snarkv_pallas_ntt_max_k"])
-    assert _declared(HDR) == want == sorted(ntt.SIGNATURES)
-    others = set(_lib._SIGNATURES) | set(ipa_prover.SIGNATURES) | set(ipa_batch.SIGNATURES) | set(ipa_fold.SIGNATURES) | \
-        set(ipa_create.SIGNATURES) | set(poly.SIGNATURES) | set(ipa_multiopen.SIGNATURES)
-    assert not set(want) & others
+    assert AU.declared(HDR) == want == sorted(ntt.SIGNATURES)
+    assert not set(want) & AU.other_tables(ntt)
     bn, pa = sv.load_library(), PL.load_library()
     for name in want:
         assert hasattr(pa if "pallas" in name else bn, name), name
@@ -54,11 +45,6 @@ def test_max_k_is_the_smaller_of_the_two_adicity_and_30():
     assert ntt.api(True).ntt_max_k() == 30 == min(U.PA.TWO_ADICITY, 30)
 
 
-class _FakeCtx(ctypes.Structure):
-    """the head of the context (csrc/ctx.hpp: device first), enough for the checks that come before any device work"""
-    _fields_ = [("device", ctypes.c_int), ("rest", ctypes.c_uint8 * 8192)]
-
-
 def test_every_refusal_comes_without_a_device():
     import snark_verifier_amd as sv
     from snark_verifier_amd import ntt
@@ -66,7 +52,7 @@ def test_every_refusal_comes_without_a_device():
     for pallas, curve in ((False, "bn254"), (True, "pallas")):
         a = ntt.api(pallas)
         r = U.CURVES[curve].R
-        ctx = _FakeCtx(device=0)
+        ctx = AU.FakeCtx(device=0)
         pc = ctypes.addressof(ctx)
         base = 0x100000  # device addresses are only compared here, never followed
         k, count = 4, 3

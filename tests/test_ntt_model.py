@@ -35,7 +35,7 @@ def host_lib(curve):
         spec = importlib.util.spec_from_file_location("_snarkv_build", os.path.join(ROOT, "snark-verifier_amd", "build.py"))
         b = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(b)
-        lib = ctypes.CDLL(b.build_hosttest_ntt(curve))
+        lib = ctypes.CDLL(b.build_hosttest("ntt", curve))
         lib.hn_curve.restype = ctypes.c_char_p
         lib.hn_bound.restype = ctypes.c_double
         lib.hn_max.restype = ctypes.c_double

@@ -5,7 +5,6 @@ none with the other tables, and every refusal of the header comes back with its 
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,6 +12,7 @@ INC = os.path.join(ROOT, "include")
 HDR = os.path.join(INC, "snarkv_poly_prod.h")
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
+import abi_util as AU  # noqa: E402
 import bn254 as BN  # noqa: E402
 import pallas as PA  # noqa: E402
 
@@ -20,27 +20,18 @@ FIELD = {"bn254": BN.R, "pallas": PA.R}
 CALLS = ["poly_mul_dev", "poly_prod_affine_dev", "poly_batch_invert_dev", "poly_grand_product_dev", "poly_perm_product_dev"]
 
 
-def _declared(path):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b((?:snarkv|bn254|pallas)_[a-z0-9_]+)\s*\(", txt)))
-
-
 def test_header_is_strict_c99():
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", HDR],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    AU.assert_strict_c99(HDR)
 
 
 def test_both_libraries_export_the_declared_names_and_the_table_lists_them():
     import snark_verifier_amd as sv
-    from snark_verifier_amd import _lib, ipa_batch, ipa_create, ipa_fold, ipa_multiopen, ipa_prover, ntt, poly, poly_prod
+    from snark_verifier_amd import poly_prod
     from snark_verifier_amd import pallas as PL
 
     want = sorted(p + c for p in ("snarkv_", "snarkv_pallas_") for c in CALLS)
-    assert _declared(HDR) == want == sorted(poly_prod.SIGNATURES)
-    others = set(_lib._SIGNATURES) | set(ipa_prover.SIGNATURES) | set(ipa_batch.SIGNATURES) | set(ipa_fold.SIGNATURES) | \
-        set(ipa_create.SIGNATURES) | set(poly.SIGNATURES) | set(ipa_multiopen.SIGNATURES) | set(ntt.SIGNATURES)
-    assert not set(want) & others
+    assert AU.declared(HDR) == want == sorted(poly_prod.SIGNATURES)
+    assert not set(want) & AU.other_tables(poly_prod)
     bn, pa = sv.load_library(), PL.load_library()
     for name in want:
         assert hasattr(pa if "pallas" in name else bn, name), name
@@ -65,11 +56,6 @@ def test_the_module_constants_are_the_kernels():
     assert poly_prod.AFFINE_TERMS == const("kProdAffineTerms")
 
 
-class _FakeCtx(ctypes.Structure):
-    """the head of the context (csrc/ctx.hpp: device first), enough for the checks that come before any device work"""
-    _fields_ = [("device", ctypes.c_int), ("rest", ctypes.c_uint8 * 8192)]
-
-
 def _u32(vals):
     return (ctypes.c_uint32 * len(vals))(*vals)
 
@@ -83,7 +69,7 @@ def test_every_refusal_comes_without_a_device():
     for pallas, curve in ((False, "bn254"), (True, "pallas")):
         a = poly_prod.api(pallas)
         r = FIELD[curve]
-        ctx = _FakeCtx(device=0)
+        ctx = AU.FakeCtx(device=0)
         pc = ctypes.addressof(ctx)
         fe = lambda v: int(v).to_bytes(32, "little")  # noqa: E731
         n, n_polys = 48, 4

@@ -32,7 +32,7 @@ def host_lib(curve):
         spec = importlib.util.spec_from_file_location("_snarkv_build", os.path.join(ROOT, "snark-verifier_amd", "build.py"))
         b = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(b)
-        lib = ctypes.CDLL(b.build_hosttest_poly_prod(curve))
+        lib = ctypes.CDLL(b.build_hosttest("poly_prod", curve))
         lib.hpp_curve.restype = ctypes.c_char_p
         lib.hpp_grand_product.restype = ctypes.c_uint32
         lib.hpp_batch_invert.restype = ctypes.c_uint32

@@ -25,7 +25,7 @@ def host_lib(curve):
     spec = importlib.util.spec_from_file_location("_snarkv_build", os.path.join(ROOT, "snark-verifier_amd", "build.py"))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
-    lib = ctypes.CDLL(b.build_hosttest_poly(curve))
+    lib = ctypes.CDLL(b.build_hosttest("poly", curve))
     lib.hp_curve.restype = ctypes.c_char_p
     lib.hp_query_sets.restype = ctypes.c_size_t
     assert lib.hp_curve() == curve.encode()

@@ -5,7 +5,6 @@ program prints them), and every refusal of the header comes back with its code, 
 argument checks come before any HIP call; the context is a fake struct)."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -14,6 +13,7 @@ INC = os.path.join(ROOT, "include")
 HDR = os.path.join(INC, "snarkv_quotient.h")
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
+import abi_util as AU  # noqa: E402
 import bn254 as BN  # noqa: E402
 import pallas as PA  # noqa: E402
 
@@ -21,30 +21,20 @@ FIELD = {"bn254": BN.R, "pallas": PA.R}
 CALLS = ["poly_extend_dev", "quotient_eval_dev", "poly_div_vanishing_dev", "quotient_dev"]
 
 
-def _declared(path):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b((?:snarkv|bn254|pallas)_[a-z0-9_]+)\s*\(", txt)))
-
-
 def test_header_is_strict_c99():
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", HDR],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    AU.assert_strict_c99(HDR)
 
 
 def test_both_libraries_export_the_declared_names_and_the_table_lists_them():
     import snark_verifier_amd as sv
-    from snark_verifier_amd import _lib, ipa_batch, ipa_create, ipa_fold, ipa_multiopen, ipa_prover, ntt, poly, poly_prod, quotient
+    from snark_verifier_amd import quotient
     from snark_verifier_amd import pallas as PL
 
     want = sorted(p + c for p in ("snarkv_", "snarkv_pallas_") for c in CALLS)
-    assert _declared(HDR) == want == sorted(quotient.SIGNATURES)
-    others = set(_lib._SIGNATURES) | set(ipa_prover.SIGNATURES) | set(ipa_batch.SIGNATURES) | set(ipa_fold.SIGNATURES) | \
-        set(ipa_create.SIGNATURES) | set(poly.SIGNATURES) | set(ipa_multiopen.SIGNATURES) | set(ntt.SIGNATURES) | \
-        set(poly_prod.SIGNATURES)
-    assert not set(want) & others
+    assert AU.declared(HDR) == want == sorted(quotient.SIGNATURES)
+    assert not set(want) & AU.other_tables(quotient)
     for hdr in ("snarkv_amd.h", "snarkv_pallas.h"):  # the two pinned headers do not declare them
-        assert not set(want) & set(_declared(os.path.join(INC, hdr)))
+        assert not set(want) & set(AU.declared(os.path.join(INC, hdr)))
     bn, pa = sv.load_library(), PL.load_library()
     for name in want:
         assert hasattr(pa if "pallas" in name else bn, name), name
@@ -82,11 +72,6 @@ def test_the_macros_of_the_header_and_the_helpers_of_the_module_agree(tmp_path):
     assert p.packed() == Q.pack_instr(Q.MUL, 1, Q.COL(0), Q.COL(0)) + Q.pack_instr(Q.FMA, 5, Q.REG(1), Q.CONST(0), Q.COL(3, -1))
 
 
-class _FakeCtx(ctypes.Structure):
-    """the head of the context (csrc/ctx.hpp: device first), enough for the checks that come before any device work"""
-    _fields_ = [("device", ctypes.c_int), ("rest", ctypes.c_uint8 * 8192)]
-
-
 def test_every_refusal_comes_without_a_device():
     """(a correct call is never made here: a fake context must not reach the runtime)"""
     import snark_verifier_amd as sv
@@ -98,7 +83,7 @@ def test_every_refusal_comes_without_a_device():
         a = Q.api(pallas)
         r = FIELD[curve]
         max_k = int(ntt.api(pallas).ntt_max_k())
-        ctx = _FakeCtx(device=0)
+        ctx = AU.FakeCtx(device=0)
         pc = ctypes.addressof(ctx)
         fe = lambda v: int(v).to_bytes(32, "little")  # noqa: E731
         k, e, n_cols = 4, 2, 3

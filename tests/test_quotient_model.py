@@ -27,7 +27,7 @@ def host_lib(curve):
         spec = importlib.util.spec_from_file_location("_snarkv_build", os.path.join(ROOT, "snark-verifier_amd", "build.py"))
         b = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(b)
-        lib = ctypes.CDLL(b.build_hosttest_quotient(curve))
+        lib = ctypes.CDLL(b.build_hosttest("quotient", curve))
         lib.hq_curve.restype = ctypes.c_char_p
         lib.hq_two_adicity.restype = ctypes.c_uint32
         lib.hq_row.restype = ctypes.c_uint32
