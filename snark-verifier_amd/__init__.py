@@ -47,6 +47,9 @@ from . import poly_prod  # noqa: F401,E402  (column products: batch inversion, g
 from . import quotient  # noqa: F401,E402  (the quotient on the extended coset: extension, gate program, vanishing division: include/snarkv_quotient.h)
 from . import lookup  # noqa: F401,E402  (the lookup argument: sort, permuted columns, product Z: include/snarkv_lookup.h)
 from . import ipa_multiopen  # noqa: F401,E402  (the Bgh19 multi-open prover in one call: include/snarkv_ipa_multiopen.h)
+from . import poly_batch  # noqa: F401,E402  (many evaluations of resident polynomials in one call: include/snarkv_poly_batch.h)
+from . import kzg_multiopen  # noqa: F401,E402  (the Gwc19 and Bdfg21 multi-open provers, BN254: include/snarkv_kzg_multiopen.h)
+from . import host_kzg_open  # noqa: F401,E402  (the same through the host mirror and its transcripts: include/snarkv_host_kzg_open.h)
 
 __all__ = [
     "host_api",
@@ -61,6 +64,9 @@ __all__ = [
     "quotient",
     "lookup",
     "ipa_multiopen",
+    "poly_batch",
+    "kzg_multiopen",
+    "host_kzg_open",
     "IpaProver",
     "Context",
     "DecidingKey",

@@ -15,7 +15,7 @@ BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsnarkv_amd.so")
 UNITS = ["ctx", "msm_api", "capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "ipa_prover", "mgpu",
          "decompress", "msm_shared", "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen", "ntt",
-         "poly_prod", "quotient", "lookup"]
+         "poly_prod", "quotient", "lookup", "poly_batch", "kzg_multiopen"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
@@ -23,7 +23,7 @@ FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
 
 # the public headers the device units include (include/; the host mirror's are in _host_stale)
 DEVICE_HEADERS = ("amd", "pallas", "pallas_decompress", "ipa_prover", "ipa_batch", "ipa_fold", "ipa_create", "poly", "ipa_multiopen",
-                  "ntt", "poly_prod", "quotient", "lookup")
+                  "ntt", "poly_prod", "quotient", "lookup", "poly_batch", "kzg_multiopen")
 
 
 def _deps():
@@ -77,7 +77,8 @@ def _link(lib, res, extra):
 
 # The pasta build of the curve-generic units (csrc/pallas.hip explains the flags, csrc/ctx.hpp the policy they select).
 PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover", "decompress_pallas", "msm_shared",
-                "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen", "ntt", "poly_prod", "quotient", "lookup"]
+                "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen", "ntt", "poly_prod", "quotient", "lookup",
+                "poly_batch"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
 
@@ -102,8 +103,9 @@ def devtest_sources():
 #   quotient   the gate program and the vanishing table (csrc/quotient.h)
 #   lookup     the comparison, merge path, tiled sort and permute rule (csrc/lookup.h)
 #   args       the entry points' shared argument checks (csrc/poly_args.hpp)
+#   kzg_open   the host-side plan of the KZG multi-open provers (csrc/kzg_multiopen_plan.h)
 HOSTTEST_DIR = os.path.join(HERE, "..", "tests", "hosttest")
-HOSTTESTS = ("curve", "poly", "ntt", "poly_prod", "quotient", "lookup", "args")
+HOSTTESTS = ("curve", "poly", "ntt", "poly_prod", "quotient", "lookup", "args", "kzg_open")
 HOSTTEST_EXCEPTIONS = {"curve": ("libhosttest_%s.so", ("curve_ops.h",))}  # the others: libhosttest_<name>_<curve>.so, one source
 
 
@@ -161,7 +163,7 @@ def _host_stale(out, dev_lib):
     inc = os.path.join(os.path.dirname(HERE), "include")
     srcs = [os.path.join(HOST, f) for f in os.listdir(HOST)] + [os.path.join(inc, h) for h in (
         "snarkv_host.h", "snarkv_host_pallas.h", "snarkv_pallas_decompress.h", "snarkv_host_pallas_fold.h", "snarkv_ipa_fold.h",
-        "snarkv_host_pallas_prove.h", "snarkv_ipa_create.h")]
+        "snarkv_host_pallas_prove.h", "snarkv_ipa_create.h", "snarkv_kzg_multiopen.h", "snarkv_host_kzg_open.h")]
     newest = max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(dev_lib)])
     return not os.path.exists(out) or os.path.getmtime(out) < newest
 

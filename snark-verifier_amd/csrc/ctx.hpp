@@ -83,6 +83,7 @@ enum Slot {
   SLOT_POLY_PROD,    // the column products (poly_prod.hip): a staged pass of affine terms, the totals of the scans' levels
   SLOT_QUOTIENT,     // the quotient (quotient.hip): the staged program and constants, the vanishing polynomial's table
   SLOT_LOOKUP,       // the lookup argument (lookup.hip): the sort's partition points, the flags and the totals of the count scans
+  SLOT_POLY_BATCH,   // the batched evaluation (poly_batch.hip): a chunk's indices, and per query the roots and totals of the levels
   SLOT_COUNT
 };
 

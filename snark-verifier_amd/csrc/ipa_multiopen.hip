@@ -15,6 +15,7 @@
 #include <string.h>
 #include <algorithm>
 #include <vector>
+#include "fr_host.h"
 #include "ipa_multiopen_sets.h"
 #include "ipa_opening.hpp"
 #include "poly.hpp"
@@ -47,80 +48,12 @@ __global__ void __launch_bounds__(64) k_mo_check_rem(const uint32_t* __restrict_
 
 namespace {
 
-// ---- the host's few scalars: Fr29 in the Montgomery domain, every result brought back to (-r/8, 9r/8) ----------------------
-Fr29 h_red(const Fr29& x) { return fr29_mul(fr29_norm(x), fr29_one()); }
-Fr29 h_load(const uint8_t* b32) {
-  uint32_t w[8];
-  memcpy(w, b32, 32);
-  return h_red(fr29_from_canonical(w));
-}
-void h_store(uint8_t* b32, const Fr29& v) {
-  uint32_t w[8];
-  fr29_to_canonical(v, w);
-  memcpy(b32, w, 32);
-}
-Fr29 h_add(const Fr29& a, const Fr29& b) { return h_red(fr29_add(a, b)); }
-Fr29 h_sub(const Fr29& a, const Fr29& b) {
-  Fr29 d;
-  for (int i = 0; i < 9; ++i) d.v[i] = a.v[i] - b.v[i];
-  return h_red(d);
-}
-Fr29 h_mul(const Fr29& a, const Fr29& b) { return h_red(fr29_mul(a, b)); }
-bool h_is_zero(const Fr29& v) {
-  uint8_t b[32];
-  h_store(b, v);
-  for (int i = 0; i < 32; ++i)
-    if (b[i]) return false;
-  return true;
-}
-Fr29 h_inv(const Fr29& x) {  // x^(r-2)
-  constexpr uint32_t rw[8] = SNARKV_FR_R_LIMBS;
-  uint32_t e[8], borrow = 2;
-  for (int i = 0; i < 8; ++i) {
-    e[i] = rw[i] - borrow;
-    borrow = rw[i] < borrow ? 1u : 0u;
-  }
-  Fr29 acc = fr29_one();
-  for (int b = 255; b >= 0; --b) {
-    acc = h_mul(acc, acc);
-    if ((e[b >> 5] >> (b & 31)) & 1u) acc = h_mul(acc, x);
-  }
-  return acc;
-}
-std::vector<Fr29> h_powers(const Fr29& x, size_t count) {
-  std::vector<Fr29> out(count, fr29_one());
-  for (size_t i = 1; i < count; ++i) out[i] = h_mul(out[i - 1], x);
-  return out;
-}
+// ---- the host's few scalars: fr_host.h; a challenge comes from the transcript -----------------------------------------------
 Fr29 h_squeeze(Blake2bState& st, uint8_t* canon32_or_null) {
   uint32_t w[8];
   const Fr29 c = h_red(tr_squeeze(st, w));
   if (canon32_or_null) memcpy(canon32_or_null, w, 32);
   return c;
-}
-
-// the coefficients of the polynomial of degree < m through (pts[j], vals[j]); false when two points coincide
-bool h_interpolate(const std::vector<Fr29>& pts, const std::vector<Fr29>& vals, std::vector<Fr29>& out) {
-  const size_t m = pts.size();
-  out.assign(m, fr29_zero());
-  for (size_t j = 0; j < m; ++j) {
-    std::vector<Fr29> num(1, fr29_one());
-    Fr29 den = fr29_one();
-    for (size_t i = 0; i < m; ++i) {
-      if (i == j) continue;
-      std::vector<Fr29> next(num.size() + 1, fr29_zero());  // num (X - p_i)
-      for (size_t t = 0; t < num.size(); ++t) {
-        next[t + 1] = h_add(next[t + 1], num[t]);
-        next[t] = h_sub(next[t], h_mul(pts[i], num[t]));
-      }
-      num.swap(next);
-      den = h_mul(den, h_sub(pts[j], pts[i]));
-    }
-    if (h_is_zero(den)) return false;
-    const Fr29 f = h_mul(vals[j], h_inv(den));
-    for (size_t t = 0; t < m; ++t) out[t] = h_add(out[t], h_mul(num[t], f));
-  }
-  return true;
 }
 
 struct MoArgs {

@@ -13,5 +13,8 @@ int poly_enqueue_lincomb(snarkv_ctx* ctx, const void* d_polys, size_t n, const u
                          size_t count, void* d_out);
 int poly_enqueue_eval(snarkv_ctx* ctx, const void* d_coeffs, size_t n, const void* d_point, void* d_out);
 int poly_enqueue_div_linear(snarkv_ctx* ctx, const void* d_coeffs, size_t n, const void* d_root, void* d_quot, void* d_rem);
+// poly_batch.hip (include/snarkv_poly_batch.h): out[i] = polys[q_poly[i]](points[q_point[i]]), the index arrays on the host
+int poly_enqueue_eval_many(snarkv_ctx* ctx, const void* d_polys, size_t n, const void* d_points, const uint32_t* q_poly,
+                           const uint32_t* q_point, size_t count, void* d_out);
 
 }  // namespace snarkv

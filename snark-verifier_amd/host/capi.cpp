@@ -2,6 +2,7 @@
 // arguments, calls the C++ mirror of the reference API (plonk.hpp / pcs.hpp / aggregation.hpp) and maps
 // `Result<_, Error>` / panics to return codes.  All EC work happens behind GpuNativeLoader on the device.
 #include "../../include/snarkv_host.h"
+#include "../../include/snarkv_host_kzg_open.h"
 
 #include <cstdio>
 #include <cstring>
@@ -536,3 +537,79 @@ int snarkv_host_accumulator_from_limbs(const uint8_t limbs[16 * 32], uint8_t acc
 }
 
 }  // extern "C"
+
+// include/snarkv_host_kzg_open.h: the prefix replayed to a fresh transcript TR, then `MOS::create_proof` of pcs.hpp
+namespace {
+template <class TR>
+int kzg_open_tr(int mos, const KzgOpenInput& in, const Fr& z, const std::vector<Query<Fr>>& queries, const uint8_t* prefix,
+                size_t prefix_len, std::vector<uint8_t>& written, uint8_t* challenges_out32) {
+  TR t;
+  for (size_t i = 0; i < prefix_len;) {
+    const uint8_t tag = prefix[i++];
+    const size_t len = tag == 0 ? 32 : tag == 1 ? 64 : 0;
+    if (tag > 2 || i + len > prefix_len) return arg_error("malformed prefix");
+    Error e;
+    if (tag == 0) {
+      Fr x;
+      if (!Fr::from_bytes(prefix + i, &x)) return arg_error("a scalar of the prefix is not a canonical Fr");
+      e = t.write_scalar(x);
+    } else if (tag == 1) {
+      e = t.write_ec_point(G1Affine::from_bytes(prefix + i));
+    } else {
+      (void)t.squeeze_challenge();
+    }
+    if (!e.ok()) return error_code(e);
+    i += len;
+  }
+  const size_t before = t.stream().size();
+  if (mos == SNARKV_HOST_MOS_GWC19) {
+    auto p = Gwc19::create_proof(in, z, queries, t);
+    if (!p.ok()) return error_code(p.err);
+    if (challenges_out32) p.value->v.to_bytes(challenges_out32);
+  } else {
+    auto p = Bdfg21::create_proof(in, z, queries, t);
+    if (!p.ok()) return error_code(p.err);
+    if (challenges_out32) {
+      p.value->mu.to_bytes(challenges_out32);
+      p.value->gamma.to_bytes(challenges_out32 + 32);
+      p.value->z_prime.to_bytes(challenges_out32 + 64);
+    }
+  }
+  written.assign(t.stream().begin() + before, t.stream().end());
+  return 1;
+}
+}  // namespace
+
+extern "C" int snarkv_host_kzg_open(int mos, int transcript, snarkv_ctx* ctx, const void* d_srs64, const void* d_polys32, size_t n,
+                                    size_t n_polys, const uint8_t z32[32], const uint32_t* q_poly, const uint8_t* q_shift32,
+                                    const uint8_t* q_eval32, size_t n_queries, const uint8_t* prefix, size_t prefix_len,
+                                    uint8_t* proof_out, size_t proof_cap, size_t* proof_len, uint8_t* challenges_out32) {
+  static_assert(SNARKV_HOST_MOS_GWC19 == SNARKV_KZG_MOS_GWC19 && SNARKV_HOST_MOS_BDFG21 == SNARKV_KZG_MOS_BDFG21, "one numbering");
+  if (!ctx || !d_srs64 || !d_polys32 || !z32 || !q_poly || !q_shift32 || !q_eval32 || !proof_len || (prefix_len && !prefix))
+    return arg_error("null argument");
+  *proof_len = 0;
+  if (mos != SNARKV_HOST_MOS_GWC19 && mos != SNARKV_HOST_MOS_BDFG21) return arg_error("unknown multi-open scheme");
+  return guarded([&] {
+    Fr z;
+    if (!Fr::from_bytes(z32, &z)) return arg_error("z is not a canonical Fr");
+    std::vector<Query<Fr>> queries(n_queries);
+    for (size_t i = 0; i < n_queries; ++i) {
+      queries[i].poly = q_poly[i];
+      if (!Fr::from_bytes(q_shift32 + 32 * i, &queries[i].shift) || !Fr::from_bytes(q_eval32 + 32 * i, &queries[i].eval))
+        return arg_error("a shift or an evaluation is not a canonical Fr");
+    }
+    const KzgOpenInput in{ctx, d_srs64, d_polys32, n, n_polys};
+    std::vector<uint8_t> written;
+    const int rc = transcript == SNARKV_HOST_TRANSCRIPT_EVM ? kzg_open_tr<EvmTranscript>(mos, in, z, queries, prefix, prefix_len, written, challenges_out32)
+                   : transcript == SNARKV_HOST_TRANSCRIPT_POSEIDON ? kzg_open_tr<PoseidonTranscript>(mos, in, z, queries, prefix, prefix_len, written, challenges_out32)
+                                                                   : arg_error("unknown transcript kind");
+    if (rc != 1) return rc;
+    *proof_len = written.size();
+    if (written.size() > proof_cap || (written.size() && !proof_out)) {
+      g_last_error = "proof buffer too small";
+      return SNARKV_HOST_ERR_CAPACITY;
+    }
+    if (written.size()) memcpy(proof_out, written.data(), written.size());
+    return 1;
+  });
+}

@@ -26,6 +26,9 @@
 #include <functional>
 
 #include "msm.hpp"
+#if !defined(SNARKV_HOST_PALLAS)
+#include "../../include/snarkv_kzg_multiopen.h"
+#endif
 
 #ifndef SNARKV_HOST_TRACE
 #define SNARKV_HOST_TRACE 0  // build with -DSNARKV_HOST_TRACE=1 for the host / device split of the phases on stderr (dev aid)
@@ -165,8 +168,24 @@ struct KzgAsProof {
   }
 };
 
-struct Gwc19 {};
-struct Bdfg21 {};
+struct Gwc19Proof;
+struct Bdfg21Proof;
+// Resident polynomials and the SRS as the device provers take them (include/snarkv_kzg_multiopen.h): device addresses,
+// n_polys x n coefficients poly-major, the n points [s^i] G.  `ctx` is the context whose stream has the polynomials ready.
+struct KzgOpenInput {
+  snarkv_ctx* ctx;
+  const void* d_srs;
+  const void* d_polys;
+  size_t n, n_polys;
+};
+// The scheme tags; each carries the prover's half (halo2's `ProverGWC` / `ProverSHPLONK`), defined below next to `read` and
+// `pcs_verify`: squeeze the challenges, open on the device, write the points in exactly the order `read` consumes.
+struct Gwc19 {
+  static Result<Gwc19Proof> create_proof(const KzgOpenInput& in, const Fr& z, const std::vector<Query<Fr>>& queries, Transcript& t);
+};
+struct Bdfg21 {
+  static Result<Bdfg21Proof> create_proof(const KzgOpenInput& in, const Fr& z, const std::vector<Query<Fr>>& queries, Transcript& t);
+};
 
 // ------------------------------------------------------------------ KzgAs
 template <class MOS>
@@ -528,6 +547,87 @@ inline Result<KzgAccumulator> KzgAs<Bdfg21>::pcs_verify<Bdfg21Proof>(const KzgSu
   // bdfg21.rs:80-81
   auto pts = L::multi_scalar_multiplication_batch({lhs.pairs(svk.g), rhs.pairs(svk.g)});
   return Result<KzgAccumulator>::Ok(KzgAccumulator{pts[0], pts[1]});
+}
+
+// ------------------------------------------------------------- the provers
+namespace kzg_open_detail {
+struct PackedQueries {
+  std::vector<uint32_t> poly;
+  std::vector<uint8_t> shift, eval;
+  explicit PackedQueries(const std::vector<Query<Fr>>& queries) : shift(32 * queries.size()), eval(32 * queries.size()) {
+    for (size_t i = 0; i < queries.size(); ++i) {
+      poly.push_back((uint32_t)queries[i].poly);
+      queries[i].shift.to_bytes(&shift[32 * i]);
+      queries[i].eval.to_bytes(&eval[32 * i]);
+    }
+  }
+};
+// a refusal of the device call: what the caller got wrong (an evaluation that does not match, coinciding points) is an
+// assertion failure of the proof being made; anything else is the device's
+template <class T>
+inline Result<T> refused(int rc, const char* what) {
+  const std::string why = std::string(what) + ": " + snarkv_last_error();
+  if (rc == SNARKV_ERR_ARG) return Result<T>::Err(Error::assertion(why));
+  throw std::runtime_error(why);
+}
+}  // namespace kzg_open_detail
+
+// gwc19.rs:102-110 read from the other side: squeeze v, write the W_k.  (The verifier squeezes u after them.)
+inline Result<Gwc19Proof> Gwc19::create_proof(const KzgOpenInput& in, const Fr& z, const std::vector<Query<Fr>>& queries,
+                                              Transcript& t) {
+  using R = Result<Gwc19Proof>;
+  const kzg_open_detail::PackedQueries q(queries);
+  Gwc19Proof proof;
+  proof.v = t.squeeze_challenge();
+  uint8_t z32[32], v32[32];
+  z.to_bytes(z32);
+  proof.v.to_bytes(v32);
+  std::vector<uint8_t> ws(64 * std::max<size_t>(queries.size(), 1));  // never more sets than queries
+  size_t n_sets = 0;
+  const int rc = snarkv_kzg_gwc19_create_proof_dev(in.ctx, in.d_srs, in.d_polys, in.n, in.n_polys, z32, q.poly.data(), q.shift.data(),
+                                                   q.eval.data(), queries.size(), v32, ws.data(), queries.size(), &n_sets);
+  if (rc != SNARKV_OK) return kzg_open_detail::refused<Gwc19Proof>(rc, "kzg_gwc19_create_proof");
+  for (size_t k = 0; k < n_sets; ++k) {
+    proof.ws.push_back(G1Affine::from_bytes(&ws[64 * k]));
+    const Error e = t.write_ec_point(proof.ws.back());
+    if (!e.ok()) return R::Err(e);
+  }
+  return R::Ok(std::move(proof));
+}
+
+// bdfg21.rs:85-120 read from the other side: squeeze mu, squeeze gamma, write W, squeeze z', write W'.  W meets the
+// transcript inside the device call, between its two synchronisations (snarkv_kzg_challenge_fn).
+inline Result<Bdfg21Proof> Bdfg21::create_proof(const KzgOpenInput& in, const Fr& z, const std::vector<Query<Fr>>& queries,
+                                                Transcript& t) {
+  using R = Result<Bdfg21Proof>;
+  const kzg_open_detail::PackedQueries q(queries);
+  Bdfg21Proof proof;
+  proof.mu = t.squeeze_challenge();
+  proof.gamma = t.squeeze_challenge();
+  uint8_t z32[32], mu32[32], gamma32[32], zp32[32];
+  z.to_bytes(z32);
+  proof.mu.to_bytes(mu32);
+  proof.gamma.to_bytes(gamma32);
+  struct Draw {
+    Transcript* t;
+    Error err;
+    static int run(void* user, const uint8_t w64[64], uint8_t z_prime32[32]) {
+      Draw* d = static_cast<Draw*>(user);
+      d->err = d->t->write_ec_point(G1Affine::from_bytes(w64));
+      if (!d->err.ok()) return 1;
+      d->t->squeeze_challenge().to_bytes(z_prime32);
+      return 0;
+    }
+  } draw{&t, {}};
+  const int rc = snarkv_kzg_bdfg21_create_proof_dev(in.ctx, in.d_srs, in.d_polys, in.n, in.n_polys, z32, q.poly.data(), q.shift.data(),
+                                                    q.eval.data(), queries.size(), mu32, gamma32, &Draw::run, &draw, proof.w.b, zp32,
+                                                    proof.w_prime.b);
+  if (!draw.err.ok()) return R::Err(draw.err);
+  if (rc != SNARKV_OK) return kzg_open_detail::refused<Bdfg21Proof>(rc, "kzg_bdfg21_create_proof");
+  if (!Fr::from_bytes(zp32, &proof.z_prime)) throw std::runtime_error("kzg_bdfg21_create_proof: non-canonical z'");
+  const Error e = t.write_ec_point(proof.w_prime);
+  if (!e.ok()) return R::Err(e);
+  return R::Ok(std::move(proof));
 }
 
 // --------------------------------------------------------- LimbsEncoding

@@ -871,3 +871,90 @@ std::vector<uint8_t> transcript_stream(const Transcript& t) {  // what a writer 
 }  // namespace
 #define SNARKV_DRV(name) hd_##name
 #include "ipa_driver.inc"
+
+// ---- the KZG multi-open provers (pcs.hpp `Gwc19::create_proof` / `Bdfg21::create_proof`) round trip -----------------------
+// A writing transcript of kind `tkind` takes the prefix (items tagged 0 = scalar [32], 1 = point [64], 2 = squeeze and
+// discard), then `create_proof` over the resident polynomials; the bytes (one of them flipped when flip_at < their count) go
+// to a reading transcript that reads the same prefix, then `read`, `pcs_verify` against `commitments64` and the device
+// decider under dk320.  Returns 1 accept, 0 reject, -10 when the reader fails on the bytes, another negative code for a
+// prover-side error; proof_out = the bytes as written (prefix included), *proof_len their count.
+namespace {
+int kzg_open_prefix(Transcript& t, const uint8_t* prefix, size_t prefix_len, bool writing) {
+  for (size_t i = 0; i < prefix_len;) {
+    const uint8_t tag = prefix[i++];
+    Error e;
+    if (tag == 0) {
+      Fr x;
+      if (!Fr::from_bytes(prefix + i, &x)) return -3;
+      if (writing) e = t.write_scalar(x);
+      else e = t.read_scalar().err;
+      i += 32;
+    } else if (tag == 1) {
+      if (writing) e = t.write_ec_point(G1Affine::from_bytes(prefix + i));
+      else e = t.read_ec_point().err;
+      i += 64;
+    } else if (tag == 2) {
+      (void)t.squeeze_challenge();
+    } else {
+      return -2;
+    }
+    if (!e.ok()) return error_code(e);
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int hd_kzg_open_roundtrip(int mos, int tkind, snarkv_ctx* ctx, const void* d_srs, const void* d_polys, size_t n,
+                                     size_t n_polys, const uint8_t* commitments64, const uint8_t* z32, const uint32_t* q_poly,
+                                     const uint8_t* q_shift32, const uint8_t* q_eval32, size_t n_queries, const uint8_t* prefix,
+                                     size_t prefix_len, const uint8_t* dk320, size_t flip_at, uint8_t* proof_out, size_t proof_cap,
+                                     size_t* proof_len) {
+  return guarded([&] {
+    Fr z;
+    if (!Fr::from_bytes(z32, &z)) return -3;
+    std::vector<Query<Fr>> queries(n_queries);
+    std::vector<Query<std::monostate>> shapes(n_queries);
+    for (size_t i = 0; i < n_queries; ++i) {
+      queries[i].poly = shapes[i].poly = q_poly[i];
+      if (!Fr::from_bytes(q_shift32 + 32 * i, &queries[i].shift) || !Fr::from_bytes(q_eval32 + 32 * i, &queries[i].eval)) return -3;
+      shapes[i].shift = queries[i].shift;
+    }
+    const KzgOpenInput in{ctx, d_srs, d_polys, n, n_polys};
+    auto wt = make_transcript(tkind, nullptr, 0);
+    int rc = kzg_open_prefix(*wt, prefix, prefix_len, true);
+    if (rc != 0) return rc - 20;
+    if (mos == SNARKV_KZG_MOS_GWC19) {
+      auto p = Gwc19::create_proof(in, z, queries, *wt);
+      if (!p.ok()) return error_code(p.err) - 40;
+    } else {
+      auto p = Bdfg21::create_proof(in, z, queries, *wt);
+      if (!p.ok()) return error_code(p.err) - 40;
+    }
+    std::vector<uint8_t> bytes = transcript_stream(*wt);
+    *proof_len = bytes.size();
+    if (bytes.size() > proof_cap) return -6;
+    memcpy(proof_out, bytes.data(), bytes.size());
+    if (flip_at < bytes.size()) bytes[flip_at] ^= 1;
+    // ---- the verifier's side
+    auto rt = make_transcript(tkind, bytes.data(), bytes.size());
+    if (kzg_open_prefix(*rt, prefix, prefix_len, false) != 0) return -10;
+    std::vector<G1Affine> cpts(n_polys);
+    std::vector<MsmT> commitments;
+    for (size_t i = 0; i < n_polys; ++i) cpts[i] = G1Affine::from_bytes(commitments64 + 64 * i);
+    for (size_t i = 0; i < n_polys; ++i) commitments.push_back(MsmT::base(&cpts[i]));
+    const KzgSuccinctVerifyingKey svk{G1Affine::from_bytes(dk320)};
+    KzgDecidingKey dk(G1Affine::from_bytes(dk320), G2Affine::from_bytes(dk320 + 64), G2Affine::from_bytes(dk320 + 192));
+    Result<KzgAccumulator> acc;
+    if (mos == SNARKV_KZG_MOS_GWC19) {
+      auto p = gwc19::read(shapes, *rt);
+      if (!p.ok()) return -10;
+      acc = KzgAs<Gwc19>::pcs_verify(svk, commitments, z, queries, *p.value);
+    } else {
+      auto p = Bdfg21Proof::read(*rt);
+      if (!p.ok()) return -10;
+      acc = KzgAs<Bdfg21>::pcs_verify(svk, commitments, z, queries, *p.value);
+    }
+    if (!acc.ok()) return error_code(acc.err);
+    return KzgAs<Gwc19>::decide(dk, *acc.value).ok() ? 1 : 0;
+  });
+}
