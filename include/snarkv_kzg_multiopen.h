@@ -5,7 +5,9 @@
  * gwc19::msms / bdfg21::msms (host/pcs.hpp, oracle/kzg.py) give lhs = [s] rhs.
  *
  * libsnarkv_amd.so only: KZG is BN254's.  Conventions of snarkv_amd.h: scalars 32-byte little-endian canonical, points
- * x || y 64 bytes with the identity as 64 zero bytes, return 0 or a negative SNARKV_ERR_*.
+ * x || y 64 bytes with the identity as 64 zero bytes, return 0 or a negative SNARKV_ERR_*.  The calls speak the wire form
+ * whatever the context's default flags say: SNARKV_FLAG_MONTGOMERY as a default neither applies to them nor is changed by
+ * them; SNARKV_FLAG_VALIDATE as a default applies (below).
  *
  * Arguments
  *   srs64         the n points [s^i] G, i < n (host memory; device memory, 16-byte aligned, for _dev)

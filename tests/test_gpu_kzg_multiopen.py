@@ -36,16 +36,6 @@ ZERO64 = b"\x00" * 64
 ERR_ARG = -5
 
 
-def _pack(vals):
-    return b"".join(int(v).to_bytes(32, "little") for v in vals)
-
-
-def _dev(raw):
-    import torch
-
-    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).cuda()
-
-
 @pytest.fixture(scope="module")
 def KM():
     from snark_verifier_amd import kzg_multiopen
@@ -56,7 +46,7 @@ def KM():
 @pytest.fixture(scope="module")
 def srs_bytes():
     """[s^i] G for i < 1000, once; a shorter SRS is its head"""
-    return U.srs(SECRET, 1000)
+    return U.srs_of(SECRET, 1000)
 
 
 @pytest.fixture(scope="module")
@@ -68,56 +58,11 @@ def dk(gpu_ctx):
     key.close()
 
 
-class Resident:
-    """polynomials and SRS on the device, and the queries with the evaluations the device computed"""
-
-    def __init__(self, ctx, srs_bytes, polys, z, pairs):
-        import torch
-
-        from snark_verifier_amd import poly_batch
-
-        self.polys, self.z, self.n = polys, z, len(polys[0])
-        self.srs = srs_bytes[:64 * self.n]
-        self.d_srs, self.d_polys = _dev(self.srs), _dev(b"".join(_pack(p) for p in polys))
-        shifts = sorted({sh for _, sh in pairs})
-        d_points = _dev(_pack([z * sh % R for sh in shifts]))
-        d_out = torch.zeros(32 * len(pairs), dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()
-        poly_batch.eval_many_dev(ctx, self.d_polys, self.n, len(polys), d_points, len(shifts), [p for p, _ in pairs],
-                                 [shifts.index(sh) for _, sh in pairs], d_out)
-        ctx.sync()
-        raw = d_out.cpu().numpy().tobytes()
-        self.queries = [(p, sh, int.from_bytes(raw[32 * i:32 * i + 32], "little")) for i, (p, sh) in enumerate(pairs)]
+Resident = U.Resident  # the device flow is shared with tests/test_gpu_kzg_multiopen_shapes.py
 
 
-def check_case(gpu_ctx, KM, dk, res, tag, forms=("host", "dev"), decide=True):
-    polys, z, queries = res.polys, res.z, res.queries
-    assert queries == U.with_evals(polys, z, [(p, sh) for p, sh, _ in queries])  # the device's evaluations are Horner's
-    rng = random.Random("challenges " + tag)
-    v, u, mu, gamma = (rng.randrange(1, R) for _ in range(4))
-    draw = U.draw_from(tag)
-    want_ws = U.gwc19_prove(SECRET, polys, z, queries, v)
-    want_w, want_zp, want_wp = U.bdfg21_prove(SECRET, polys, z, queries, mu, gamma, draw)
-    for form in forms:
-        if form == "host":
-            ws = KM.gwc19_create_proof(gpu_ctx, res.srs, polys, z, queries, v)
-            w, zp, wp = KM.bdfg21_create_proof(gpu_ctx, res.srs, polys, z, queries, mu, gamma, draw)
-        else:
-            ws = KM.gwc19_create_proof_dev(gpu_ctx, res.d_srs, res.d_polys, res.n, len(polys), z, queries, v)
-            w, zp, wp = KM.bdfg21_create_proof_dev(gpu_ctx, res.d_srs, res.d_polys, res.n, len(polys), z, queries, mu, gamma, draw)
-        assert ws == want_ws, (tag, form)
-        assert (w, zp, wp) == (want_w, want_zp, want_wp), (tag, form)
-    assert len(ws) == KM.n_sets(KM.MOS_GWC19, queries)
-    if not decide:
-        return ws, (w, zp, wp)
-    cms = [K.Msm.base(c) for c in U.commitments(SECRET, polys)]
-    pt = O.g1_from_bytes
-    for lhs, rhs in (K.gwc19_verify(O.G1_GEN, cms, z, queries, v, [pt(x) for x in ws], u),
-                     K.bdfg21_verify(O.G1_GEN, cms, z, queries, mu, gamma, pt(w), zp, pt(wp))):
-        assert rhs is not None and lhs == O.g1_mul(rhs, SECRET), tag
-        assert gpu_ctx.decide(dk, O.g1_to_bytes(lhs) + O.g1_to_bytes(rhs)), tag
-        assert not gpu_ctx.decide(dk, O.g1_to_bytes(O.g1_add(lhs, O.G1_GEN)) + O.g1_to_bytes(rhs)), tag
-    return ws, (w, zp, wp)
+def check_case(gpu_ctx, KM, dk, res, tag, **kw):
+    return U.check_case(gpu_ctx, KM, dk, SECRET, res, tag, **kw)
 
 
 @pytest.mark.parametrize("n", [4, 257, 1000])
