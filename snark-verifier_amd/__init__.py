@@ -50,6 +50,7 @@ from . import ipa_multiopen  # noqa: F401,E402  (the Bgh19 multi-open prover in 
 from . import poly_batch  # noqa: F401,E402  (many evaluations of resident polynomials in one call: include/snarkv_poly_batch.h)
 from . import kzg_multiopen  # noqa: F401,E402  (the Gwc19 and Bdfg21 multi-open provers, BN254: include/snarkv_kzg_multiopen.h)
 from . import host_kzg_open  # noqa: F401,E402  (the same through the host mirror and its transcripts: include/snarkv_host_kzg_open.h)
+from . import host_plonk_prove  # noqa: F401,E402  (the PLONK prover session of the host mirror: include/snarkv_host_plonk_prove.h)
 
 __all__ = [
     "host_api",
@@ -67,6 +68,7 @@ __all__ = [
     "poly_batch",
     "kzg_multiopen",
     "host_kzg_open",
+    "host_plonk_prove",
     "IpaProver",
     "Context",
     "DecidingKey",

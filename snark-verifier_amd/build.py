@@ -15,7 +15,7 @@ BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsnarkv_amd.so")
 UNITS = ["ctx", "msm_api", "capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "ipa_prover", "mgpu",
          "decompress", "msm_shared", "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen", "ntt",
-         "poly_prod", "quotient", "lookup", "poly_batch", "kzg_multiopen"]
+         "poly_prod", "quotient", "lookup", "poly_batch", "kzg_multiopen", "plonk_prove"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
@@ -23,7 +23,7 @@ FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
 
 # the public headers the device units include (include/; the host mirror's are in _host_stale)
 DEVICE_HEADERS = ("amd", "pallas", "pallas_decompress", "ipa_prover", "ipa_batch", "ipa_fold", "ipa_create", "poly", "ipa_multiopen",
-                  "ntt", "poly_prod", "quotient", "lookup", "poly_batch", "kzg_multiopen")
+                  "ntt", "poly_prod", "quotient", "lookup", "poly_batch", "kzg_multiopen", "plonk_prove")
 
 
 def _deps():
@@ -163,7 +163,8 @@ def _host_stale(out, dev_lib):
     inc = os.path.join(os.path.dirname(HERE), "include")
     srcs = [os.path.join(HOST, f) for f in os.listdir(HOST)] + [os.path.join(inc, h) for h in (
         "snarkv_host.h", "snarkv_host_pallas.h", "snarkv_pallas_decompress.h", "snarkv_host_pallas_fold.h", "snarkv_ipa_fold.h",
-        "snarkv_host_pallas_prove.h", "snarkv_ipa_create.h", "snarkv_kzg_multiopen.h", "snarkv_host_kzg_open.h")]
+        "snarkv_host_pallas_prove.h", "snarkv_ipa_create.h", "snarkv_kzg_multiopen.h", "snarkv_host_kzg_open.h",
+        "snarkv_host_plonk_prove.h", "snarkv_plonk_prove.h", "snarkv_quotient.h", "snarkv_ntt.h", "snarkv_poly.h", "snarkv_poly_batch.h")]
     newest = max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(dev_lib)])
     return not os.path.exists(out) or os.path.getmtime(out) < newest
 

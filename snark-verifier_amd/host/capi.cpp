@@ -3,6 +3,7 @@
 // `Result<_, Error>` / panics to return codes.  All EC work happens behind GpuNativeLoader on the device.
 #include "../../include/snarkv_host.h"
 #include "../../include/snarkv_host_kzg_open.h"
+#include "../../include/snarkv_host_plonk_prove.h"
 
 #include <cstdio>
 #include <cstring>
@@ -11,6 +12,7 @@
 #include "aggregation.hpp"
 #include "pcs.hpp"
 #include "plonk.hpp"
+#include "plonk_prover.hpp"
 #include "serde_json.hpp"
 #include "transcript.hpp"
 #include "wire.hpp"
@@ -613,3 +615,119 @@ extern "C" int snarkv_host_kzg_open(int mos, int transcript, snarkv_ctx* ctx, co
     return 1;
   });
 }
+
+// include/snarkv_host_plonk_prove.h: a `PlonkProver<MOS, TR>` session of plonk_prover.hpp behind a handle
+struct snarkv_host_plonk_prover {
+  std::unique_ptr<PlonkProverSession> s;
+  size_t next_phase = 0;
+  bool closed = false;  // finish has returned a verdict, or a call has failed past its argument checks: only destroy is left
+};
+
+namespace {
+template <class MOS, class TR>
+int plonk_prover_begin_tr(const PlonkProtocol& pr, snarkv_ctx* ctx, const void* d_srs, const void* d_pre,
+                          const std::vector<std::vector<Fr>>& inst, snarkv_host_plonk_prover** out) {
+  auto s = std::make_unique<PlonkProver<MOS, TR>>();
+  const Error e = s->begin(pr, ctx, d_srs, d_pre, inst);
+  if (!e.ok()) return e.kind == Error::AssertionFailure ? SNARKV_HOST_ERR_OTHER : error_code(e);
+  *out = new snarkv_host_plonk_prover{std::move(s)};
+  return 1;
+}
+}  // namespace
+
+extern "C" {
+
+int snarkv_host_plonk_prover_plan(const snarkv_host_protocol* protocol, uint32_t* e, size_t* n_cols, size_t* n_instr,
+                                  size_t* n_consts, size_t* bytes) {
+  if (!protocol) return arg_error("null argument");
+  return guarded([&] {
+    try {
+      const ProverPlan plan = plan_prover(protocol->pr, snarkv_ntt_max_k());
+      if (e) *e = plan.num.e;
+      if (n_cols) *n_cols = plan.num.n_cols;
+      if (n_instr) *n_instr = plan.num.prog.size();
+      if (n_consts) *n_consts = plan.num.consts.size();
+      if (bytes) *bytes = plan.device_bytes;
+      return 1;
+    } catch (const InvalidProtocol& ex) {
+      return error_code(Error{Error::InvalidProtocol, ex.what()});
+    }
+  });
+}
+
+int snarkv_host_plonk_prover_begin(const snarkv_host_protocol* protocol, int mos, int transcript, snarkv_ctx* ctx,
+                                   const void* d_srs64, const void* d_preprocessed32, const uint8_t* instances,
+                                   size_t instances_len, snarkv_host_plonk_prover** out) {
+  if (!out) return arg_error("null argument");
+  *out = nullptr;
+  if (!protocol || !ctx || !d_srs64 || !instances || (!d_preprocessed32 && !protocol->pr.preprocessed.empty()))
+    return arg_error("null argument");
+  if (mos != SNARKV_HOST_MOS_GWC19 && mos != SNARKV_HOST_MOS_BDFG21) return arg_error("unknown multi-open scheme");
+  if (transcript != SNARKV_HOST_TRANSCRIPT_EVM && transcript != SNARKV_HOST_TRANSCRIPT_POSEIDON)
+    return arg_error("unknown transcript kind: the prover writes the host's EVM or Poseidon transcript");
+  if ((uintptr_t)d_srs64 % 16 || (uintptr_t)d_preprocessed32 % 16) return arg_error("a device address is not 16-byte aligned");
+  return guarded([&] {
+    if (snarkv_ctx_get_flags(ctx) & SNARKV_FLAG_MONTGOMERY) return arg_error("the context's default form is Montgomery: the prover speaks the wire form");
+    const std::vector<std::vector<Fr>> inst = wire::parse_instances(instances, instances_len);
+    const PlonkProtocol& pr = protocol->pr;
+    const bool gwc = mos == SNARKV_HOST_MOS_GWC19, evm = transcript == SNARKV_HOST_TRANSCRIPT_EVM;
+    return gwc ? (evm ? plonk_prover_begin_tr<Gwc19, EvmTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, out)
+                      : plonk_prover_begin_tr<Gwc19, PoseidonTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, out))
+               : (evm ? plonk_prover_begin_tr<Bdfg21, EvmTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, out)
+                      : plonk_prover_begin_tr<Bdfg21, PoseidonTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, out));
+  });
+}
+
+int snarkv_host_plonk_prover_phase(snarkv_host_plonk_prover* p, const void* d_witness32, int form, uint8_t* challenges_out32,
+                                   size_t cap, size_t* n_challenges) {
+  if (!p || !n_challenges) return arg_error("null argument");
+  *n_challenges = 0;
+  if (p->closed) return arg_error("the session has ended: only destroy is accepted");
+  if (p->next_phase >= p->s->num_phases()) return arg_error("every phase has been given: finish comes next");
+  if (form != SNARKV_HOST_PLONK_COEFFS && form != SNARKV_HOST_PLONK_VALUES) return arg_error("unknown form of the witness polynomials");
+  const size_t want = p->s->phase_challenges(p->next_phase);
+  *n_challenges = want;
+  if (!d_witness32 && p->s->phase_witnesses(p->next_phase)) return arg_error("null argument");
+  if ((uintptr_t)d_witness32 % 16) return arg_error("a device address is not 16-byte aligned");
+  if (want && !challenges_out32) return arg_error("null argument");
+  if (cap < want) {
+    g_last_error = "challenge buffer too small";
+    return SNARKV_HOST_ERR_CAPACITY;
+  }
+  const int rc = guarded([&] {
+    auto r = p->s->phase(d_witness32, form);
+    if (!r.ok()) return r.err.kind == Error::AssertionFailure ? SNARKV_HOST_ERR_OTHER : error_code(r.err);
+    for (size_t i = 0; i < r.value->size(); ++i) (*r.value)[i].to_bytes(challenges_out32 + 32 * i);
+    return 1;
+  });
+  if (rc == 1) ++p->next_phase;
+  else p->closed = true;
+  return rc;
+}
+
+int snarkv_host_plonk_prover_finish(snarkv_host_plonk_prover* p, uint8_t* proof_out, size_t proof_cap, size_t* proof_len) {
+  if (!p || !proof_len) return arg_error("null argument");
+  *proof_len = 0;
+  if (p->closed) return arg_error("the session has ended: only destroy is accepted");
+  if (p->next_phase < p->s->num_phases()) return arg_error("finish comes after the last phase");
+  const size_t need = p->s->proof_length();
+  if (proof_cap < need) {
+    *proof_len = need;
+    g_last_error = "proof buffer too small";
+    return SNARKV_HOST_ERR_CAPACITY;
+  }
+  if (!proof_out && need) return arg_error("null argument");
+  p->closed = true;
+  return guarded([&] {
+    auto r = p->s->finish();
+    if (!r.ok()) return error_code(r.err);  // an assertion failure is 0: the witness does not satisfy the constraints
+    if (r.value->size() != need) throw std::runtime_error("the proof is not of the length the protocol gives");
+    memcpy(proof_out, r.value->data(), need);
+    *proof_len = need;
+    return 1;
+  });
+}
+
+void snarkv_host_plonk_prover_destroy(snarkv_host_plonk_prover* p) { delete p; }
+
+}  // extern "C"

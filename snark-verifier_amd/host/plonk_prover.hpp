@@ -1,0 +1,338 @@
+// PlonkProver<MOS, TR>: the mirror image of PlonkVerifier (plonk.hpp) -- protocol and witness polynomials in, proof bytes out.
+// Driven by the protocol alone: `PlonkProof::read` fixes what is written and when, the numerator is compiled to a gate program
+// (plonk_compile.hpp), and the witness polynomials arrive phase by phase from a caller who makes them with the resident-column
+// calls (snarkv_ntt.h, snarkv_poly_prod.h, snarkv_lookup.h).  BN254 / KZG; TR is EvmTranscript or PoseidonTranscript.
+//
+// A session:
+//   begin    one resident buffer:  [l_0] [X] | preprocessed | instance | witness | quotient slot | h | work | small block
+//            The quotient (snarkv_quotient_dev) reads the columns from the extra ones up to the last witness, contiguous; the
+//            opening reads from `preprocessed` on and finds the quotient at index n_pre + n_inst + n_wit.  The instance
+//            polynomials are built (values in rows 0.., inverse transform); the transcript absorbs the initial state and
+//            the instances as `PlonkProof::read` does.  No synchronisation.
+//   phase    copy (values: and inverse-transform) into the witness columns, commit them in one batch of MSMs over the SRS,
+//            write the points, squeeze the phase's challenges.  One synchronisation (none for a phase without witnesses).
+//   finish   quotient -> tail check -> chunk commitments (sync 1: points and the status word) -> z -> every evaluation in one
+//            batched call (sync 2) -> Q = sum (z^n)^i h_i into the quotient slot -> the verifier's own identity check on the
+//            host -> MOS::create_proof (Gwc19: one more synchronisation, Bdfg21: two).
+// The prover draws no randomness: blinding rows and the random polynomial are the caller's columns.
+#pragma once
+#include <type_traits>
+
+#include "../../include/snarkv_ntt.h"
+#include "../../include/snarkv_plonk_prove.h"
+#include "../../include/snarkv_poly.h"
+#include "../../include/snarkv_poly_batch.h"
+#include "../../include/snarkv_quotient.h"
+#include "plonk.hpp"
+#include "plonk_compile.hpp"
+#include "transcript.hpp"
+
+namespace snarkv_host {
+
+constexpr const char* kPlonkUnsatisfied = "the witness does not satisfy the protocol's constraints";
+enum PlonkWitnessForm { kPlonkCoeffs = 0, kPlonkValues = 1 };
+
+// halo2's ZETA: a primitive cube root of unity, g^((r - 1) / 3) with g = 7 -- the coset shift of the extended domain
+inline Fr plonk_zeta() {
+  uint8_t b[32];
+  (Fr::zero() - Fr::one()).to_bytes(b);  // r - 1
+  unsigned rem = 0;
+  for (int i = 31; i >= 0; --i) {
+    const unsigned cur = rem * 256 + b[i];
+    b[i] = (uint8_t)(cur / 3);
+    rem = cur % 3;
+  }
+  if (rem != 0) throw Panic("3 does not divide r - 1");
+  uint64_t e[4];
+  memcpy(e, b, 32);
+  return Fr::from_u64(7).pow(e);
+}
+
+struct PlonkProverSession {
+  virtual ~PlonkProverSession() = default;
+  virtual size_t num_phases() const = 0;
+  virtual size_t phase_challenges(size_t phase) const = 0;
+  virtual size_t phase_witnesses(size_t phase) const = 0;
+  virtual size_t proof_length() const = 0;
+  // Result of phase: the challenges squeezed
+  virtual Result<std::vector<Fr>> phase(const void* d_witness, int form) = 0;
+  virtual Result<std::vector<uint8_t>> finish() = 0;
+};
+
+template <class MOS, class TR>
+struct PlonkProver : PlonkProverSession {
+  static constexpr size_t kPointBytes = std::is_same<TR, EvmTranscript>::value ? 64 : 32;
+
+  PlonkProtocol pr;
+  ProverPlan plan;
+  snarkv_ctx* ctx = nullptr;
+  const void* d_srs = nullptr;
+  uint8_t* d_mem = nullptr;
+  std::vector<std::vector<Fr>> instances;
+  std::vector<Fr> challenges;
+  TR t;
+  size_t next_phase = 0, witness_done = 0, n_sets = 0;
+  // byte offsets into d_mem
+  size_t off_polys = 0, off_h = 0, off_work = 0, off_blk = 0;
+  size_t blk_points = 0, blk_evals = 0, blk_bytes = 0;
+  std::vector<int32_t> rotations;  // the distinct ones of the evaluations and the queries
+  std::vector<PQuery> wanted;      // every (poly, rotation) to evaluate, the protocol's evaluations first
+
+  static void dev(int rc, const char* what) {
+    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + snarkv_last_error());
+  }
+  uint8_t* col(size_t i) const { return d_mem + 32 * plan.n * i; }                      // by column of the buffer
+  uint8_t* poly(size_t p) const { return d_mem + off_polys + 32 * plan.n * p; }         // by the protocol's index
+  uint32_t* status() const { return (uint32_t*)(d_mem + off_blk); }
+  uint8_t* commits() const { return d_mem + off_blk + 32; }
+
+  PlonkProver() = default;
+  PlonkProver(const PlonkProver&) = delete;
+  ~PlonkProver() override {
+    if (d_mem) snarkv_plonk_session_free(ctx, d_mem);
+  }
+
+  // d_preprocessed: the n_pre polynomials as coefficients, n each, in the protocol's order
+  Error begin(const PlonkProtocol& protocol, snarkv_ctx* c, const void* srs, const void* d_preprocessed,
+              const std::vector<std::vector<Fr>>& inst) {
+    pr = protocol;
+    ctx = c;
+    d_srs = srs;
+    instances = inst;
+    try {
+      plan = plan_prover(pr, snarkv_ntt_max_k());
+    } catch (const InvalidProtocol& e) {
+      return Error{Error::InvalidProtocol, e.what()};
+    }
+    if (plan.k == 0) return Error{Error::InvalidProtocol, "k = 0: the polynomial X has no column of one coefficient"};
+    if (pr.num_instance.size() != inst.size()) return Error{Error::InvalidInstances, ""};
+    for (size_t i = 0; i < inst.size(); ++i)
+      if (pr.num_instance[i] != inst[i].size() || inst[i].size() > plan.n) return Error{Error::InvalidInstances, ""};
+    const size_t n = plan.n;
+    // the rotations and the evaluation list
+    std::set<PQuery> seen;
+    for (auto* list : {&pr.evaluations, &pr.queries})
+      for (auto& q : *list) {
+        if (std::find(rotations.begin(), rotations.end(), q.rotation) == rotations.end()) rotations.push_back(q.rotation);
+        if (q.poly != plan.q_index && seen.insert(q).second) wanted.push_back(q);
+      }
+    if (std::find(rotations.begin(), rotations.end(), 0) == rotations.end()) rotations.push_back(0);  // the chunks' point
+    {
+      std::vector<uint32_t> qp;
+      std::vector<uint8_t> qs(32 * pr.queries.size());
+      for (size_t i = 0; i < pr.queries.size(); ++i) {
+        qp.push_back((uint32_t)pr.queries[i].poly);
+        pr.domain.rotate_scalar(Fr::one(), pr.queries[i].rotation).to_bytes(&qs[32 * i]);
+      }
+      if (pr.queries.empty()) return Error{Error::InvalidProtocol, "the protocol has no queries"};
+      dev(snarkv_kzg_multiopen_sets(std::is_same<MOS, Gwc19>::value ? SNARKV_KZG_MOS_GWC19 : SNARKV_KZG_MOS_BDFG21, qp.data(), qs.data(),
+                                    qp.size(), &n_sets),
+          "kzg_multiopen_sets");
+    }
+    // the layout
+    size_t most = plan.num_chunk;
+    for (size_t ph = 0; ph < plan.phases; ++ph) most = std::max(most, pr.num_witness[ph]);
+    off_polys = 32 * n * plan.num.first_poly;
+    off_h = 32 * n * plan.cols_total();
+    off_work = off_h + 32 * plan.N;
+    off_blk = off_work + 32 * plan.N * plan.num.n_cols;
+    blk_points = 32 + 64 * most;
+    blk_evals = blk_points + 32 * rotations.size();
+    blk_bytes = blk_evals + 32 * (wanted.size() + plan.num_chunk);
+    void* d = nullptr;
+    dev(snarkv_plonk_session_alloc(ctx, off_blk + blk_bytes, &d), "plonk_session_alloc");
+    d_mem = (uint8_t*)d;
+    // the extra columns: l_0 = (1/n, 1/n, ...) as coefficients, X = (0, 1, 0, ...)
+    if (plan.num.l0_col >= 0) {
+      std::vector<uint8_t> l0(32 * n);
+      pr.domain.n_inv.to_bytes(l0.data());
+      for (size_t i = 1; i < n; ++i) memcpy(&l0[32 * i], l0.data(), 32);
+      dev(snarkv_plonk_session_upload(ctx, col(plan.num.l0_col), l0.data(), l0.size()), "plonk_session_upload");
+    }
+    if (plan.num.x_col >= 0) {
+      uint8_t one[32];
+      Fr::one().to_bytes(one);
+      dev(snarkv_plonk_session_upload(ctx, col(plan.num.x_col) + 32, one, 32), "plonk_session_upload");
+    }
+    if (plan.n_pre) dev(snarkv_plonk_session_copy(ctx, poly(0), d_preprocessed, 32 * n * plan.n_pre), "plonk_session_copy");
+    if (plan.n_inst) {
+      std::vector<uint8_t> vals(32 * n * plan.n_inst, 0);
+      for (size_t i = 0; i < inst.size(); ++i)
+        for (size_t j = 0; j < inst[i].size(); ++j) inst[i][j].to_bytes(&vals[32 * (n * i + j)]);
+      dev(snarkv_plonk_session_upload(ctx, poly(plan.n_pre), vals.data(), vals.size()), "plonk_session_upload");
+      dev(snarkv_ntt_dev(ctx, poly(plan.n_pre), poly(plan.n_pre), (uint32_t)plan.k, plan.n_inst, SNARKV_NTT_INVERSE, nullptr), "ntt");
+    }
+    // proof.rs:52-108, the prover's side
+    if (pr.transcript_initial_state) {
+      Error e = t.common_scalar(*pr.transcript_initial_state);
+      if (!e.ok()) return e;
+    }
+    for (auto& column : inst)
+      for (auto& x : column) {
+        Error e = t.common_scalar(x);
+        if (!e.ok()) return e;
+      }
+    return Error{};
+  }
+
+  size_t num_phases() const override { return plan.phases; }
+  size_t phase_challenges(size_t ph) const override { return pr.num_challenge[ph]; }
+  size_t phase_witnesses(size_t ph) const override { return pr.num_witness[ph]; }
+  size_t proof_length() const override {
+    const size_t opening = std::is_same<MOS, Gwc19>::value ? n_sets : 2;
+    return kPointBytes * (plan.n_wit + plan.num_chunk + opening) + 32 * pr.evaluations.size();
+  }
+
+  // `count` polynomials of n coefficients at d_first, committed in one batch -> written to the transcript
+  Error commit_and_write(const uint8_t* d_first, size_t count, uint32_t* status_out) {
+    std::vector<const void*> d_s(count), d_p(count, d_srs);
+    std::vector<size_t> ns(count, plan.n);
+    for (size_t i = 0; i < count; ++i) d_s[i] = d_first + 32 * plan.n * i;
+    dev(snarkv_g1_msm_pippenger_many_dev(ctx, count, d_s.data(), d_p.data(), ns.data(), 0, commits()), "g1_msm_pippenger_many");
+    std::vector<uint8_t> out(32 + 64 * count);
+    dev(snarkv_plonk_session_download(ctx, out.data(), status(), out.size()), "plonk_session_download");
+    if (status_out) memcpy(status_out, out.data(), 4);
+    if (status_out && *status_out) return Error{};
+    for (size_t i = 0; i < count; ++i) {
+      Error e = t.write_ec_point(G1Affine::from_bytes(&out[32 + 64 * i]));
+      if (!e.ok()) return e;
+    }
+    return Error{};
+  }
+
+  Result<std::vector<Fr>> phase(const void* d_witness, int form) override {
+    using R = Result<std::vector<Fr>>;
+    const size_t nw = pr.num_witness[next_phase];
+    if (nw) {
+      uint8_t* dst = poly(plan.n_pre + plan.n_inst + witness_done);
+      dev(snarkv_plonk_session_copy(ctx, dst, d_witness, 32 * plan.n * nw), "plonk_session_copy");
+      if (form == kPlonkValues) dev(snarkv_ntt_dev(ctx, dst, dst, (uint32_t)plan.k, nw, SNARKV_NTT_INVERSE, nullptr), "ntt");
+      Error e = commit_and_write(dst, nw, nullptr);
+      if (!e.ok()) return R::Err(e);
+    }
+    witness_done += nw;
+    std::vector<Fr> out = t.squeeze_n_challenges(pr.num_challenge[next_phase]);
+    challenges.insert(challenges.end(), out.begin(), out.end());
+    ++next_phase;
+    return R::Ok(std::move(out));
+  }
+
+  Result<std::vector<uint8_t>> finish() override {
+    using R = Result<std::vector<uint8_t>>;
+    const size_t n = plan.n, N = plan.N;
+    uint8_t* d_h = d_mem + off_h;
+    // 1. the quotient on the extended coset
+    const Fr zeta = plonk_zeta();
+    uint8_t zeta32[32], zeta_inv32[32];
+    zeta.to_bytes(zeta32);
+    zeta.square().to_bytes(zeta_inv32);  // zeta^3 = 1
+    std::vector<uint8_t> consts;
+    try {
+      consts = plan.num.fill(challenges);
+    } catch (const InvalidProtocol& e) {
+      return R::Err(Error{Error::InvalidProtocol, e.what()});
+    }
+    dev(snarkv_quotient_dev(ctx, d_mem, (uint32_t)plan.k, plan.num.e, plan.num.n_cols, plan.num.prog.data(), plan.num.prog.size(),
+                            consts.data(), plan.num.consts.size(), zeta32, zeta_inv32, d_mem + off_work, d_h),
+        "quotient");
+    // 2. its coefficients from num_chunk * n on are zero, or the numerator does not vanish on the domain
+    const uint32_t zero[4] = {0, 0, 0, 0};
+    dev(snarkv_plonk_session_upload(ctx, status(), zero, 16), "plonk_session_upload");
+    dev(snarkv_plonk_tail_check_dev(ctx, d_h + 32 * n * plan.num_chunk, N - n * plan.num_chunk, status()), "plonk_tail_check");
+    // 3. the chunks, committed in one batch; the status word comes with the points
+    uint32_t tail = 0;
+    Error e = commit_and_write(d_h, plan.num_chunk, &tail);
+    if (!e.ok()) return R::Err(e);
+    if (tail) return R::Err(Error::assertion(kPlonkUnsatisfied));
+    const Fr z = t.squeeze_challenge();
+    // 4. every evaluation in one call: the protocol's, the queries' that are not among them, the chunks' at z
+    std::vector<uint8_t> points(32 * rotations.size());
+    for (size_t i = 0; i < rotations.size(); ++i) pr.domain.rotate_scalar(z, rotations[i]).to_bytes(&points[32 * i]);
+    dev(snarkv_plonk_session_upload(ctx, d_mem + off_blk + blk_points, points.data(), points.size()), "plonk_session_upload");
+    auto point_of = [&](int32_t rot) { return (uint32_t)(std::find(rotations.begin(), rotations.end(), rot) - rotations.begin()); };
+    std::vector<uint32_t> q_poly, q_point;
+    for (auto& q : wanted) {
+      q_poly.push_back((uint32_t)q.poly);
+      q_point.push_back(point_of(q.rotation));
+    }
+    const size_t first_chunk = plan.q_index + 1;  // h follows the quotient's slot
+    for (size_t i = 0; i < plan.num_chunk; ++i) {
+      q_poly.push_back((uint32_t)(first_chunk + i));
+      q_point.push_back(point_of(0));
+    }
+    dev(snarkv_poly_eval_many_dev(ctx, poly(0), n, first_chunk + plan.num_chunk, d_mem + off_blk + blk_points, rotations.size(),
+                                  q_poly.data(), q_point.data(), q_poly.size(), d_mem + off_blk + blk_evals),
+        "poly_eval_many");
+    std::vector<uint8_t> raw(32 * q_poly.size());
+    dev(snarkv_plonk_session_download(ctx, raw.data(), d_mem + off_blk + blk_evals, raw.size()), "plonk_session_download");
+    std::map<PQuery, Fr> value;
+    std::vector<Fr> chunk_at_z(plan.num_chunk);
+    for (size_t i = 0; i < q_poly.size(); ++i) {
+      Fr x;
+      if (!Fr::from_bytes(&raw[32 * i], &x)) throw std::runtime_error("poly_eval_many: a non-canonical evaluation");
+      if (i < wanted.size()) value[wanted[i]] = x;
+      else chunk_at_z[i - wanted.size()] = x;
+    }
+    PlonkProof<MOS> proof;  // what the verifier will have read, for its own code below
+    proof.challenges = challenges;
+    proof.z = z;
+    for (auto& q : pr.evaluations) {
+      proof.evaluations.push_back(value.at(q));
+      e = t.write_scalar(proof.evaluations.back());
+      if (!e.ok()) return R::Err(e);
+    }
+    // 5. Q = sum (z^n)^i h_i into the quotient's slot
+    const CommonPolyEval cpe(pr.domain, pr.langranges(), z);
+    const std::vector<Fr> zn_powers = cpe.zn.powers(plan.num_chunk);
+    std::vector<uint32_t> idx(plan.num_chunk);
+    std::vector<uint8_t> scalars(32 * plan.num_chunk);
+    Fr q_at_z = Fr::zero();
+    for (size_t i = 0; i < plan.num_chunk; ++i) {
+      idx[i] = (uint32_t)i;
+      zn_powers[i].to_bytes(&scalars[32 * i]);
+      q_at_z = q_at_z + zn_powers[i] * chunk_at_z[i];
+    }
+    dev(snarkv_poly_lincomb_dev(ctx, d_h, n, plan.num_chunk, idx.data(), scalars.data(), plan.num_chunk, poly(plan.q_index)), "poly_lincomb");
+    // 6. the verifier's identity, with the verifier's code: numerator(z) = Q(z) (z^n - 1)
+    std::map<PQuery, Fr> evals = proof.evaluations_map(pr, instances, cpe);
+    struct V {
+      const PlonkProof<MOS>& proof;
+      const CommonPolyEval& cpe;
+      const std::map<PQuery, Fr>& evals;
+      Fr constant(const Fr& s) { return s; }
+      Fr common_identity() { return cpe.identity; }
+      Fr common_lagrange(int32_t i) { return cpe.get_lagrange(i); }
+      Fr poly(const PQuery& q) {
+        auto it = evals.find(q);
+        if (it == evals.end()) throw InvalidProtocol("Missing query");
+        return it->second;
+      }
+      Fr challenge(size_t i) {
+        if (i >= proof.challenges.size()) throw InvalidProtocol("Missing challenge");
+        return proof.challenges[i];
+      }
+      Fr negated(const Fr& a) { return -a; }
+      Fr sum(const Fr& a, const Fr& b) { return a + b; }
+      Fr product(const Fr& a, const Fr& b) { return a * b; }
+      Fr scaled(const Fr& a, const Fr& s) { return a * s; }
+    } v{proof, cpe, evals};
+    Fr numerator;
+    try {
+      numerator = expr_evaluate<Fr>(*pr.quotient.numerator, v);
+    } catch (const InvalidProtocol& ex) {
+      return R::Err(Error{Error::InvalidProtocol, ex.what()});
+    }
+    if (numerator != q_at_z * cpe.zn_minus_one) return R::Err(Error::assertion(kPlonkUnsatisfied));
+    // 7. the opening
+    std::vector<Query<Fr>> queries;
+    for (auto& q : pr.queries)
+      queries.push_back(Query<Fr>{q.poly, pr.domain.rotate_scalar(Fr::one(), q.rotation), q.poly == plan.q_index ? q_at_z : value.at(q)});
+    const KzgOpenInput in{ctx, d_srs, poly(0), n, plan.q_index + 1};
+    auto opened = MOS::create_proof(in, z, queries, t);
+    if (!opened.ok()) return R::Err(opened.err);
+    // 8. the bytes
+    return R::Ok(t.stream());
+  }
+};
+
+}  // namespace snarkv_host

@@ -958,3 +958,36 @@ extern "C" int hd_kzg_open_roundtrip(int mos, int tkind, snarkv_ctx* ctx, const 
     return KzgAs<Gwc19>::decide(dk, *acc.value).ok() ? 1 : 0;
   });
 }
+
+// ---- the numerator compiler of the PLONK prover (plonk_compile.hpp) -----------------------------------------------------------
+// `whole` = 0: compile_numerator alone; 1: plan_prover, with the protocol-level refusals.  info[0..9] = e, degree, n_cols,
+// n_instr, n_consts, l0_col + 1, x_col + 1 (0: none), first_poly, n_slots, registers used; prog_out = the packed
+// snarkv_quot_instr, consts_out = the table with the challenge entries zero, slots_out = n_slots pairs (entry, challenge).
+// Returns 1; -12 for InvalidProtocol with the message in err_out; -6 when a buffer is too small.
+#include "plonk_compile.hpp"
+extern "C" int hd_plonk_compile(const uint8_t* protocol, size_t plen, int whole, uint32_t* info, uint8_t* prog_out, size_t prog_cap,
+                                uint8_t* consts_out, size_t consts_cap, uint32_t* slots_out, size_t slots_cap, char* err_out,
+                                size_t err_cap) {
+  return guarded([&] {
+    PlonkProtocol pr = parse_protocol(protocol, plen);
+    NumeratorProgram np;
+    try {
+      np = whole ? plan_prover(pr).num : compile_numerator(pr);
+    } catch (const InvalidProtocol& e) {
+      if (err_out && err_cap) snprintf(err_out, err_cap, "%s", e.what());
+      return -12;
+    }
+    const uint32_t head[10] = {np.e, (uint32_t)np.degree, (uint32_t)np.n_cols, (uint32_t)np.prog.size(), (uint32_t)np.consts.size(),
+                               (uint32_t)(np.l0_col + 1), (uint32_t)(np.x_col + 1), (uint32_t)np.first_poly, (uint32_t)np.slots.size(),
+                               (uint32_t)np.regs};
+    memcpy(info, head, sizeof(head));
+    if (16 * np.prog.size() > prog_cap || 32 * np.consts.size() > consts_cap || 2 * np.slots.size() > slots_cap) return -6;
+    memcpy(prog_out, np.prog.data(), 16 * np.prog.size());
+    for (size_t i = 0; i < np.consts.size(); ++i) np.consts[i].to_bytes(consts_out + 32 * i);
+    for (size_t i = 0; i < np.slots.size(); ++i) {
+      slots_out[2 * i] = (uint32_t)np.slots[i].first;
+      slots_out[2 * i + 1] = (uint32_t)np.slots[i].second;
+    }
+    return 1;
+  });
+}
