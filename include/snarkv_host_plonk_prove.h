@@ -34,7 +34,9 @@
  *                                  for a phase without witnesses.  They are committed in one batch over the SRS and the points
  *                                  written; the phase's challenges are squeezed and returned (32 bytes each) for the caller to
  *                                  build the next phase.  *n_challenges is always set; a `cap` below it is
- *                                  SNARKV_HOST_ERR_CAPACITY before any work.  One synchronisation.
+ *                                  SNARKV_HOST_ERR_CAPACITY before any work.  One synchronisation.  A witness polynomial that is
+ *                                  zero commits to the identity, which the transcript refuses as the reference's does:
+ *                                  SNARKV_HOST_ERR_TRANSCRIPT, no challenge is written and the session has ended.
  * snarkv_host_plonk_prover_finish  after the last phase: quotient, chunk commitments, z, evaluations, the opening.  Returns 1
  *                                  with the proof (what `PlonkProof::read` reads) in proof_out.  *proof_len is always set; a
  *                                  proof_cap below the proof's length is SNARKV_HOST_ERR_CAPACITY with the needed length in
@@ -42,7 +44,16 @@
  *                                  quotient has coefficients from num_chunk * n on, or numerator(z) != Q(z) (z^n - 1) with the
  *                                  verifier's own evaluation -- returns 0 with "the witness does not satisfy the protocol's
  *                                  constraints" and *proof_len = 0; no proof byte is written.  Three synchronisations with
- *                                  Gwc19, four with Bdfg21.
+ *                                  Gwc19, four with Bdfg21.  The verdict on the tail comes before the chunks are written.
+ *                                  Without a tail, a chunk of h that is zero commits to the identity:
+ *                                  SNARKV_HOST_ERR_TRANSCRIPT.  That is every good witness of a protocol with
+ *                                  num_chunk * 2^k = 2^(k+e): h has fewer coefficients than that, so the top chunk is zero and
+ *                                  such a protocol never yields a proof; a bad witness of it has no tail to show and is
+ *                                  refused by the identity at z alone.  A numerator that names a (polynomial, rotation)
+ *                                  which is neither an instance polynomial nor among the protocol's evaluations is found
+ *                                  where the verifier finds it, in the identity at z after all the device work:
+ *                                  SNARKV_HOST_ERR_INVALID_PROTOCOL, "Missing query".  *proof_len = 0 and no proof byte is
+ *                                  written in all of these, and the session has ended.
  * snarkv_host_plonk_prover_destroy frees the session and its device memory (waits for the context's stream); null is ignored.
  *
  * A null argument, an unknown mos / transcript / form, a call out of order (a phase after the last, finish before it, anything

@@ -44,71 +44,7 @@ def host_dk():
     key.close()
 
 
-def to_dev(raw):
-    import torch
-
-    t = torch.frombuffer(bytearray(raw), dtype=torch.uint8).cuda()
-    assert t.data_ptr() % 16 == 0
-    return t
-
-
-def pack_cols(cols):
-    return b"".join(PU.U.pack(c) for c in cols)
-
-
-class Setup:
-    """a circuit's protocol handle, SRS and preprocessed polynomials on the device"""
-
-    def __init__(self, circuit):
-        import torch
-
-        from snark_verifier_amd import host_api as H
-
-        self.circuit = circuit
-        self.protocol = H.Protocol(S.pack_protocol(circuit.protocol))
-        self.d_srs = to_dev(PU.srs_bytes(circuit.n))
-        self.d_pre = to_dev(pack_cols(circuit.pre_coeffs))
-        torch.cuda.synchronize()
-
-    def session(self, HP, ctx, mos, transcript):
-        return HP.PlonkProver(self.protocol, ctx, self.d_srs, self.d_pre, self.circuit.instances, PU.MOS_ID[mos], PU.TRANSCRIPT_ID[transcript])
-
-
-def prove(HP, ctx, setup, mos, transcript, form, phase_columns=None):
-    """the whole session -> proof bytes or None.  phase_columns(phase, challenges) -> a device buffer of the phase's columns"""
-    import torch
-
-    c = setup.circuit
-    given = []
-    with setup.session(HP, ctx, mos, transcript) as p:
-        challenges = []
-        for ph, nw in enumerate(c.protocol["num_witness"]):
-            d = None
-            if nw and phase_columns is not None:
-                d = phase_columns(ph, list(challenges))
-            elif nw:
-                d = to_dev(pack_cols((c.phase_values if form == HP.FORM_VALUES else c.phase_coeffs)(ph, list(challenges))))
-            if d is not None:
-                given.append((d, d.cpu().numpy().tobytes()))
-            torch.cuda.synchronize()
-            challenges += p.phase(d, form)
-        proof = p.finish()
-    torch.cuda.synchronize()
-    assert all(d.cpu().numpy().tobytes() == raw for d, raw in given)  # the caller's memory is not written
-    return proof
-
-
-def check_three_ways(host_dk, setup, proof, mos, transcript):
-    from snark_verifier_amd import host_api as H
-
-    c = setup.circuit
-    want, _ = PU.model_proof(c, mos, transcript)
-    assert proof == want
-    assert PU.oracle_accepts(c.protocol, c.instances, proof, mos, transcript)
-    inst = S.pack_instances(c.instances)
-    assert H.plonk_verify(setup.protocol, host_dk, inst, H.pack_proofs([proof]), 1, PU.MOS_ID[mos], PU.TRANSCRIPT_ID[transcript])
-    return inst
-
+Setup, prove, check_three_ways, to_dev, pack_cols = PU.Setup, PU.prove, PU.check_three_ways, PU.to_dev, PU.pack_cols
 
 _SETUPS = {}
 
