@@ -23,7 +23,7 @@ FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
 
 # the public headers the device units include (include/; the host mirror's are in _host_stale)
 DEVICE_HEADERS = ("amd", "pallas", "pallas_decompress", "ipa_prover", "ipa_batch", "ipa_fold", "ipa_create", "poly", "ipa_multiopen",
-                  "ntt", "poly_prod", "quotient", "lookup", "poly_batch", "kzg_multiopen", "plonk_prove")
+                  "ntt", "poly_prod", "quotient", "quotient_cosets", "lookup", "poly_batch", "kzg_multiopen", "plonk_prove")
 
 
 def _deps():
@@ -104,8 +104,9 @@ def devtest_sources():
 #   lookup     the comparison, merge path, tiled sort and permute rule (csrc/lookup.h)
 #   args       the entry points' shared argument checks (csrc/poly_args.hpp)
 #   kzg_open   the host-side plan of the KZG multi-open provers (csrc/kzg_multiopen_plan.h)
+#   quotient_cosets  the join of the coset-at-a-time quotient, tile by tile (csrc/quotient.h)
 HOSTTEST_DIR = os.path.join(HERE, "..", "tests", "hosttest")
-HOSTTESTS = ("curve", "poly", "ntt", "poly_prod", "quotient", "lookup", "args", "kzg_open")
+HOSTTESTS = ("curve", "poly", "ntt", "poly_prod", "quotient", "lookup", "args", "kzg_open", "quotient_cosets")
 HOSTTEST_EXCEPTIONS = {"curve": ("libhosttest_%s.so", ("curve_ops.h",))}  # the others: libhosttest_<name>_<curve>.so, one source
 
 
@@ -164,7 +165,8 @@ def _host_stale(out, dev_lib):
     srcs = [os.path.join(HOST, f) for f in os.listdir(HOST)] + [os.path.join(inc, h) for h in (
         "snarkv_host.h", "snarkv_host_pallas.h", "snarkv_pallas_decompress.h", "snarkv_host_pallas_fold.h", "snarkv_ipa_fold.h",
         "snarkv_host_pallas_prove.h", "snarkv_ipa_create.h", "snarkv_kzg_multiopen.h", "snarkv_host_kzg_open.h",
-        "snarkv_host_plonk_prove.h", "snarkv_plonk_prove.h", "snarkv_quotient.h", "snarkv_ntt.h", "snarkv_poly.h", "snarkv_poly_batch.h")]
+        "snarkv_host_plonk_prove.h", "snarkv_host_plonk_prove_opts.h", "snarkv_plonk_prove.h", "snarkv_quotient.h",
+        "snarkv_quotient_cosets.h", "snarkv_ntt.h", "snarkv_poly.h", "snarkv_poly_batch.h")]
     newest = max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(dev_lib)])
     return not os.path.exists(out) or os.path.getmtime(out) < newest
 

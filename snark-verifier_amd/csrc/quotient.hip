@@ -7,6 +7,14 @@
 //                  read at a rotation is consecutive across the lanes, the wrap is in the index (quot_row)
 //   k_quot_table   the 2^e values of the vanishing polynomial on the coset, canonical words, for the batch inversion
 //   k_quot_div     out[i] = in[i] table[i mod 2^e]
+// and the coset-at-a-time route (include/snarkv_quotient_cosets.h): the same program on one coset of the small domain after
+// the other, over a work buffer of n_cols * n elements, and
+//   k_quot_join_tables  the tables of powers the join reads, into the slot's program and constant regions, which the stream has
+//                       done with by then
+//   k_quot_join    one workgroup per tile of consecutive t by all 2^e cosets (1024 Fr29, 36 KiB of LDS): load times W^(-j t)
+//                  and the inverted vanishing entry, e radix-2 levels across the cosets with a barrier each, store times
+//                  s^-T 2^-e.  A tile reads and writes the same 2^e rows of t, so in place is safe.  Consecutive lanes take
+//                  consecutive t of one coset.  The arithmetic is quotient.h's.
 //
 // The register file.  16 registers of 9 limbs are indexed by the instruction, at run time, so they cannot live in VGPRs.
 // They are in private memory: `Fr29 regs[16]`, 576 bytes per lane, which the compiler lays out dword-interleaved over the
@@ -23,6 +31,7 @@
 #include "quotient.h"
 #include "../../include/snarkv_ntt.h"
 #include "../../include/snarkv_quotient.h"
+#include "../../include/snarkv_quotient_cosets.h"
 
 namespace snarkv {
 
@@ -37,6 +46,7 @@ enum : size_t {
   QS_END = QS_TABLE + 32 * ((size_t)1 << SNARKV_QUOT_MAX_E),
 };
 static_assert(sizeof(snarkv_quot_instr) == 16, "the instruction format of the header");
+static_assert(sizeof(Fr29) * JT_END <= QS_TABLE, "the join's tables lie in front of the vanishing table");
 
 struct QuotColsDev {
   const uint32_t* __restrict__ p;
@@ -81,6 +91,42 @@ __global__ void __launch_bounds__(kQuotThreads) k_quot_div(const uint32_t* in, u
   const uint32_t i = blockIdx.x * kQuotThreads + threadIdx.x;
   if (i >> log_n) return;
   st_fr(out + 8 * (size_t)i, fr29_mul(ld_fr(in + 8 * (size_t)i), ld_fr(table + 8 * (size_t)(i & mask))));
+}
+
+__global__ void __launch_bounds__(kQuotThreads) k_quot_join_tables(Fr29 w_inv, Fr29 s_inv, Fr29 om_inv, uint32_t e,
+                                                                   const uint32_t* __restrict__ inv_words, Fr29* __restrict__ out) {
+  const uint32_t idx = blockIdx.x * kQuotThreads + threadIdx.x;
+  if (idx < JT_END) out[idx] = quot_join_table_entry(idx, w_inv, s_inv, om_inv, e, inv_words);
+}
+
+// in[j][t] -> out[t + q n]; `in` may be `out`.  The grid's x is the tile: n >> tile_bits of them.
+__global__ void __launch_bounds__(kQuotThreads) k_quot_join(const uint32_t* in, uint32_t k, uint32_t e, uint32_t tile_bits,
+                                                            const Fr29* __restrict__ tab, uint32_t* out) {
+  __shared__ Fr29 buf[1u << kQuotJoinTileBits];
+  const uint32_t lane = threadIdx.x, t0 = blockIdx.x << tile_bits, slots = 1u << (tile_bits + e);
+#pragma unroll 1
+  for (uint32_t slot = lane; slot < slots; slot += kQuotThreads) {
+    const uint4* src = reinterpret_cast<const uint4*>(in + 8 * quot_join_in_index(slot, t0, k, tile_bits));
+    const uint4 a = src[0], b = src[1];
+    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    buf[quot_join_in_slot(slot, e, tile_bits)] = quot_join_in(w, tab, slot, t0, k, e, tile_bits);
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t level = 0; level < e; ++level) {
+#pragma unroll 1
+    for (uint32_t b = lane; b < slots / 2; b += kQuotThreads) quot_join_butterfly(buf, tab, b, level, e, tile_bits);
+    __syncthreads();
+  }
+#pragma unroll 1
+  for (uint32_t slot = lane; slot < slots; slot += kQuotThreads) {
+    const size_t T = quot_join_out_index(slot, t0, k, tile_bits);
+    uint32_t w[8];
+    quot_join_out(buf[slot], tab, (uint32_t)T, k, e, w);
+    uint4* dst = reinterpret_cast<uint4*>(out + 8 * T);
+    dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+  }
 }
 
 namespace {
@@ -167,8 +213,8 @@ int quot_enqueue_extend(snarkv_ctx* ctx, const void* d_coeffs, uint32_t k, uint3
   return SNARKV_OK;
 }
 
-int quot_enqueue_eval(snarkv_ctx* ctx, const void* d_cols, uint32_t k, uint32_t e, const snarkv_quot_instr* prog, size_t n_instr,
-                      const uint8_t* consts32, size_t n_consts, void* d_out) {
+// the program and the constants into the slot
+int quot_stage_program(snarkv_ctx* ctx, const snarkv_quot_instr* prog, size_t n_instr, const uint8_t* consts32, size_t n_consts) {
   uint8_t* scr;
   SNARKV_TRY(slot_of(ctx, &scr));
   std::vector<Fr29> consts(n_consts);
@@ -181,7 +227,13 @@ int quot_enqueue_eval(snarkv_ctx* ctx, const void* d_cols, uint32_t k, uint32_t 
   SNARKV_HIP(hipMemcpyAsync(scr + QS_PROG, prog, sizeof(snarkv_quot_instr) * n_instr, hipMemcpyHostToDevice, ctx->stream));
   if (n_consts)
     SNARKV_HIP(hipMemcpyAsync(scr + QS_CONSTS, consts.data(), sizeof(Fr29) * n_consts, hipMemcpyHostToDevice, ctx->stream));
-  const uint32_t log_n = k + e;
+  return SNARKV_OK;
+}
+
+// the staged program over n_cols columns of 2^log_n values; a rotation is rot 2^e rows
+int quot_launch_eval(snarkv_ctx* ctx, const void* d_cols, uint32_t log_n, uint32_t e, size_t n_instr, void* d_out) {
+  uint8_t* scr;
+  SNARKV_TRY(slot_of(ctx, &scr));
   hipLaunchKernelGGL(k_quot_eval, dim3(blocks_of(log_n)), dim3(kQuotThreads), 0, ctx->stream, (const uint32_t*)d_cols, log_n, e,
                      (const snarkv_quot_instr*)(scr + QS_PROG), (uint32_t)n_instr, (const Fr29*)(scr + QS_CONSTS),
                      (uint32_t*)d_out);
@@ -189,17 +241,53 @@ int quot_enqueue_eval(snarkv_ctx* ctx, const void* d_cols, uint32_t k, uint32_t 
   return SNARKV_OK;
 }
 
-int quot_enqueue_div(snarkv_ctx* ctx, const void* d_in, uint32_t k, uint32_t e, const uint32_t* shift, void* d_out) {
+int quot_enqueue_eval(snarkv_ctx* ctx, const void* d_cols, uint32_t k, uint32_t e, const snarkv_quot_instr* prog, size_t n_instr,
+                      const uint8_t* consts32, size_t n_consts, void* d_out) {
+  SNARKV_TRY(quot_stage_program(ctx, prog, n_instr, consts32, n_consts));
+  return quot_launch_eval(ctx, d_cols, k + e, e, n_instr, d_out);
+}
+
+// the 2^e inverted values of the vanishing polynomial into the slot's table: canonical words
+int quot_enqueue_table(snarkv_ctx* ctx, uint32_t k, uint32_t e, const uint32_t* shift, uint32_t** table_out) {
   uint8_t* scr;
   SNARKV_TRY(slot_of(ctx, &scr));
   uint32_t* table = (uint32_t*)(scr + QS_TABLE);
-  const uint32_t entries = 1u << e, log_n = k + e;
+  const uint32_t entries = 1u << e;
   hipLaunchKernelGGL(k_quot_table, dim3((entries + kQuotThreads - 1) / kQuotThreads), dim3(kQuotThreads), 0, ctx->stream,
                      quot_shift_to_n(fr29_from_canonical(shift), k), quot_coset_root(e), entries, table);
   SNARKV_HIP(hipGetLastError());
   SNARKV_TRY(prod_batch_invert_enqueue(ctx, table, entries, table));  // the one field inversion of the call
+  *table_out = table;
+  return SNARKV_OK;
+}
+
+int quot_enqueue_div(snarkv_ctx* ctx, const void* d_in, uint32_t k, uint32_t e, const uint32_t* shift, void* d_out) {
+  uint32_t* table;
+  SNARKV_TRY(quot_enqueue_table(ctx, k, e, shift, &table));
+  const uint32_t entries = 1u << e, log_n = k + e;
   hipLaunchKernelGGL(k_quot_div, dim3(blocks_of(log_n)), dim3(kQuotThreads), 0, ctx->stream, (const uint32_t*)d_in, log_n,
                      (const uint32_t*)table, entries - 1u, (uint32_t*)d_out);
+  SNARKV_HIP(hipGetLastError());
+  return SNARKV_OK;
+}
+
+// The way back from the 2^e cosets (quotient.h): every coset's values to coefficients by one inverse transform of size k
+// over all of them, d_vals -> d_out, then the join over d_out in place.  Its tables go into the slot's program and constant
+// regions: whatever kernel read a program there is ahead on the stream.  d_inv: the 2^e canonical factors g_j on the device,
+// or null for one.
+int quot_enqueue_join(snarkv_ctx* ctx, const void* d_vals, uint32_t k, uint32_t e, const uint32_t* shift_inv, const uint32_t* d_inv,
+                      void* d_out) {
+  SNARKV_TRY(ntt_enqueue(ctx, d_vals, d_out, k, (size_t)1 << e, true, nullptr));
+  uint8_t* scr;
+  SNARKV_TRY(slot_of(ctx, &scr));
+  Fr29* tab = (Fr29*)(scr + QS_PROG);
+  hipLaunchKernelGGL(k_quot_join_tables, dim3((JT_END + kQuotThreads - 1) / kQuotThreads), dim3(kQuotThreads), 0, ctx->stream,
+                     ntt_root_squared(true, SNARKV_FR_TWO_ADICITY - (k + e)), fr29_from_canonical(shift_inv),
+                     ntt_root_squared(true, SNARKV_FR_TWO_ADICITY - e), e, d_inv, tab);
+  SNARKV_HIP(hipGetLastError());
+  const uint32_t tile_bits = quot_join_tile_bits(k, e);
+  hipLaunchKernelGGL(k_quot_join, dim3(1u << (k - tile_bits)), dim3(kQuotThreads), 0, ctx->stream, (const uint32_t*)d_out, k, e,
+                     tile_bits, (const Fr29*)tab, (uint32_t*)d_out);
   SNARKV_HIP(hipGetLastError());
   return SNARKV_OK;
 }
@@ -278,6 +366,58 @@ int SNARKV_API(quotient_dev)(snarkv_ctx* ctx, const void* d_coeffs32, uint32_t k
   SNARKV_TRY(quot_enqueue_eval(ctx, d_work32, k, e, prog, n_instr, consts32, n_consts, d_h32));
   SNARKV_TRY(quot_enqueue_div(ctx, d_h32, k, e, shift, d_h32));
   return ntt_enqueue(ctx, d_h32, d_h32, k + e, 1, true, shift_inv);
+}
+
+int SNARKV_API(poly_cosets_join_dev)(snarkv_ctx* ctx, const void* d_vals32, uint32_t k, uint32_t e, const uint8_t* shift_inv32,
+                                     void* d_out32) {
+  if (!ctx || !aligned16(d_vals32) || !aligned16(d_out32) || bad_shift("poly_cosets_join", shift_inv32)) return SNARKV_ERR_ARG;
+  if (partial_overlap(d_out32, d_vals32, ext_bytes(k, e, 1)))
+    return refuse_overlap("poly_cosets_join", "out is the input itself or disjoint from it");
+  if (!below_r(shift_inv32)) return SNARKV_ERR_ENCODING;
+  SNARKV_TRY(check_shape(k, e));
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  uint32_t shift_inv[8];
+  memcpy(shift_inv, shift_inv32, 32);
+  return quot_enqueue_join(ctx, d_vals32, k, e, shift_inv, nullptr, d_out32);
+}
+
+int SNARKV_API(quotient_cosets_dev)(snarkv_ctx* ctx, const void* d_coeffs32, uint32_t k, uint32_t e, size_t n_cols,
+                                    const snarkv_quot_instr* prog, size_t n_instr, const uint8_t* consts32, size_t n_consts,
+                                    const uint8_t* shift32, const uint8_t* shift_inv32, void* d_work32, void* d_h32) {
+  if (!ctx || !aligned16(d_coeffs32) || !aligned16(d_work32) || !aligned16(d_h32) || !prog || (n_consts && !consts32))
+    return SNARKV_ERR_ARG;
+  if (bad_shift("quotient_cosets", shift32) || bad_shift("quotient_cosets", shift_inv32)) return SNARKV_ERR_ARG;
+  SNARKV_TRY(check_program("quotient_cosets", prog, n_instr, n_consts, n_cols));
+  const size_t coeffs = ext_bytes(k, 0, n_cols), work = coeffs, h = ext_bytes(k, e, 1);  // work is one coset of every column
+  if (overlap(d_work32, work, d_coeffs32, coeffs) || overlap(d_h32, h, d_coeffs32, coeffs) || overlap(d_h32, h, d_work32, work))
+    return refuse_overlap("quotient_cosets", "work, h and the coefficients are pairwise disjoint");
+  if (!all_below_r(consts32, n_consts) || !below_r(shift32) || !below_r(shift_inv32)) return SNARKV_ERR_ENCODING;
+  if (n_cols == 0 || n_instr == 0) return SNARKV_ERR_EMPTY;
+  SNARKV_TRY(check_shape(k, e));
+  SNARKV_TRY(check_program_lengths(n_cols, n_instr, n_consts));
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  uint32_t shift[8], shift_inv[8];
+  memcpy(shift, shift32, 32);
+  memcpy(shift_inv, shift_inv32, 32);
+  // once: the program, the inverted vanishing table
+  SNARKV_TRY(quot_stage_program(ctx, prog, n_instr, consts32, n_consts));
+  uint32_t* table;
+  SNARKV_TRY(quot_enqueue_table(ctx, k, e, shift, &table));
+  // per coset j: the columns on (s W^j) H by one size-k transform each, the program there with a rotation of one row
+  const Fr29 root = ntt_root_squared(false, SNARKV_FR_TWO_ADICITY - (k + e));  // W
+  Fr29 coset_shift = fr29_from_canonical(shift);                               // s W^j: products only
+  for (uint32_t j = 0; !(j >> e); ++j) {
+    uint32_t sj[8];
+    fr29_to_canonical(coset_shift, sj);
+    for (size_t p0 = 0; p0 < n_cols; p0 += kQuotMaxCount) {  // the transform takes 65 535 polynomials per call
+      const size_t c = n_cols - p0 < kQuotMaxCount ? n_cols - p0 : kQuotMaxCount;
+      SNARKV_TRY(ntt_enqueue(ctx, (const uint8_t*)d_coeffs32 + ((p0 * 32) << k), (uint8_t*)d_work32 + ((p0 * 32) << k), k, c, false, sj));
+    }
+    SNARKV_TRY(quot_launch_eval(ctx, d_work32, k, 0, n_instr, (uint8_t*)d_h32 + (((size_t)j * 32) << k)));
+    coset_shift = fr29_mul(coset_shift, root);
+  }
+  // back: every coset's values to coefficients in one call and the join across the cosets, with the division in it
+  return quot_enqueue_join(ctx, d_h32, k, e, shift_inv, table, d_h32);
 }
 
 }  // extern "C"

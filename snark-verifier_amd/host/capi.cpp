@@ -4,6 +4,7 @@
 #include "../../include/snarkv_host.h"
 #include "../../include/snarkv_host_kzg_open.h"
 #include "../../include/snarkv_host_plonk_prove.h"
+#include "../../include/snarkv_host_plonk_prove_opts.h"
 
 #include <cstdio>
 #include <cstring>
@@ -626,9 +627,9 @@ struct snarkv_host_plonk_prover {
 namespace {
 template <class MOS, class TR>
 int plonk_prover_begin_tr(const PlonkProtocol& pr, snarkv_ctx* ctx, const void* d_srs, const void* d_pre,
-                          const std::vector<std::vector<Fr>>& inst, snarkv_host_plonk_prover** out) {
+                          const std::vector<std::vector<Fr>>& inst, uint32_t flags, snarkv_host_plonk_prover** out) {
   auto s = std::make_unique<PlonkProver<MOS, TR>>();
-  const Error e = s->begin(pr, ctx, d_srs, d_pre, inst);
+  const Error e = s->begin(pr, ctx, d_srs, d_pre, inst, flags);
   if (!e.ok()) return e.kind == Error::AssertionFailure ? SNARKV_HOST_ERR_OTHER : error_code(e);
   *out = new snarkv_host_plonk_prover{std::move(s)};
   return 1;
@@ -639,7 +640,13 @@ extern "C" {
 
 int snarkv_host_plonk_prover_plan(const snarkv_host_protocol* protocol, uint32_t* e, size_t* n_cols, size_t* n_instr,
                                   size_t* n_consts, size_t* bytes) {
+  return snarkv_host_plonk_prover_plan_opts(protocol, 0, e, n_cols, n_instr, n_consts, bytes);
+}
+
+int snarkv_host_plonk_prover_plan_opts(const snarkv_host_protocol* protocol, uint32_t flags, uint32_t* e, size_t* n_cols,
+                                       size_t* n_instr, size_t* n_consts, size_t* bytes) {
   if (!protocol) return arg_error("null argument");
+  if (flags & ~kPlonkKnownFlags) return arg_error("unknown flag bit");
   return guarded([&] {
     try {
       const ProverPlan plan = plan_prover(protocol->pr, snarkv_ntt_max_k());
@@ -647,7 +654,7 @@ int snarkv_host_plonk_prover_plan(const snarkv_host_protocol* protocol, uint32_t
       if (n_cols) *n_cols = plan.num.n_cols;
       if (n_instr) *n_instr = plan.num.prog.size();
       if (n_consts) *n_consts = plan.num.consts.size();
-      if (bytes) *bytes = plan.device_bytes;
+      if (bytes) *bytes = plan.device_bytes_of(flags & kPlonkQuotientCosets);
       return 1;
     } catch (const InvalidProtocol& ex) {
       return error_code(Error{Error::InvalidProtocol, ex.what()});
@@ -658,6 +665,13 @@ int snarkv_host_plonk_prover_plan(const snarkv_host_protocol* protocol, uint32_t
 int snarkv_host_plonk_prover_begin(const snarkv_host_protocol* protocol, int mos, int transcript, snarkv_ctx* ctx,
                                    const void* d_srs64, const void* d_preprocessed32, const uint8_t* instances,
                                    size_t instances_len, snarkv_host_plonk_prover** out) {
+  return snarkv_host_plonk_prover_begin_opts(protocol, mos, transcript, 0, ctx, d_srs64, d_preprocessed32, instances, instances_len,
+                                             out);
+}
+
+int snarkv_host_plonk_prover_begin_opts(const snarkv_host_protocol* protocol, int mos, int transcript, uint32_t flags,
+                                        snarkv_ctx* ctx, const void* d_srs64, const void* d_preprocessed32,
+                                        const uint8_t* instances, size_t instances_len, snarkv_host_plonk_prover** out) {
   if (!out) return arg_error("null argument");
   *out = nullptr;
   if (!protocol || !ctx || !d_srs64 || !instances || (!d_preprocessed32 && !protocol->pr.preprocessed.empty()))
@@ -666,15 +680,16 @@ int snarkv_host_plonk_prover_begin(const snarkv_host_protocol* protocol, int mos
   if (transcript != SNARKV_HOST_TRANSCRIPT_EVM && transcript != SNARKV_HOST_TRANSCRIPT_POSEIDON)
     return arg_error("unknown transcript kind: the prover writes the host's EVM or Poseidon transcript");
   if ((uintptr_t)d_srs64 % 16 || (uintptr_t)d_preprocessed32 % 16) return arg_error("a device address is not 16-byte aligned");
+  if (flags & ~kPlonkKnownFlags) return arg_error("unknown flag bit");
   return guarded([&] {
     if (snarkv_ctx_get_flags(ctx) & SNARKV_FLAG_MONTGOMERY) return arg_error("the context's default form is Montgomery: the prover speaks the wire form");
     const std::vector<std::vector<Fr>> inst = wire::parse_instances(instances, instances_len);
     const PlonkProtocol& pr = protocol->pr;
     const bool gwc = mos == SNARKV_HOST_MOS_GWC19, evm = transcript == SNARKV_HOST_TRANSCRIPT_EVM;
-    return gwc ? (evm ? plonk_prover_begin_tr<Gwc19, EvmTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, out)
-                      : plonk_prover_begin_tr<Gwc19, PoseidonTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, out))
-               : (evm ? plonk_prover_begin_tr<Bdfg21, EvmTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, out)
-                      : plonk_prover_begin_tr<Bdfg21, PoseidonTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, out));
+    return gwc ? (evm ? plonk_prover_begin_tr<Gwc19, EvmTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, flags, out)
+                      : plonk_prover_begin_tr<Gwc19, PoseidonTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, flags, out))
+               : (evm ? plonk_prover_begin_tr<Bdfg21, EvmTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, flags, out)
+                      : plonk_prover_begin_tr<Bdfg21, PoseidonTranscript>(pr, ctx, d_srs64, d_preprocessed32, inst, flags, out));
   });
 }
 

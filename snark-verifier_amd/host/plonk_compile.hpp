@@ -295,6 +295,10 @@ struct ProverPlan {
   size_t k = 0, n = 0, N = 0;
   size_t device_bytes = 0;  // the columns, the quotient's work buffer and h
   size_t cols_total() const { return num.first_poly + q_index + 1; }  // extra | protocol order | the quotient's slot
+  // the quotient's work buffer in elements: every column on the extended coset, or on one coset of the domain at a time
+  // (snarkv_quotient_cosets.h)
+  size_t work_elems(bool by_cosets) const { return num.n_cols * (by_cosets ? n : N); }
+  size_t device_bytes_of(bool by_cosets) const { return device_bytes - 32 * (work_elems(false) - work_elems(by_cosets)); }
 };
 
 inline ProverPlan plan_prover(const PlonkProtocol& pr, uint32_t max_k = 28) {

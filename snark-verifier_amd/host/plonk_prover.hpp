@@ -5,6 +5,8 @@
 //
 // A session:
 //   begin    one resident buffer:  [l_0] [X] | preprocessed | instance | witness | quotient slot | h | work | small block
+//            (work is n_cols * N elements; n_cols * n in a session begun with kPlonkQuotientCosets, whose finish takes the
+//            quotient one coset at a time: snarkv_quotient_cosets_dev, the same bytes.)
 //            The quotient (snarkv_quotient_dev) reads the columns from the extra ones up to the last witness, contiguous; the
 //            opening reads from `preprocessed` on and finds the quotient at index n_pre + n_inst + n_wit.  The instance
 //            polynomials are built (values in rows 0.., inverse transform); the transcript absorbs the initial state and
@@ -23,6 +25,7 @@
 #include "../../include/snarkv_poly.h"
 #include "../../include/snarkv_poly_batch.h"
 #include "../../include/snarkv_quotient.h"
+#include "../../include/snarkv_quotient_cosets.h"
 #include "plonk.hpp"
 #include "plonk_compile.hpp"
 #include "transcript.hpp"
@@ -31,6 +34,8 @@ namespace snarkv_host {
 
 constexpr const char* kPlonkUnsatisfied = "the witness does not satisfy the protocol's constraints";
 enum PlonkWitnessForm { kPlonkCoeffs = 0, kPlonkValues = 1 };
+constexpr uint32_t kPlonkQuotientCosets = 1u;  // SNARKV_HOST_PLONK_QUOTIENT_COSETS
+constexpr uint32_t kPlonkKnownFlags = kPlonkQuotientCosets;
 
 // halo2's ZETA: a primitive cube root of unity, g^((r - 1) / 3) with g = 7 -- the coset shift of the extended domain
 inline Fr plonk_zeta() {
@@ -72,6 +77,7 @@ struct PlonkProver : PlonkProverSession {
   std::vector<Fr> challenges;
   TR t;
   size_t next_phase = 0, witness_done = 0, n_sets = 0;
+  uint32_t flags = 0;  // kPlonk* of begin
   // byte offsets into d_mem
   size_t off_polys = 0, off_h = 0, off_work = 0, off_blk = 0;
   size_t blk_points = 0, blk_evals = 0, blk_bytes = 0;
@@ -94,8 +100,9 @@ struct PlonkProver : PlonkProverSession {
 
   // d_preprocessed: the n_pre polynomials as coefficients, n each, in the protocol's order
   Error begin(const PlonkProtocol& protocol, snarkv_ctx* c, const void* srs, const void* d_preprocessed,
-              const std::vector<std::vector<Fr>>& inst) {
+              const std::vector<std::vector<Fr>>& inst, uint32_t session_flags = 0) {
     pr = protocol;
+    flags = session_flags;
     ctx = c;
     d_srs = srs;
     instances = inst;
@@ -135,7 +142,7 @@ struct PlonkProver : PlonkProverSession {
     off_polys = 32 * n * plan.num.first_poly;
     off_h = 32 * n * plan.cols_total();
     off_work = off_h + 32 * plan.N;
-    off_blk = off_work + 32 * plan.N * plan.num.n_cols;
+    off_blk = off_work + 32 * plan.work_elems(flags & kPlonkQuotientCosets);
     blk_points = 32 + 64 * most;
     blk_evals = blk_points + 32 * rotations.size();
     blk_bytes = blk_evals + 32 * (wanted.size() + plan.num_chunk);
@@ -232,7 +239,7 @@ struct PlonkProver : PlonkProverSession {
     } catch (const InvalidProtocol& e) {
       return R::Err(Error{Error::InvalidProtocol, e.what()});
     }
-    dev(snarkv_quotient_dev(ctx, d_mem, (uint32_t)plan.k, plan.num.e, plan.num.n_cols, plan.num.prog.data(), plan.num.prog.size(),
+    dev((flags & kPlonkQuotientCosets ? snarkv_quotient_cosets_dev : snarkv_quotient_dev)(ctx, d_mem, (uint32_t)plan.k, plan.num.e, plan.num.n_cols, plan.num.prog.data(), plan.num.prog.size(),
                             consts.data(), plan.num.consts.size(), zeta32, zeta_inv32, d_mem + off_work, d_h),
         "quotient");
     // 2. its coefficients from num_chunk * n on are zero, or the numerator does not vanish on the domain

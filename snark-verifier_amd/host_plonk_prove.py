@@ -9,7 +9,10 @@
 
 `plan(protocol)` needs no device: what the protocol compiles to, or the refusal as a `HostError`.
 
-This ctypes table is this module's own: one table per header."""
+`flags=QUOTIENT_COSETS` on `plan` and `PlonkProver` (include/snarkv_host_plonk_prove_opts.h): the session takes the quotient
+one coset of the domain at a time, over a work region 2^e times smaller; the proof bytes are the same.
+
+The ctypes tables are this module's own: one table per header."""
 import ctypes
 
 from . import host_api as H
@@ -22,6 +25,7 @@ MOS_GWC19, MOS_BDFG21 = 0, 1
 TRANSCRIPT_EVM, TRANSCRIPT_POSEIDON = 0, 1
 FORM_COEFFS, FORM_VALUES = 0, 1
 UNSATISFIED = "the witness does not satisfy the protocol's constraints"
+QUOTIENT_COSETS = 1  # SNARKV_HOST_PLONK_QUOTIENT_COSETS
 
 PREFIX = "snarkv_host_plonk_prover_"
 # every function include/snarkv_host_plonk_prove.h declares, without the prefix
@@ -33,7 +37,14 @@ SHAPES = {
     "destroy": (None, [_vp]),
 }
 SIGNATURES = {PREFIX + n: s for n, s in SHAPES.items()}
-_bound = None
+# ... and include/snarkv_host_plonk_prove_opts.h
+_u32 = ctypes.c_uint32
+OPTS_SHAPES = {
+    "plan_opts": (_int, [_vp, _u32, ctypes.POINTER(_u32), _szp, _szp, _szp, _szp]),
+    "begin_opts": (_int, [_vp, _int, _int, _u32, _vp, _vp, _vp, _cp, _sz, ctypes.POINTER(_vp)]),
+}
+OPTS_SIGNATURES = {PREFIX + n: s for n, s in OPTS_SHAPES.items()}
+_bound = _bound_opts = None
 
 
 def api():
@@ -42,6 +53,14 @@ def api():
     if _bound is None:
         _bound = Api(H.load_library(), PREFIX, SHAPES)  # AttributeError if the header and the library drift
     return _bound
+
+
+def opts_api():
+    """the functions of the options header, bound once"""
+    global _bound_opts
+    if _bound_opts is None:
+        _bound_opts = Api(H.load_library(), PREFIX, OPTS_SHAPES)
+    return _bound_opts
 
 
 def _check(rc):
@@ -62,10 +81,12 @@ def pack_instances(instances):
     return out
 
 
-def plan(protocol):
-    """-> {"e", "n_cols", "n_instr", "n_consts", "bytes"}; a protocol the prover refuses raises HostError naming the cause"""
+def plan(protocol, flags=0):
+    """-> {"e", "n_cols", "n_instr", "n_consts", "bytes"}; a protocol the prover refuses raises HostError naming the cause.
+    `bytes` is what a session begun with the same `flags` allocates."""
     e, cols, instr, consts, nbytes = ctypes.c_uint32(0), _sz(0), _sz(0), _sz(0), _sz(0)
-    _check(api().plan(protocol._h, ctypes.byref(e), ctypes.byref(cols), ctypes.byref(instr), ctypes.byref(consts), ctypes.byref(nbytes)))
+    outs = (ctypes.byref(e), ctypes.byref(cols), ctypes.byref(instr), ctypes.byref(consts), ctypes.byref(nbytes))
+    _check(opts_api().plan_opts(protocol._h, flags, *outs) if flags else api().plan(protocol._h, *outs))
     return {"e": e.value, "n_cols": cols.value, "n_instr": instr.value, "n_consts": consts.value, "bytes": nbytes.value}
 
 
@@ -73,11 +94,13 @@ class PlonkProver:
     """A prover session.  `instances`: [[int]] or a packed block.  The SRS (n points) and whatever a phase is given stay the
     caller's; the session keeps its own copy of every polynomial."""
 
-    def __init__(self, protocol, ctx, d_srs, d_preprocessed, instances, mos=MOS_GWC19, transcript=TRANSCRIPT_EVM):
-        self._a = api()
+    def __init__(self, protocol, ctx, d_srs, d_preprocessed, instances, mos=MOS_GWC19, transcript=TRANSCRIPT_EVM, flags=0):
+        self._a, self._h = api(), None
         inst = bytes(instances) if isinstance(instances, (bytes, bytearray)) else pack_instances(instances)
         h = _vp()
-        _check(self._a.begin(protocol._h, mos, transcript, ctx._h, _addr(d_srs), _addr(d_preprocessed), inst, len(inst), ctypes.byref(h)))
+        rest = (ctx._h, _addr(d_srs), _addr(d_preprocessed), inst, len(inst), ctypes.byref(h))
+        _check(opts_api().begin_opts(protocol._h, mos, transcript, flags, *rest) if flags
+               else self._a.begin(protocol._h, mos, transcript, *rest))
         self._h, self._keep = h, (protocol, ctx, d_srs)
 
     def phase(self, d_witness, form=FORM_COEFFS):

@@ -1,13 +1,14 @@
 """The quotient polynomial on the extended coset (include/snarkv_quotient.h), over a BN254 `Context` or a pallas
 `PallasContext`: coefficient columns to their values on the coset (`extend_dev`), a straight-line gate program run at every
 row (`eval_dev`), the division by the vanishing polynomial (`div_vanishing_dev`), and the three with the inverse transform in
-one call (`quotient_dev`).  Every call enqueues on the context's stream and returns; the caller synchronises before it reads a
+one call (`quotient_dev`); and the same quotient one coset of the small domain at a time, over a work buffer 2^e times smaller
+(`cosets_dev`, with its last step `cosets_join_dev`: include/snarkv_quotient_cosets.h).  Every call enqueues on the context's stream and returns; the caller synchronises before it reads a
 result.
 
 Columns are device addresses (ints, or anything with `data_ptr()`); shifts and constants are ints or 32-byte strings.  A
 program is a `Program`, or a pair (packed instructions, list of constants).
 
-This ctypes table is this module's own, as `poly_prod`'s and `ntt`'s are: one table per header.
+The ctypes tables are this module's own, as `poly_prod`'s and `ntt`'s are: one table per header.
 """
 import ctypes
 import struct
@@ -32,9 +33,22 @@ _SHAPES = {
 SIGNATURES = signatures(_SHAPES)
 
 
+# ... and include/snarkv_quotient_cosets.h
+_COSETS_SHAPES = {
+    "quotient_cosets_dev": _SHAPES["quotient_dev"],
+    "poly_cosets_join_dev": (_int, [_vp, _vp, _u32, _u32, _cp, _vp]),
+}
+COSETS_SIGNATURES = signatures(_COSETS_SHAPES)
+
+
 def api(pallas):
     """the functions of one library (`pallas`: the pasta build)"""
     return bind(_SHAPES, None, pallas)
+
+
+def cosets_api(pallas):
+    """the functions of include/snarkv_quotient_cosets.h in one library"""
+    return bind(_COSETS_SHAPES, None, pallas)
 
 
 def REG(i):
@@ -130,3 +144,18 @@ def quotient_dev(ctx, d_coeffs, k, e, n_cols, prog, shift, shift_inv, d_work, d_
     code, n_instr, consts, n_consts = _program(prog)
     a.check(a.quotient_dev(ctx._h, _addr(d_coeffs), k, e, n_cols, code, n_instr, consts, n_consts, _fe(shift), _fe(shift_inv),
                            _addr(d_work), _addr(d_h)))
+
+
+def cosets_dev(ctx, d_coeffs, k, e, n_cols, prog, shift, shift_inv, d_work, d_h):
+    """`quotient_dev`'s h, byte for byte, one coset of the 2^k domain at a time; d_work holds n_cols * 2^k elements"""
+    a = cosets_api(is_pallas(ctx))
+    code, n_instr, consts, n_consts = _program(prog)
+    a.check(a.quotient_cosets_dev(ctx._h, _addr(d_coeffs), k, e, n_cols, code, n_instr, consts, n_consts, _fe(shift), _fe(shift_inv),
+                                  _addr(d_work), _addr(d_h)))
+
+
+def cosets_join_dev(ctx, d_vals, k, e, shift_inv, d_out):
+    """2^e rows of 2^k values, row j the values on the coset (s W^j) H -> the 2^(k+e) coefficients of the polynomial; out may be
+    the input"""
+    a = cosets_api(is_pallas(ctx))
+    a.check(a.poly_cosets_join_dev(ctx._h, _addr(d_vals), k, e, _fe(shift_inv), _addr(d_out)))
