@@ -39,6 +39,7 @@ from . import host_api_pallas  # noqa: F401,E402  (the pasta flavour of the host
 from . import ipa_prover  # noqa: F401,E402  (the IPA prover on the device: include/snarkv_ipa_prover.h)
 from .ipa_prover import IpaProver  # noqa: F401,E402
 from . import ipa_batch  # noqa: F401,E402  (many vectors against one resident IPA key: include/snarkv_ipa_batch.h)
+from . import ipa_commit_blinded  # noqa: F401,E402  (many blinded commitments per call: include/snarkv_ipa_commit_blinded.h)
 from . import ipa_fold  # noqa: F401,E402  (decide_all as one folded check: include/snarkv_ipa_fold.h)
 from . import ipa_create  # noqa: F401,E402  (Ipa::create_proof in one call, Blake2b transcript on the device: include/snarkv_ipa_create.h)
 from . import poly  # noqa: F401,E402  (resident polynomials: linear combination, evaluation, division: include/snarkv_poly.h)
@@ -57,6 +58,7 @@ __all__ = [
     "host_api_pallas",
     "ipa_prover",
     "ipa_batch",
+    "ipa_commit_blinded",
     "ipa_fold",
     "ipa_create",
     "poly",

@@ -23,7 +23,8 @@ FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
 
 # the public headers the device units include (include/; the host mirror's are in _host_stale)
 DEVICE_HEADERS = ("amd", "pallas", "pallas_decompress", "ipa_prover", "ipa_batch", "ipa_fold", "ipa_create", "poly", "ipa_multiopen",
-                  "ntt", "poly_prod", "quotient", "quotient_cosets", "lookup", "poly_batch", "kzg_multiopen", "plonk_prove")
+                  "ntt", "poly_prod", "quotient", "quotient_cosets", "lookup", "poly_batch", "kzg_multiopen", "plonk_prove",
+                  "ipa_commit_blinded")
 
 
 def _deps():
@@ -105,8 +106,9 @@ def devtest_sources():
 #   args       the entry points' shared argument checks (csrc/poly_args.hpp)
 #   kzg_open   the host-side plan of the KZG multi-open provers (csrc/kzg_multiopen_plan.h)
 #   quotient_cosets  the join of the coset-at-a-time quotient, tile by tile (csrc/quotient.h)
+#   blind      the blind term of a blinded commitment, lane by lane and level by level (csrc/msm_blind.h)
 HOSTTEST_DIR = os.path.join(HERE, "..", "tests", "hosttest")
-HOSTTESTS = ("curve", "poly", "ntt", "poly_prod", "quotient", "lookup", "args", "kzg_open", "quotient_cosets")
+HOSTTESTS = ("curve", "poly", "ntt", "poly_prod", "quotient", "lookup", "args", "kzg_open", "quotient_cosets", "blind")
 HOSTTEST_EXCEPTIONS = {"curve": ("libhosttest_%s.so", ("curve_ops.h",))}  # the others: libhosttest_<name>_<curve>.so, one source
 
 

@@ -84,6 +84,7 @@ enum Slot {
   SLOT_QUOTIENT,     // the quotient (quotient.hip): the staged program and constants, the vanishing polynomial's table
   SLOT_LOOKUP,       // the lookup argument (lookup.hip): the sort's partition points, the flags and the totals of the count scans
   SLOT_POLY_BATCH,   // the batched evaluation (poly_batch.hip): a chunk's indices, and per query the roots and totals of the levels
+  SLOT_BLIND_ROWS,   // the blind term of a blinded commitment (msm_shared.hip): the rows 2^(8 w) S of the last S, S, staging
   SLOT_COUNT
 };
 
@@ -130,6 +131,9 @@ struct snarkv_ctx {
   // the transforms (ntt.hip): which (k, direction) the tables in SLOT_NTT were built for (0: none), and where the slot was then
   void* ntt_tables;
   uint32_t ntt_key;
+  // the blind term (msm_shared.hip): the S that the rows in SLOT_BLIND_ROWS were built for
+  uint8_t blind_s[64];
+  bool blind_rows_ready;
 };
 
 struct snarkv_dk {
@@ -237,6 +241,10 @@ int ipa_dk_table_prepare(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, bool* have);
 // encoding.  The table must be built.  slices = 0: chosen so that m x slices workgroups fill the machine.
 int launch_msm_shared(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_scalars, size_t n, size_t m, uint32_t slices,
                       void* d_out64s);
+// ... + blinds[a] * S: d_blinds = m canonical scalars in device memory, s64 = S on the host (read before the call returns).  The
+// blind terms are one more partial per vector, computed beside the MSM on the context's first lane.
+int launch_msm_shared_blinded(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_scalars, size_t n, size_t m,
+                              uint32_t slices, const void* d_blinds, const uint8_t* s64, void* d_out64s);
 // enqueue steps that another unit chains (quotient.hip), arguments taken as checked: the transform of snarkv_ntt_dev
 // (ntt.hip; shift = 8 canonical words or null) and the batch inversion of snarkv_poly_batch_invert_dev (poly_prod.hip)
 int ntt_enqueue(snarkv_ctx* ctx, const void* d_in, void* d_out, uint32_t k, size_t count, bool inverse, const uint32_t* shift);

@@ -20,6 +20,7 @@
 #include "ipa_prover.hpp"
 #include "../../include/snarkv_ipa_prover.h"
 #include "../../include/snarkv_ipa_batch.h"
+#include "../../include/snarkv_ipa_commit_blinded.h"
 
 namespace snarkv {
 
@@ -483,14 +484,18 @@ int SNARKV_API(ipa_commit)(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const uint8
 
 // m commitments against the resident key: the shared-key MSM (msm_shared.hip) when the key can have its window table,
 // one MSM per vector otherwise (a key over kSharedTableCap, SNARKV_IPA_SHARED=0).  Device to device, enqueued.
-static int commit_batch_run(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_polys, size_t n, size_t m,
-                            uint32_t slices, void* d_out, uint8_t* d_small) {
+static bool commit_shared_never() {
   static const bool never = [] {
     const char* e = getenv("SNARKV_IPA_SHARED");
     return e && *e && atoi(e) == 0;
   }();
+  return never;
+}
+
+static int commit_batch_run(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_polys, size_t n, size_t m,
+                            uint32_t slices, void* d_out, uint8_t* d_small) {
   bool shared = false;
-  if (!never) SNARKV_TRY(ipa_dk_table_prepare(ctx, dk, &shared));
+  if (!commit_shared_never()) SNARKV_TRY(ipa_dk_table_prepare(ctx, dk, &shared));
   if (shared) return launch_msm_shared(ctx, dk, d_polys, n, m, slices, d_out);
   const uint32_t off[2] = {0, (uint32_t)n};
   SNARKV_HIP(hipMemcpyAsync(d_small + 8, off, sizeof(off), hipMemcpyHostToDevice, ctx->stream));
@@ -532,6 +537,78 @@ int SNARKV_API(ipa_commit_batch_dev)(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, c
   SNARKV_TRY(ctx_reserve(ctx, SLOT_IPA_OUT, 64, &d_sm));
   SNARKV_TRY(commit_batch_validate(ctx, d_polys32, m * n, (uint8_t*)d_sm));
   return commit_batch_run(ctx, dk, d_polys32, n, m, slices, d_out64s, (uint8_t*)d_sm);
+}
+
+// The per-vector route of the blinded batch: the m MSMs write C_a into the point pairs [C_a, S], then ONE segmented launch
+// forms 1 C_a + blind_a S for every a.  Staging (SLOT_IPA_H): pairs | scalars [1, blind_a] | offsets {0, 2, .., 2 m} | {0, n}.
+static int commit_blinded_per_vector(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const uint8_t* s64, const void* d_polys, size_t n,
+                                     size_t m, const uint8_t* blinds32, void* d_out) {
+  const size_t o_sc = 128 * m, o_off = o_sc + 64 * m, o_0n = o_off + 4 * (m + 1), bytes = o_0n + 8;
+  std::vector<uint8_t> st(bytes, 0);
+  for (size_t a = 0; a < m; ++a) {
+    memcpy(&st[128 * a + 64], s64, 64);
+    st[o_sc + 64 * a] = 1;
+    memcpy(&st[o_sc + 64 * a + 32], blinds32 + 32 * a, 32);
+  }
+  for (size_t a = 0; a <= m; ++a) {
+    const uint32_t o = (uint32_t)(2 * a);
+    memcpy(&st[o_off + 4 * a], &o, 4);
+  }
+  const uint32_t off0n[2] = {0, (uint32_t)n};
+  memcpy(&st[o_0n], off0n, sizeof(off0n));
+  void* d;
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_IPA_H, bytes, &d));
+  uint8_t* d_st = (uint8_t*)d;
+  SNARKV_HIP(hipMemcpyAsync(d_st, st.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  SNARKV_HIP(hipStreamSynchronize(ctx->stream));  // `st` lives on this frame (as commit_batch_run's offsets do)
+  for (size_t a = 0; a < m; ++a)
+    SNARKV_TRY(ipa_msm(ctx, (const uint8_t*)d_polys + 32 * a * n, dk->d_points, n, d_st + o_0n, d_st + 128 * a));
+  return launch_msm_batched(ctx, d_st + o_sc, d_st, d_st + o_off, m, 2 * m, d_out);
+}
+
+int SNARKV_API(ipa_commit_blinded_batch_dev)(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const uint8_t s64[64],
+                                             const void* d_polys32, size_t n, size_t m, const uint8_t* blinds32,
+                                             uint32_t slices, void* d_out64s) {
+  if (!s64 || !blinds32) return SNARKV_ERR_ARG;
+  SNARKV_TRY(commit_batch_check(ctx, dk, d_polys32, n, m, d_out64s));
+  if (m > ((size_t)1 << 24)) return SNARKV_ERR_LENGTH;  // the staging of the blinds is one buffer
+  bool s_zero = true;
+  for (int i = 0; i < 64; ++i) s_zero = s_zero && s64[i] == 0;
+  if (s_zero) {
+    set_last_error("ipa_commit_blinded_batch: S is the point at infinity");
+    return SNARKV_ERR_ENCODING;
+  }
+  const bool validate = (ctx->flags & SNARKV_FLAG_VALIDATE) != 0;
+  if (validate)
+    for (size_t a = 0; a < m; ++a)
+      if (!host_canonical(blinds32 + 32 * a)) {
+        set_last_error("ipa_commit_blinded_batch: blind %zu is not canonical", a);
+        return SNARKV_ERR_ENCODING;
+      }
+  SNARKV_HIP(hipSetDevice(ctx->device));
+  SNARKV_WIRE_FORM(ctx);
+  void* d_sm;
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_IPA_OUT, 128, &d_sm));
+  if (validate) {  // S as every point under the flag: canonical coordinates, on the curve
+    int bad = 0;
+    SNARKV_HIP(hipMemcpyAsync((uint8_t*)d_sm + 64, s64, 64, hipMemcpyHostToDevice, ctx->stream));
+    SNARKV_TRY(launch_validate(ctx, nullptr, (uint8_t*)d_sm + 64, 1, &bad));
+    if (bad) {
+      set_last_error("ipa_commit_blinded_batch: S is not a canonical point of the curve");
+      return SNARKV_ERR_ENCODING;
+    }
+  }
+  SNARKV_TRY(commit_batch_validate(ctx, d_polys32, m * n, (uint8_t*)d_sm));
+  bool shared = false;
+  if (!commit_shared_never()) SNARKV_TRY(ipa_dk_table_prepare(ctx, dk, &shared));
+  if (!shared) return commit_blinded_per_vector(ctx, dk, s64, d_polys32, n, m, blinds32, d_out64s);
+  // the blinds through a buffer of this frame: pageable memory, which the transfer has left when hipMemcpyAsync returns
+  // (session_open's `st`), whatever memory the caller's are in
+  std::vector<uint8_t> st(blinds32, blinds32 + 32 * m);
+  void* d_bl;
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_IPA_XI, 32 * m, &d_bl));
+  SNARKV_HIP(hipMemcpyAsync(d_bl, st.data(), st.size(), hipMemcpyHostToDevice, ctx->stream));
+  return launch_msm_shared_blinded(ctx, dk, d_polys32, n, m, slices, d_bl, s64, d_out64s);
 }
 
 int SNARKV_API(ipa_commit_batch)(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const uint8_t* polys32, size_t n, size_t m,

@@ -19,12 +19,16 @@
 //                      (equal and opposite points, a piece that sums to the identity); identity rows are skipped;
 //                      the pieces of a bucket are stitched by a segmented suffix scan (steps without work are skipped);
 //                      sum_b b B_b by the running-sum identity over 64 lanes x 2 buckets -> one XYZZ partial per slice
+//   k_shared_blind   (blinded commitments) one wavefront per vector: blind * S against the 32 rows 2^(8 w) S, one digit of
+//                    the blind per lane (msm_blind.h) -> one more XYZZ partial per vector, beside k_shared_msm on a lane
 //   k_final          (msm_pippenger.hip, launch_fold_partials_many) folds the slices of every vector to its affine point
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 #include "ctx.hpp"
 #include "g1_29.h"
 #include "msm_shared.h"
+#include "msm_blind.h"
 
 namespace snarkv {
 
@@ -158,10 +162,11 @@ __device__ __forceinline__ void load_scalar(const uint32_t* __restrict__ p, uint
   shared_reduce_mod_r(s);
 }
 
-// grid (slices, vectors).  Slice s of vector a holds terms [s tps, min(n, (s + 1) tps)), tps <= kShMaxTerms.
+// grid (slices, vectors).  Slice s of vector a holds terms [s tps, min(n, (s + 1) tps)), tps <= kShMaxTerms; its partial
+// goes to partials[a * pstride + s]  (pstride = slices, or slices + 1 when k_shared_blind fills one more).
 __global__ void __launch_bounds__(64)
     k_shared_msm(const uint32_t* __restrict__ scalars, uint32_t n, uint32_t tps, const G1Packed* __restrict__ table,
-                 uint32_t nkey, G1Xyzz29* __restrict__ partials) {
+                 uint32_t nkey, uint32_t pstride, G1Xyzz29* __restrict__ partials) {
   __shared__ uint32_t ent[kShMaxEntries];
   __shared__ G1Xyzz29 part[kShSlots];
   __shared__ uint32_t cnt[kSharedBuckets], cur[kSharedBuckets], off[kSharedBuckets + 1], pbase[kSharedBuckets + 1];
@@ -307,7 +312,28 @@ __global__ void __launch_bounds__(64)
     __syncthreads();
     xyzz29_add_careful(x, y);
   }
-  if (lane == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = xyzz29_sanitize(x);
+  if (lane == 0) partials[(size_t)blockIdx.y * pstride + blockIdx.x] = xyzz29_sanitize(x);
+}
+
+// grid (vectors), one wavefront each: partials[a * pstride + slot] = blinds[a] * S from rows[w] = 2^(8 w) S.  Lane w < 32
+// takes digit w of the blind (reduced mod r first, so no carry leaves window 31); the arithmetic is msm_blind.h's.
+__global__ void __launch_bounds__(64)
+    k_shared_blind(const uint32_t* __restrict__ blinds, const G1Packed* __restrict__ rows, uint32_t pstride, uint32_t slot,
+                   G1Xyzz29* __restrict__ partials) {
+  __shared__ G1Xyzz29 sh[kSharedW];
+  const uint32_t lane = threadIdx.x;
+  if (lane < (uint32_t)kSharedW) {
+    uint32_t s[8];
+    load_scalar(blinds + 8 * (size_t)blockIdx.x, s);
+    sh[lane] = blind_lane_point(rows[lane], blind_digit(s, (int)lane));
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t half = kSharedW / 2; half >= 1; half >>= 1) {
+    blind_fold_level(sh, lane, half);
+    __syncthreads();
+  }
+  if (lane == 0) partials[(size_t)blockIdx.x * pstride + slot] = sh[0];
 }
 
 bool ipa_dk_table_fits(const snarkv_ipa_dk* dk) {
@@ -362,23 +388,76 @@ static uint32_t shared_slices(size_t n, size_t m, uint32_t slices) {
   return (uint32_t)std::max(s, s_min);
 }
 
-int launch_msm_shared(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_scalars, size_t n, size_t m, uint32_t slices,
-                      void* d_out64s) {
+// The rows 2^(8 w) S of the blind term, kept with the context: built on its stream when S differs from the one they were built
+// for (k_shared_table over the one-point key {S}: a chain of 248 doublings on one lane, once per S and not per call), read by
+// this stream and by the lane forked from it only.  Layout of the slot: rows | S | the table kernel's staging.
+constexpr size_t kBlindRowsBytes = kSharedW * sizeof(G1Packed);
+
+static int shared_blind_rows(snarkv_ctx* ctx, const uint8_t* s64, const G1Packed** rows) {
+  void* d;
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_BLIND_ROWS, kBlindRowsBytes + 64 + kSharedW * sizeof(ShTableTmp), &d));  // never grows
+  uint8_t* base = (uint8_t*)d;
+  *rows = (const G1Packed*)base;
+  if (ctx->blind_rows_ready && memcmp(ctx->blind_s, s64, 64) == 0) return SNARKV_OK;
+  ctx->blind_rows_ready = false;
+  memcpy(ctx->blind_s, s64, 64);
+  // from the context's own copy: it outlives the transfer
+  SNARKV_HIP(hipMemcpyAsync(base + kBlindRowsBytes, ctx->blind_s, 64, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_shared_table, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t*)(base + kBlindRowsBytes), 0u, 1u, 1u,
+                     (ShTableTmp*)(base + kBlindRowsBytes + 64), (G1Packed*)base);
+  SNARKV_HIP(hipGetLastError());
+  ctx->blind_rows_ready = true;
+  return SNARKV_OK;
+}
+
+// d_blinds = m canonical scalars and s64 = the point S (host), or both null: no blind term
+static int msm_shared_run(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_scalars, size_t n, size_t m, uint32_t slices,
+                          const void* d_blinds, const uint8_t* s64, void* d_out64s) {
   if (!dk->d_table || n == 0 || n > dk->count || m == 0) return SNARKV_ERR_ARG;
   const uint32_t tps = (uint32_t)((n + shared_slices(n, m, slices) - 1) / shared_slices(n, m, slices));
   const uint32_t S = (uint32_t)((n + tps - 1) / tps);  // no empty slice
-  const size_t group = std::min<size_t>({m, (size_t)kShMaxGroup, std::max<size_t>(1, kShPartialsCap / (S * sizeof(G1Xyzz29)))});
+  const uint32_t P = S + (d_blinds ? 1u : 0u);         // partials of a vector: its slices, then the blind term
+  const size_t group = std::min<size_t>({m, (size_t)kShMaxGroup, std::max<size_t>(1, kShPartialsCap / (P * sizeof(G1Xyzz29)))});
   void* d_parts;
-  SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_PARTIALS, group * S * sizeof(G1Xyzz29), &d_parts));
+  SNARKV_TRY(ctx_reserve(ctx, SLOT_TERM_PARTIALS, group * P * sizeof(G1Xyzz29), &d_parts));
+  const G1Packed* rows = nullptr;
+  // the blind kernel runs beside k_shared_msm on the first lane (a lane has none of its own: there it goes first)
+  const bool beside = d_blinds && !ctx->is_lane;
+  if (d_blinds) SNARKV_TRY(shared_blind_rows(ctx, s64, &rows));
+  if (beside) SNARKV_TRY(ctx_lanes(ctx));
   for (size_t a0 = 0; a0 < m; a0 += group) {
     const size_t g = std::min(group, m - a0);
+    if (d_blinds) {
+      hipStream_t bs = ctx->stream;
+      if (beside) {  // after everything enqueued so far: the rows, the blinds, the last fold that read these partials
+        bs = ctx->sub[0]->stream;
+        SNARKV_HIP(hipEventRecord(ctx->sub_ev[4], ctx->stream));
+        SNARKV_HIP(hipStreamWaitEvent(bs, ctx->sub_ev[4], 0));
+      }
+      hipLaunchKernelGGL(k_shared_blind, dim3((uint32_t)g), dim3(kShLanes), 0, bs, (const uint32_t*)d_blinds + 8 * a0, rows, P, S,
+                         (G1Xyzz29*)d_parts);
+      SNARKV_HIP(hipGetLastError());
+      if (beside) SNARKV_HIP(hipEventRecord(ctx->sub_ev[0], bs));
+    }
     hipLaunchKernelGGL(k_shared_msm, dim3(S, (uint32_t)g), dim3(kShLanes), 0, ctx->stream,
                        (const uint32_t*)d_scalars + 8 * a0 * n, (uint32_t)n, tps, (const G1Packed*)dk->d_table,
-                       (uint32_t)dk->count, (G1Xyzz29*)d_parts);
+                       (uint32_t)dk->count, P, (G1Xyzz29*)d_parts);
     SNARKV_HIP(hipGetLastError());
-    SNARKV_TRY(launch_fold_partials_many(ctx, d_parts, S, g, (uint8_t*)d_out64s + 64 * a0));
+    if (beside) SNARKV_HIP(hipStreamWaitEvent(ctx->stream, ctx->sub_ev[0], 0));
+    SNARKV_TRY(launch_fold_partials_many(ctx, d_parts, P, g, (uint8_t*)d_out64s + 64 * a0));
   }
   return SNARKV_OK;
+}
+
+int launch_msm_shared(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_scalars, size_t n, size_t m, uint32_t slices,
+                      void* d_out64s) {
+  return msm_shared_run(ctx, dk, d_scalars, n, m, slices, nullptr, nullptr, d_out64s);
+}
+
+int launch_msm_shared_blinded(snarkv_ctx* ctx, const snarkv_ipa_dk* dk, const void* d_scalars, size_t n, size_t m,
+                              uint32_t slices, const void* d_blinds, const uint8_t* s64, void* d_out64s) {
+  if (!d_blinds || !s64) return SNARKV_ERR_ARG;
+  return msm_shared_run(ctx, dk, d_scalars, n, m, slices, d_blinds, s64, d_out64s);
 }
 
 }  // namespace snarkv
