@@ -52,6 +52,7 @@ from . import poly_batch  # noqa: F401,E402  (many evaluations of resident polyn
 from . import kzg_multiopen  # noqa: F401,E402  (the Gwc19 and Bdfg21 multi-open provers, BN254: include/snarkv_kzg_multiopen.h)
 from . import host_kzg_open  # noqa: F401,E402  (the same through the host mirror and its transcripts: include/snarkv_host_kzg_open.h)
 from . import host_plonk_prove  # noqa: F401,E402  (the PLONK prover session of the host mirror: include/snarkv_host_plonk_prove.h)
+from . import host_plonk_prove_pallas  # noqa: F401,E402  (... on pallas over IPA: include/snarkv_host_pallas_plonk_prove.h)
 
 __all__ = [
     "host_api",
@@ -71,6 +72,7 @@ __all__ = [
     "kzg_multiopen",
     "host_kzg_open",
     "host_plonk_prove",
+    "host_plonk_prove_pallas",
     "IpaProver",
     "Context",
     "DecidingKey",

@@ -24,7 +24,7 @@ FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
 # the public headers the device units include (include/; the host mirror's are in _host_stale)
 DEVICE_HEADERS = ("amd", "pallas", "pallas_decompress", "ipa_prover", "ipa_batch", "ipa_fold", "ipa_create", "poly", "ipa_multiopen",
                   "ntt", "poly_prod", "quotient", "quotient_cosets", "lookup", "poly_batch", "kzg_multiopen", "plonk_prove",
-                  "ipa_commit_blinded")
+                  "ipa_commit_blinded", "pallas_session")
 
 
 def _deps():
@@ -79,7 +79,7 @@ def _link(lib, res, extra):
 # The pasta build of the curve-generic units (csrc/pallas.hip explains the flags, csrc/ctx.hpp the policy they select).
 PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover", "decompress_pallas", "msm_shared",
                 "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen", "ntt", "poly_prod", "quotient", "lookup",
-                "poly_batch"]
+                "poly_batch", "session"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
 
@@ -160,6 +160,8 @@ HOST_PALLAS_API_LIB = os.path.join(HERE, "libsnarkv_host_pallas.so")  # pasta fl
 HOST_PALLAS_FOLD_LIB = os.path.join(HERE, "libsnarkv_host_pallas_fold.so")
 # Ipa::create_proof in one call on top of it (host/capi_pallas_prove.cpp, include/snarkv_host_pallas_prove.h)
 HOST_PALLAS_PROVE_LIB = os.path.join(HERE, "libsnarkv_host_pallas_prove.so")
+# the PLONK prover session over IPA on top of it (host/capi_pallas_plonk_prove.cpp, include/snarkv_host_pallas_plonk_prove.h)
+HOST_PALLAS_PLONK_PROVE_LIB = os.path.join(HERE, "libsnarkv_host_pallas_plonk_prove.so")
 
 
 def _host_stale(out, dev_lib):
@@ -168,7 +170,8 @@ def _host_stale(out, dev_lib):
         "snarkv_host.h", "snarkv_host_pallas.h", "snarkv_pallas_decompress.h", "snarkv_host_pallas_fold.h", "snarkv_ipa_fold.h",
         "snarkv_host_pallas_prove.h", "snarkv_ipa_create.h", "snarkv_kzg_multiopen.h", "snarkv_host_kzg_open.h",
         "snarkv_host_plonk_prove.h", "snarkv_host_plonk_prove_opts.h", "snarkv_plonk_prove.h", "snarkv_quotient.h",
-        "snarkv_quotient_cosets.h", "snarkv_ntt.h", "snarkv_poly.h", "snarkv_poly_batch.h")]
+        "snarkv_quotient_cosets.h", "snarkv_ntt.h", "snarkv_poly.h", "snarkv_poly_batch.h", "snarkv_host_pallas_plonk_prove.h",
+        "snarkv_pallas_session.h", "snarkv_ipa_multiopen.h", "snarkv_ipa_commit_blinded.h")]
     newest = max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(dev_lib)])
     return not os.path.exists(out) or os.path.getmtime(out) < newest
 
@@ -210,6 +213,8 @@ def build_host_driver():
         _gxx(HOST_PALLAS_FOLD_LIB, "capi_pallas_fold.cpp", pasta, "snarkv_pallas", ["snarkv_host_pallas"])
     if os.path.exists(HOST_PALLAS_API_LIB) and _host_stale(HOST_PALLAS_PROVE_LIB, HOST_PALLAS_API_LIB):
         _gxx(HOST_PALLAS_PROVE_LIB, "capi_pallas_prove.cpp", pasta, "snarkv_pallas", ["snarkv_host_pallas"])
+    if os.path.exists(HOST_PALLAS_API_LIB) and _host_stale(HOST_PALLAS_PLONK_PROVE_LIB, HOST_PALLAS_API_LIB):
+        _gxx(HOST_PALLAS_PLONK_PROVE_LIB, "capi_pallas_plonk_prove.cpp", pasta, "snarkv_pallas", ["snarkv_host_pallas"])
     return HOST_LIB
 
 
@@ -231,6 +236,11 @@ def build_host_api_pallas_fold():
 def build_host_api_pallas_prove():
     build_host_driver()
     return HOST_PALLAS_PROVE_LIB
+
+
+def build_host_api_pallas_plonk_prove():
+    build_host_driver()
+    return HOST_PALLAS_PLONK_PROVE_LIB
 
 
 if __name__ == "__main__":

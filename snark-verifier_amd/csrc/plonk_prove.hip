@@ -1,91 +1,28 @@
 // The device side of the PLONK prover session (include/snarkv_plonk_prove.h): resident memory, stream-ordered copies, and
 // the one new kernel of the flow -- is the top of the quotient zero?  Everything else the session runs is the existing
-// stages' (ntt.hip, quotient.hip, poly_batch.hip, poly.hip, kzg_multiopen.hip, the Pippenger batch).
-#include <algorithm>
-#include "ctx.hpp"
-#include "poly_args.hpp"
+// stages' (ntt.hip, quotient.hip, poly_batch.hip, poly.hip, kzg_multiopen.hip, the Pippenger batch).  The bodies are
+// session_mem.hpp's, which the pasta build has under names of its own (session.hip).
+#include "session_mem.hpp"
 #include "../../include/snarkv_plonk_prove.h"
-
-namespace snarkv {
-
-// Any word of `vecs` 16-byte vectors not zero sets bit 0 of *status.  A pass over memory: 16 bytes a lane and step, the grid
-// strides; a wave that saw only zeros issues no atomic, so a quotient that divides costs none at all.  The status word is read
-// by the host at its next synchronisation, as k_kzg_check_rem's is.
-__global__ void __launch_bounds__(256) k_plonk_tail_nonzero(const uint4* __restrict__ tail, size_t vecs, uint32_t* __restrict__ status) {
-  uint32_t any = 0;
-  for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < vecs; i += (size_t)gridDim.x * 256u) {
-    const uint4 v = tail[i];
-    any |= v.x | v.y | v.z | v.w;
-  }
-  if (__ballot(any != 0) != 0 && (threadIdx.x & 63u) == 0) atomicOr(status, 1u);
-}
-
-}  // namespace snarkv
 
 using namespace snarkv;
 
 extern "C" {
 
-int snarkv_plonk_session_alloc(snarkv_ctx* ctx, size_t bytes, void** d_out) {
-  if (!ctx || !d_out) return SNARKV_ERR_ARG;
-  *d_out = nullptr;
-  if (bytes == 0) return SNARKV_ERR_EMPTY;
-  SNARKV_HIP(hipSetDevice(ctx->device));
-  void* d = nullptr;
-  SNARKV_HIP(hipMalloc(&d, bytes));
-  const hipError_t e = hipMemsetAsync(d, 0, bytes, ctx->stream);
-  if (e != hipSuccess) {
-    (void)hipFree(d);
-    set_last_error("plonk_session_alloc: hipMemsetAsync -> %s", hipGetErrorString(e));
-    return SNARKV_ERR_DEVICE;
-  }
-  *d_out = d;
-  return SNARKV_OK;
-}
+int snarkv_plonk_session_alloc(snarkv_ctx* ctx, size_t bytes, void** d_out) { return resident_alloc(ctx, bytes, d_out, "plonk_session_alloc"); }
 
-void snarkv_plonk_session_free(snarkv_ctx* ctx, void* d_mem) {
-  if (!ctx || !d_mem) return;
-  if (hipSetDevice(ctx->device) != hipSuccess) return;
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_mem);
-}
+void snarkv_plonk_session_free(snarkv_ctx* ctx, void* d_mem) { resident_free(ctx, d_mem); }
 
-int snarkv_plonk_session_upload(snarkv_ctx* ctx, void* d_dst, const void* src, size_t bytes) {
-  if (!ctx || !d_dst || !src) return SNARKV_ERR_ARG;
-  if (bytes == 0) return SNARKV_OK;
-  SNARKV_HIP(hipSetDevice(ctx->device));
-  SNARKV_HIP(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));  // pageable: staged before it returns
-  return SNARKV_OK;
-}
+int snarkv_plonk_session_upload(snarkv_ctx* ctx, void* d_dst, const void* src, size_t bytes) { return resident_upload(ctx, d_dst, src, bytes); }
 
 int snarkv_plonk_session_copy(snarkv_ctx* ctx, void* d_dst, const void* d_src, size_t bytes) {
-  if (!ctx || !d_dst || !d_src) return SNARKV_ERR_ARG;
-  if (overlap(d_dst, bytes, d_src, bytes)) return refuse_overlap("plonk_session_copy", "the source and the destination");
-  if (bytes == 0) return SNARKV_OK;
-  SNARKV_HIP(hipSetDevice(ctx->device));
-  SNARKV_HIP(hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  return SNARKV_OK;
+  return resident_copy(ctx, d_dst, d_src, bytes, "plonk_session_copy");
 }
 
-int snarkv_plonk_session_download(snarkv_ctx* ctx, void* dst, const void* d_src, size_t bytes) {
-  if (!ctx || !dst || !d_src) return SNARKV_ERR_ARG;
-  SNARKV_HIP(hipSetDevice(ctx->device));
-  if (bytes) SNARKV_HIP(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  SNARKV_HIP(hipStreamSynchronize(ctx->stream));
-  return SNARKV_OK;
-}
+int snarkv_plonk_session_download(snarkv_ctx* ctx, void* dst, const void* d_src, size_t bytes) { return resident_download(ctx, dst, d_src, bytes); }
 
 int snarkv_plonk_tail_check_dev(snarkv_ctx* ctx, const void* d_tail32, size_t count, void* d_status) {
-  if (!ctx || !aligned16(d_tail32) || !d_status || (uintptr_t)d_status % 4 != 0) return SNARKV_ERR_ARG;
-  if (count > ((size_t)1 << 36)) return SNARKV_ERR_LENGTH;
-  if (overlap(d_tail32, bytes_of(count), d_status, 4)) return refuse_overlap("plonk_tail_check", "the status word and the tail");
-  if (count == 0) return SNARKV_OK;
-  SNARKV_HIP(hipSetDevice(ctx->device));
-  const size_t vecs = 2 * count;  // the grid: one step per lane up to 2048 workgroups, strides beyond
-  const uint32_t blocks = (uint32_t)std::min<size_t>((vecs + 255) / 256, 2048);
-  hipLaunchKernelGGL(k_plonk_tail_nonzero, dim3(blocks), dim3(256), 0, ctx->stream, (const uint4*)d_tail32, vecs, (uint32_t*)d_status);
-  SNARKV_HIP(hipGetLastError());
-  return SNARKV_OK;
+  return resident_tail_check(ctx, d_tail32, count, d_status, "plonk_tail_check");
 }
 
 }  // extern "C"

@@ -253,7 +253,7 @@ class Blake2bTranscript : public Transcript {
 
   Fr squeeze_challenge() override {
     const uint8_t prefix = 0;
-    state_.update(&prefix, 1);
+    absorb(&prefix, 1);
     uint8_t h[64];
     state_.digest(h);
     return from_uniform_bytes(h);
@@ -266,15 +266,15 @@ class Blake2bTranscript : public Transcript {
   Error common_ec_point(const G1Affine& p) override {
     if (p.is_identity()) return Error{Error::Transcript, "cannot write points at infinity to the transcript"};
     const uint8_t prefix = 1;
-    state_.update(&prefix, 1);
-    state_.update(p.b, 64);
+    absorb(&prefix, 1);
+    absorb(p.b, 64);
     return {};
   }
   Error common_scalar(const Fr& s) override {
     uint8_t b[33];
     b[0] = 2;
     s.to_bytes(b + 1);
-    state_.update(b, 33);
+    absorb(b, 33);
     return {};
   }
   Result<Fr> read_scalar() override {
@@ -343,6 +343,16 @@ class Blake2bTranscript : public Transcript {
     return {};
   }
   const std::vector<uint8_t>& finalize() const { return stream_; }
+  const std::vector<uint8_t>& stream() const { return stream_; }  // the spelling of the KZG transcripts (transcript.hpp)
+  // The prover's hand-over to a device call that continues this transcript on its own hasher (the `absorbed` argument of
+  // include/snarkv_ipa_create.h and snarkv_ipa_multiopen.h).  From `record_absorbed()` on, every byte the hasher takes is
+  // kept as well: the prefixes, the points, the scalars and the 0 byte of each squeeze, in order.  Hashing `absorbed()`
+  // afresh gives this transcript's state.  Off by default; the reading side pays one untaken branch per update.
+  void record_absorbed() { recording_ = true; }
+  const std::vector<uint8_t>& absorbed() const { return absorbed_; }
+  // ... and what the call wrote comes back as bytes of the stream.  The hasher does not take them: the device's has, and
+  // nothing is squeezed from this transcript after an opening.
+  void append_opening(const uint8_t* bytes, size_t len) { stream_.insert(stream_.end(), bytes, bytes + len); }
   size_t remaining() const { return stream_.size() - pos_; }
   // Candidate decodings of the stream's compressed points: hint i = the 64-byte point and validity flag the device
   // answered for the 32 bytes at stream offset offs[i] (ascending).  Borrowed views of the batch's arrays: nothing is
@@ -403,6 +413,10 @@ class Blake2bTranscript : public Transcript {
     Fr::from_bytes(b, &out);
     return out;
   }
+  void absorb(const uint8_t* in, size_t len) {
+    state_.update(in, len);
+    if (recording_) absorbed_.insert(absorbed_.end(), in, in + len);
+  }
   bool take(uint8_t* out, size_t n) {
     if (pos_ + n > stream_.size()) return false;
     memcpy(out, stream_.data() + pos_, n);
@@ -412,6 +426,8 @@ class Blake2bTranscript : public Transcript {
   Blake2b state_;
   std::vector<uint8_t> stream_;
   size_t pos_ = 0;
+  bool recording_ = false;
+  std::vector<uint8_t> absorbed_;
 };
 
 }  // namespace snarkv_host

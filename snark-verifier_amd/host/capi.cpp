@@ -629,7 +629,8 @@ template <class MOS, class TR>
 int plonk_prover_begin_tr(const PlonkProtocol& pr, snarkv_ctx* ctx, const void* d_srs, const void* d_pre,
                           const std::vector<std::vector<Fr>>& inst, uint32_t flags, snarkv_host_plonk_prover** out) {
   auto s = std::make_unique<PlonkProver<MOS, TR>>();
-  const Error e = s->begin(pr, ctx, d_srs, d_pre, inst, flags);
+  s->scheme.d_srs = d_srs;
+  const Error e = s->begin(pr, ctx, d_pre, inst, flags);
   if (!e.ok()) return e.kind == Error::AssertionFailure ? SNARKV_HOST_ERR_OTHER : error_code(e);
   *out = new snarkv_host_plonk_prover{std::move(s)};
   return 1;

@@ -29,6 +29,9 @@
 
 #include "../../include/snarkv_ipa_prover.h"
 #include "../../include/snarkv_ipa_batch.h"
+#if defined(SNARKV_HOST_PALLAS)
+#include "../../include/snarkv_ipa_multiopen.h"
+#endif
 #include "pcs.hpp"
 
 // the prover session of the library the mirror is linked against (include/snarkv_ipa_prover.h)
@@ -519,7 +522,34 @@ inline Result<IpaAccumulator> IpaAs<MOS>::create_proof(const IpaDecidingKey& dk,
 // ------------------------------------------------------------------ Bgh19
 // bgh19.rs:98-153.  The IPA part arrives in halo2's order (S, xi, z, rounds, c, blind, G) and
 // is stored as the `IpaProof` it maps to (bgh19.rs:150).
-struct Bgh19 {};
+#if defined(SNARKV_HOST_PALLAS)
+class Blake2bTranscript;
+// What the device prover (include/snarkv_ipa_multiopen.h) takes besides the queries: the context whose stream has the
+// polynomials ready, the whole resident key with its h and s, n_polys x n coefficients contiguous in device memory, one blind
+// per polynomial, and the randomness, which is the caller's, in the order the prover draws it.
+struct Bgh19OpenInput {
+  snarkv_ctx* ctx;
+  const snarkv_ipa_dk* dk;
+  const G1Affine *h, *s;
+  const void* d_polys;
+  size_t n, n_polys;
+  const std::vector<Fr>* blinds;
+  Fr f_blind;
+  const void* d_pbar;
+  Fr omega_bar;
+};
+constexpr const char* kBgh19EvalMismatch = "evaluation does not match the polynomial";
+#endif
+// The scheme tag.  The pasta flavour carries the prover's half (halo2's `ProverIPA`), defined at the end of this file: one
+// call of the device prover over the bytes the transcript has hashed (`record_absorbed`), whose output is appended to the
+// stream.  A query whose evaluation is not its polynomial's is Error::assertion(kBgh19EvalMismatch); a point at infinity that
+// would have to be written is Error::Transcript; any other refusal of the device throws.
+struct Bgh19 {
+#if defined(SNARKV_HOST_PALLAS)
+  static Result<IpaAccumulator> create_proof(const Bgh19OpenInput& in, const Fr& z, const std::vector<Query<Fr>>& queries,
+                                             Blake2bTranscript& t);
+#endif
+};
 struct Bgh19Proof {
   Fr x_1, x_2;
   G1Affine f;
@@ -685,3 +715,49 @@ struct IpaBgh19 {
 };
 
 }  // namespace snarkv_host
+
+#if defined(SNARKV_HOST_PALLAS)
+#include "blake2b_transcript.hpp"
+
+namespace snarkv_host {
+
+inline Result<IpaAccumulator> Bgh19::create_proof(const Bgh19OpenInput& in, const Fr& z, const std::vector<Query<Fr>>& queries,
+                                                  Blake2bTranscript& t) {
+  using R = Result<IpaAccumulator>;
+  if (!in.blinds || in.blinds->size() != in.n_polys) throw Panic("Bgh19::create_proof: one blind per polynomial");
+  const size_t k = snarkv_pallas_ipa_dk_k(in.dk);
+  std::vector<uint8_t> blinds = ipa_prover_detail::pack(*in.blinds);
+  std::vector<uint32_t> q_poly(queries.size());
+  std::vector<uint8_t> q_shift(32 * queries.size()), q_eval(32 * queries.size());
+  for (size_t i = 0; i < queries.size(); ++i) {
+    q_poly[i] = (uint32_t)queries[i].poly;
+    queries[i].shift.to_bytes(&q_shift[32 * i]);
+    queries[i].eval.to_bytes(&q_eval[32 * i]);
+  }
+  uint8_t z32[32], f_blind32[32], omega_bar32[32], u[64];
+  z.to_bytes(z32);
+  in.f_blind.to_bytes(f_blind32);
+  in.omega_bar.to_bytes(omega_bar32);
+  const std::vector<uint8_t>& absorbed = t.absorbed();
+  std::vector<uint8_t> proof(64 * k + 32 * queries.size() + 160), xi(32 * k);  // at most one set per query
+  size_t len = 0;
+  const int rc = snarkv_pallas_ipa_multiopen_create_proof_dev(
+      in.ctx, in.dk, in.h->b, in.s->b, in.d_polys, in.n, in.n_polys, blinds.data(), z32, q_poly.data(), q_shift.data(), q_eval.data(),
+      queries.size(), f_blind32, in.d_pbar, omega_bar32, absorbed.data(), absorbed.size(), proof.data(), proof.size(), &len, xi.data(), u);
+  if (rc != SNARKV_OK) {
+    const std::string what = snarkv_pallas_last_error();
+    if (rc == SNARKV_ERR_ENCODING) return R::Err(Error{Error::Transcript, what});
+    if (rc == SNARKV_ERR_ARG && what.find(kBgh19EvalMismatch) != std::string::npos) return R::Err(Error::assertion(kBgh19EvalMismatch));
+    throw std::runtime_error("ipa_multiopen_create_proof: " + what + " (code " + std::to_string(rc) + ")");
+  }
+  t.append_opening(proof.data(), len);
+  IpaAccumulator acc;
+  acc.xi.resize(k);
+  for (size_t i = 0; i < k; ++i)
+    if (!Fr::from_bytes(&xi[32 * i], &acc.xi[i])) throw std::runtime_error("ipa_multiopen_create_proof: a non-canonical challenge");
+  acc.u = G1Affine::from_bytes(u);
+  return R::Ok(std::move(acc));
+}
+
+}  // namespace snarkv_host
+#endif

@@ -128,4 +128,50 @@ int hp_transcript_script(const uint8_t* proof, size_t plen, const char* ops, siz
     return (int)n_ops;
   });
 }
+// The prover's side with the record of the hasher's input (Blake2bTranscript::record_absorbed): ops = 's' common_scalar (32
+// bytes of `data`), 'p' write_ec_point (64 bytes), 'w' write_scalar (32 bytes), 'C' squeeze.  Then the next challenge is drawn
+// twice: from the transcript (next_a), and from a fresh hasher over the recorded bytes and the 0 byte of a squeeze (next_b) --
+// what a device call that is handed `absorbed` does.  `tail` is appended as an opening's bytes.  Out: the recorded bytes and the
+// stream.  `record` = 0 leaves the record off: it stays empty.  Returns the ops done, -10 at a Transcript error, -11 when an
+// output does not fit `cap`.
+int hp_transcript_record(const uint8_t* data, const char* ops, size_t n_ops, int record, const uint8_t* tail, size_t tail_len,
+                         uint8_t* rec_out, size_t* rec_len, uint8_t* stream_out, size_t* stream_len, size_t cap, uint8_t* next_a,
+                         uint8_t* next_b) {
+  return guarded([&] {
+    Blake2bTranscript t;
+    if (record) t.record_absorbed();
+    size_t at = 0;
+    for (size_t i = 0; i < n_ops; ++i) {
+      Error e;
+      Fr x;
+      if (ops[i] == 'p') {
+        e = t.write_ec_point(G1Affine::from_bytes(data + at));
+        at += 64;
+      } else if (ops[i] == 'C') {
+        (void)t.squeeze_challenge();
+      } else {
+        if (!Fr::from_bytes(data + at, &x)) return -10;
+        e = ops[i] == 's' ? t.common_scalar(x) : t.write_scalar(x);
+        at += 32;
+      }
+      if (!e.ok()) return -10;
+    }
+    const std::vector<uint8_t> rec = t.absorbed();
+    t.squeeze_challenge().to_bytes(next_a);
+    Blake2b fresh(64, "Halo2-Transcript");
+    fresh.update(rec.data(), rec.size());
+    const uint8_t zero = 0;
+    fresh.update(&zero, 1);
+    uint8_t h[64];
+    fresh.digest(h);
+    Blake2bTranscript::from_uniform_bytes(h).to_bytes(next_b);
+    t.append_opening(tail, tail_len);
+    if (rec.size() > cap || t.stream().size() > cap) return -11;
+    if (!rec.empty()) memcpy(rec_out, rec.data(), rec.size());
+    *rec_len = rec.size();
+    if (!t.stream().empty()) memcpy(stream_out, t.stream().data(), t.stream().size());
+    *stream_len = t.stream().size();
+    return (int)n_ops;
+  });
+}
 }
