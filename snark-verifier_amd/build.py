@@ -107,8 +107,9 @@ def devtest_sources():
 #   kzg_open   the host-side plan of the KZG multi-open provers (csrc/kzg_multiopen_plan.h)
 #   quotient_cosets  the join of the coset-at-a-time quotient, tile by tile (csrc/quotient.h)
 #   blind      the blind term of a blinded commitment, lane by lane and level by level (csrc/msm_blind.h)
+#   curve_fm   the friendly-multiple products of csrc/fq29.h and the fast adders of csrc/g1_29.h on them, raw limbs
 HOSTTEST_DIR = os.path.join(HERE, "..", "tests", "hosttest")
-HOSTTESTS = ("curve", "poly", "ntt", "poly_prod", "quotient", "lookup", "args", "kzg_open", "quotient_cosets", "blind")
+HOSTTESTS = ("curve", "poly", "ntt", "poly_prod", "quotient", "lookup", "args", "kzg_open", "quotient_cosets", "blind", "curve_fm")
 HOSTTEST_EXCEPTIONS = {"curve": ("libhosttest_%s.so", ("curve_ops.h",))}  # the others: libhosttest_<name>_<curve>.so, one source
 
 

@@ -30,6 +30,10 @@
 //     sites in g1_29.h feed narrower operands and stay inside (-p/4, 5p/4).
 //     tests/fq29_model.py asserts the budget, the shape and that range on raw
 //     limbs, for the host build and the device builds.
+//     The `_fm` products (fq29_mul_fm ...: a Montgomery-friendly multiple of p in seven
+//     of the nine reduction steps, no digit multiply there) have the same contract
+//     with the range a*b/2^261 + [0, (1 + 2^-29) p); the Pippenger's fast bucket
+//     additions run on them (tests/fq29_fm_model.py).
 //   * add/sub/neg are limb-wise and never carry; `fq29_norm` re-normalises the
 //     limbs (value unchanged) when the next product needs it.
 //   * zero/equality tests mod p need `fq29_is_zero_mod_p` (canonicalising).
@@ -54,6 +58,18 @@ SNARKV_HD constexpr int32_t fq29_p(int i) {
   constexpr int32_t p[9] = SNARKV_FQ29_P_LIMBS;
   return p[i];
 }
+
+// The Montgomery-friendly multiple of p used by the `_fm` products below: M = NINV * p = -1 (mod 2^29), ten limbs with
+// limb 0 = 2^29 - 1 and limb 1 stored ALREADY INCREMENTED (SNARKV_FQ29_FM_LIMBS, gen_consts.py).  The first kFq29FmSteps of
+// the nine reduction steps add a multiple of M, the last two a multiple of p.  Seven, not eight: with eight the excess
+// over a*b/2^261 reaches 1.14 p (exact-integer model), with seven it stays below (1 + 2^-29) p.
+constexpr int kFq29FmSteps = 7;
+
+SNARKV_HD constexpr int32_t fq29_fm(int i) {
+  constexpr int32_t m[10] = SNARKV_FQ29_FM_LIMBS;
+  return m[i];
+}
+static_assert(fq29_fm(0) == kMask29, "limb 0 of the friendly multiple must be 2^29 - 1: the digit is the column's low bits");
 
 SNARKV_HD Fq29 fq29_zero() {
   Fq29 r;
@@ -250,6 +266,146 @@ SNARKV_HD Fq29 fq29_sqr(const Fq29& a) {
   return r;
 #endif
 }
+
+// ---- the same three products with the friendly multiple in the low reduction steps ("_fm") ----
+// Step k of the reduction above spends one `v_mul_lo_u32` on its digit m[k] = (acc * NINV) & mask -- a full-rate issue slot
+// like a multiply-add, 9 per product, 81 per bucket addition.  For k < kFq29FmSteps the `_fm` products add q M 2^(29 k)
+// instead of m[k] p 2^(29 k), M = NINV p: since M = -1 (mod 2^29) the digit is q = acc & mask (no product), column k needs
+// no multiply-add at all (acc + q (2^29 - 1) has its low 29 bits clear) and carries (acc >> 29) + q; that + q rides in the
+// next column through the constant fq29_fm(1) = M_1 + 1.  Columns k + 1 .. k + 9 take q * fq29_fm(1 .. 9): nine
+// multiply-adds, as many as q * p_0 .. p_8 before.  Steps 7 and 8 are the ordinary ones, so the value still fits nine limbs:
+// what is added is below 2^203 M + 2^261 p, and
+//     out  in  a*b/2^261 + [0, (1 + 2^-29) p)     (same residue, a DIFFERENT representative than fq29_mul's)
+// with limbs 0..7 in [0, 2^29) and the same column budget (the constants of a column are again at most nine limbs below
+// 2^29).  Operand contracts as for fq29_mul / fq29_mul2 / fq29_sqr.  Raw limbs differ from the pinned products, so these are
+// only for formulas whose sets close with the wider interval: the fast adders of g1_29.h (tests/fq29_fm_model.py redoes
+// their interval argument); canonicalisation, the careful adders and everything outside the Pippenger keep the pinned ones.
+// On pallas p_0 = 1 and three limbs of p are zero where only two of M are: the `_fm` form is one multiply-add per step
+// MORE there, so the pasta build's Pippenger does not select it (SNARKV_FQ29_FM, msm_pippenger.hip).
+
+// reduction products of column k: digit i against M (i < kFq29FmSteps) or against p
+SNARKV_HD int64_t fq29_fm_column(int k, const int32_t m[9], int64_t acc) {
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    if (i >= k) continue;
+    if (i < kFq29FmSteps) {
+      if (k - i <= 9) acc += (int64_t)m[i] * fq29_fm(k - i);
+    } else if (k - i <= 8) {
+      acc += (int64_t)m[i] * fq29_p(k - i);
+    }
+  }
+  return acc;
+}
+
+// digit of column k < 9, and the column's carry
+SNARKV_HD int64_t fq29_fm_digit(int k, int32_t m[9], int64_t acc) {
+  if (k < kFq29FmSteps) {
+    m[k] = (int32_t)acc & kMask29;  // acc + m[k] (2^29 - 1) = (acc >> 29) 2^29 + m[k] 2^29: the + m[k] is in fq29_fm(1)
+  } else {
+    m[k] = (int32_t)(((uint32_t)acc * (uint32_t)SNARKV_FQ29_NINV) & (uint32_t)kMask29);
+    acc += (int64_t)m[k] * fq29_p(0);
+  }
+  return acc >> 29;
+}
+
+SNARKV_HD Fq29 fq29_mul_fm(const Fq29& a, const Fq29& b) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(SNARKV_NO_SMAD_ASM)
+#include "fq29_mul_fm_asm.inc"
+#else
+  int32_t m[9];
+  Fq29 r;
+  int64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+#pragma unroll
+    for (int i = 0; i <= k; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
+    acc = fq29_fm_digit(k, m, fq29_fm_column(k, m, acc));
+  }
+#pragma unroll
+  for (int k = 9; k < 17; ++k) {
+#pragma unroll
+    for (int i = k - 8; i < 9; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
+    acc = fq29_fm_column(k, m, acc);
+    r.v[k - 9] = (int32_t)acc & kMask29;
+    acc >>= 29;
+  }
+  r.v[8] = (int32_t)acc;
+  return r;
+#endif
+}
+
+SNARKV_HD Fq29 fq29_mul2_fm(const Fq29& a, const Fq29& b, const Fq29& c, const Fq29& d) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(SNARKV_NO_SMAD_ASM)
+#include "fq29_mul2_fm_asm.inc"
+#else
+  int32_t m[9];
+  Fq29 r;
+  int64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+#pragma unroll
+    for (int i = 0; i <= k; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
+#pragma unroll
+    for (int i = 0; i <= k; ++i) acc = fq29_smad(c.v[i], d.v[k - i], acc);
+    acc = fq29_fm_digit(k, m, fq29_fm_column(k, m, acc));
+  }
+#pragma unroll
+  for (int k = 9; k < 17; ++k) {
+#pragma unroll
+    for (int i = k - 8; i < 9; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
+#pragma unroll
+    for (int i = k - 8; i < 9; ++i) acc = fq29_smad(c.v[i], d.v[k - i], acc);
+    acc = fq29_fm_column(k, m, acc);
+    r.v[k - 9] = (int32_t)acc & kMask29;
+    acc >>= 29;
+  }
+  r.v[8] = (int32_t)acc;
+  return r;
+#endif
+}
+
+SNARKV_HD Fq29 fq29_sqr_fm(const Fq29& a) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(SNARKV_NO_SMAD_ASM)
+#include "fq29_sqr_fm_asm.inc"
+#else
+  int32_t m[9], a2[9];
+  Fq29 r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) a2[i] = a.v[i] * 2;
+  int64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+#pragma unroll
+    for (int i = 0; 2 * i < k; ++i) acc = fq29_smad(a2[i], a.v[k - i], acc);
+    if ((k & 1) == 0) acc = fq29_smad(a.v[k / 2], a.v[k / 2], acc);
+    acc = fq29_fm_digit(k, m, fq29_fm_column(k, m, acc));
+  }
+#pragma unroll
+  for (int k = 9; k < 17; ++k) {
+#pragma unroll
+    for (int i = k - 8; 2 * i < k; ++i) acc = fq29_smad(a2[i], a.v[k - i], acc);
+    if ((k & 1) == 0) acc = fq29_smad(a.v[k / 2], a.v[k / 2], acc);
+    acc = fq29_fm_column(k, m, acc);
+    r.v[k - 9] = (int32_t)acc & kMask29;
+    acc >>= 29;
+  }
+  r.v[8] = (int32_t)acc;
+  return r;
+#endif
+}
+
+// The products a formula is written over: the pinned ones above, or the `_fm` ones.  g1_29.h takes one of these as the
+// template parameter of its fast adders.
+struct Fq29Pinned {
+  SNARKV_HD static Fq29 mul(const Fq29& a, const Fq29& b) { return fq29_mul(a, b); }
+  SNARKV_HD static Fq29 sqr(const Fq29& a) { return fq29_sqr(a); }
+  SNARKV_HD static Fq29 mul2(const Fq29& a, const Fq29& b, const Fq29& c, const Fq29& d) { return fq29_mul2(a, b, c, d); }
+};
+struct Fq29Fm {
+  SNARKV_HD static Fq29 mul(const Fq29& a, const Fq29& b) { return fq29_mul_fm(a, b); }
+  SNARKV_HD static Fq29 sqr(const Fq29& a) { return fq29_sqr_fm(a); }
+  SNARKV_HD static Fq29 mul2(const Fq29& a, const Fq29& b, const Fq29& c, const Fq29& d) { return fq29_mul2_fm(a, b, c, d); }
+};
 
 // (Measured and removed, round 2: PAIRS of independent products interleaved column by column -- 2 404 -> 2 278 issued
 // instructions per bucket addition, one MSM alone level, four in flight 1-5 % slower: profiles/r02_ab_pairs.txt, git tag

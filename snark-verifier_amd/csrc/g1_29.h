@@ -16,6 +16,7 @@
 //   acc.x   carry-normalised, value in (-4p, 2p)
 //   acc.y   lazy difference of two N: |limb| < 2^29, value in (-2p, 2p)
 //   acc.zz, acc.zzz   N
+// (the same with the `_fm` products, N then being a*b/2^261 + [0, (1 + 2^-29) p): every interval below has that much room)
 // This set S is CLOSED under every adder and under xyzz29_double, for BN254 and
 // for pallas (2^261/p = 128, the tighter one: pp = sqr(pn) reaches 1.20p).
 // A Jacobian doubling chain (jac29_double ... jac29_to_xyzz, xyzz29_double_n)
@@ -122,9 +123,20 @@ SNARKV_HD G1Xyzz29 xyzz29_from_affine(const G1Affine29& p) {
   return r;
 }
 
+// ---- the fast adders, written ONCE over the products PR (fq29.h): Fq29Pinned gives the functions every other layer and
+// the raw-limb tests know (xyzz29_madd_fast ...), Fq29Fm the `_fm` forms of the Pippenger's bucket additions
+// (xyzz29_madd_fast_fm ...), whose product outputs lie in a*b/2^261 + [0, (1 + 2^-29) p): the set S closes under them too
+// (tests/fq29_fm_model.py runs the interval argument and the corners).  The members are at column 0 and spell their
+// products fq29_mul / fq29_sqr / fq29_mul2 because tests/fq29_model.py reads and executes this text.
+template <class PR>
+struct Xyzz29Fast {
+SNARKV_HD static Fq29 fq29_mul(const Fq29& a, const Fq29& b) { return PR::mul(a, b); }
+SNARKV_HD static Fq29 fq29_sqr(const Fq29& a) { return PR::sqr(a); }
+SNARKV_HD static Fq29 fq29_mul2(const Fq29& a, const Fq29& b, const Fq29& c, const Fq29& d) { return PR::mul2(a, b, c, d); }
+
 // ---- shared tail of madd / add: given U1 (=X1 scaled), S1, P, R (normalised) --
 //   X3 = R^2 - PPP - 2Q,  Y3 = R (Q - X3) - S1 PPP
-SNARKV_HD void xyzz29_finish(G1Xyzz29& acc, const Fq29& u1, const Fq29& s1, const Fq29& pn, const Fq29& rn,
+SNARKV_HD static void xyzz29_finish(G1Xyzz29& acc, const Fq29& u1, const Fq29& s1, const Fq29& pn, const Fq29& rn,
                              Fq29& pp, Fq29& ppp) {
   pp = fq29_sqr(pn);
   ppp = fq29_mul(pn, pp);
@@ -138,7 +150,7 @@ SNARKV_HD void xyzz29_finish(G1Xyzz29& acc, const Fq29& u1, const Fq29& s1, cons
 }
 
 // acc += P (affine, non-identity), acc non-identity.  madd-2008-s, 8M + 2S.
-SNARKV_HD void xyzz29_madd_fast(G1Xyzz29& acc, const G1Affine29& p) {
+SNARKV_HD static void xyzz29_madd_fast(G1Xyzz29& acc, const G1Affine29& p) {
   Fq29 u2 = fq29_mul(p.x, acc.zz);
   Fq29 s2 = fq29_mul(p.y, acc.zzz);
   Fq29 pn = fq29_norm(fq29_sub(u2, acc.x));  // limbs (-2^29, 2^30) -> norm
@@ -151,7 +163,7 @@ SNARKV_HD void xyzz29_madd_fast(G1Xyzz29& acc, const G1Affine29& p) {
 }
 
 // acc += b, both non-identity.  add-2008-s, 12M + 2S.
-SNARKV_HD void xyzz29_add_fast(G1Xyzz29& acc, const G1Xyzz29& b) {
+SNARKV_HD static void xyzz29_add_fast(G1Xyzz29& acc, const G1Xyzz29& b) {
   Fq29 u1 = fq29_mul(acc.x, b.zz);
   Fq29 u2 = fq29_mul(b.x, acc.zz);
   Fq29 s1 = fq29_mul(acc.y, b.zzz);
@@ -162,6 +174,40 @@ SNARKV_HD void xyzz29_add_fast(G1Xyzz29& acc, const G1Xyzz29& b) {
   xyzz29_finish(acc, u1, s1, pn, rn, pp, ppp);
   acc.zz = fq29_mul(fq29_mul(acc.zz, b.zz), pp);
   acc.zzz = fq29_mul(fq29_mul(acc.zzz, b.zzz), ppp);
+}
+
+// acc += b where either may be the stored identity (exact zero ZZ); fast
+// formulas otherwise.  A fast addition that meets an exceptional case leaves
+// ZZ = 0 (mod p), i.e. the integer 0 or p.  The integer 0 would later pass for
+// the stored identity, so it is caught HERE (`bad`, sticky); the value p keeps
+// its non-zero limbs, poisons everything it is added to, and is caught by the
+// caller's final `xyzz29_is_degenerate`.
+SNARKV_HD static void xyzz29_add_skipid_fast(G1Xyzz29& acc, const G1Xyzz29& b, bool& bad) {
+  if (xyzz29_is_identity(b)) return;
+  if (xyzz29_is_identity(acc)) {
+    acc = b;
+    return;
+  }
+  xyzz29_add_fast(acc, b);
+  bad = bad || fq29_limbs_all_zero(acc.zz);
+}
+};  // Xyzz29Fast
+
+SNARKV_HD void xyzz29_finish(G1Xyzz29& acc, const Fq29& u1, const Fq29& s1, const Fq29& pn, const Fq29& rn, Fq29& pp, Fq29& ppp) {
+  Xyzz29Fast<Fq29Pinned>::xyzz29_finish(acc, u1, s1, pn, rn, pp, ppp);
+}
+SNARKV_HD void xyzz29_madd_fast(G1Xyzz29& acc, const G1Affine29& p) { Xyzz29Fast<Fq29Pinned>::xyzz29_madd_fast(acc, p); }
+SNARKV_HD void xyzz29_add_fast(G1Xyzz29& acc, const G1Xyzz29& b) { Xyzz29Fast<Fq29Pinned>::xyzz29_add_fast(acc, b); }
+SNARKV_HD void xyzz29_add_skipid_fast(G1Xyzz29& acc, const G1Xyzz29& b, bool& bad) {
+  Xyzz29Fast<Fq29Pinned>::xyzz29_add_skipid_fast(acc, b, bad);
+}
+SNARKV_HD void xyzz29_finish_fm(G1Xyzz29& acc, const Fq29& u1, const Fq29& s1, const Fq29& pn, const Fq29& rn, Fq29& pp, Fq29& ppp) {
+  Xyzz29Fast<Fq29Fm>::xyzz29_finish(acc, u1, s1, pn, rn, pp, ppp);
+}
+SNARKV_HD void xyzz29_madd_fast_fm(G1Xyzz29& acc, const G1Affine29& p) { Xyzz29Fast<Fq29Fm>::xyzz29_madd_fast(acc, p); }
+SNARKV_HD void xyzz29_add_fast_fm(G1Xyzz29& acc, const G1Xyzz29& b) { Xyzz29Fast<Fq29Fm>::xyzz29_add_fast(acc, b); }
+SNARKV_HD void xyzz29_add_skipid_fast_fm(G1Xyzz29& acc, const G1Xyzz29& b, bool& bad) {
+  Xyzz29Fast<Fq29Fm>::xyzz29_add_skipid_fast(acc, b, bad);
 }
 
 // 2*P (dbl-2008-s-1, a = 0), P non-identity.
@@ -320,22 +366,6 @@ SNARKV_HD void xyzz29_add_careful(G1Xyzz29& acc, const G1Xyzz29& b) {
   xyzz29_finish(acc, u1, s1, pn, rn, pp, ppp);
   acc.zz = fq29_mul(fq29_mul(acc.zz, b.zz), pp);
   acc.zzz = fq29_mul(fq29_mul(acc.zzz, b.zzz), ppp);
-}
-
-// acc += b where either may be the stored identity (exact zero ZZ); fast
-// formulas otherwise.  A fast addition that meets an exceptional case leaves
-// ZZ = 0 (mod p), i.e. the integer 0 or p.  The integer 0 would later pass for
-// the stored identity, so it is caught HERE (`bad`, sticky); the value p keeps
-// its non-zero limbs, poisons everything it is added to, and is caught by the
-// caller's final `xyzz29_is_degenerate`.
-SNARKV_HD void xyzz29_add_skipid_fast(G1Xyzz29& acc, const G1Xyzz29& b, bool& bad) {
-  if (xyzz29_is_identity(b)) return;
-  if (xyzz29_is_identity(acc)) {
-    acc = b;
-    return;
-  }
-  xyzz29_add_fast(acc, b);
-  bad = bad || fq29_limbs_all_zero(acc.zz);
 }
 
 // Make a result storable: a degenerate ZZ (= 0 mod p but non-zero limbs) must

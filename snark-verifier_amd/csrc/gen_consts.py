@@ -37,6 +37,13 @@ def generic_section(p, r, b, name, r_gen):
     print("#define SNARKV_FR_R_LIMBS { %s }" % lim(r))
     print("#define SNARKV_FQ29_P_LIMBS { %s }" % lim29(p))
     print("#define SNARKV_FQ29_NINV 0x%08x  // -p^-1 mod 2^29" % ((-pow(p, -1, 1 << 29)) % (1 << 29)))
+    # the Montgomery-friendly multiple of p (fq29_mul_fm): M = NINV * p = -1 mod 2^29, ten limbs, limb 1 already incremented
+    # (the digit a friendly reduction step leaves in the carry rides there)
+    ninv = (-pow(p, -1, 1 << 29)) % (1 << 29)
+    fm = [((ninv * p) >> (29 * i)) & ((1 << 29) - 1) for i in range(10)]
+    assert fm[0] == (1 << 29) - 1 and (ninv * p) >> 290 == 0 and fm[1] + 1 < 1 << 29
+    fm[1] += 1
+    print("#define SNARKV_FQ29_FM_LIMBS { %s }  // NINV * p, limb 1 + 1" % ", ".join("0x%08x" % v for v in fm))
     print("#define SNARKV_FQ29_ONE_LIMBS { %s }  // 2^261 mod p" % lim29(r29 % p))
     print("#define SNARKV_FQ29_R2_LIMBS { %s }  // 2^522 mod p" % lim29(r29 * r29 % p))
     # halo2curves / pasta_curves keep field elements as a * 2^256 mod p in 4 x u64: in by 2^266 (-> a * 2^261), out by 2^256

@@ -113,6 +113,24 @@ namespace snarkv {
 #define SNARKV_BPRIO 3
 #endif
 #define SNARKV_RAISE_PRIO() __builtin_amdgcn_s_setprio(SNARKV_BPRIO)
+// The products under the FAST bucket additions (k_accumulate's mixed additions, the running sums of k_bucket_reduce, the
+// stitch of k_fixup): 1 = the `_fm` products of fq29.h (friendly multiple of p in seven of the nine reduction steps: 63
+// `v_mul_lo_u32` less per addition on BN254), 0 = the pinned ones.  The sets of g1_29.h close under either and the two
+// mix freely (a bucket one kernel leaves is an operand of the next); every careful adder, the degeneracy tests and
+// to_affine keep the pinned products.  Off on pallas, where the friendly multiple has two zero limbs against the three of
+// p and p_0 = 1 makes the digit a negation already: the `_fm` form would issue MORE there (fq29.h).
+#ifndef SNARKV_FQ29_FM
+#if defined(SNARKV_CURVE_PALLAS)
+#define SNARKV_FQ29_FM 0
+#else
+#define SNARKV_FQ29_FM 1
+#endif
+#endif
+#if SNARKV_FQ29_FM
+using PipFast = Xyzz29Fast<Fq29Fm>;
+#else
+using PipFast = Xyzz29Fast<Fq29Pinned>;
+#endif
 
 constexpr int kHalves = SNARKV_GLV ? 2 : 1;       // virtual points per input point: P and phi(P), or P alone
 constexpr int kDigitWords = SNARKV_GLV ? 4 : 8;   // words of a digit source: a 127-bit GLV half / the 255-bit scalar
@@ -698,10 +716,10 @@ __global__ void __launch_bounds__(64, SNARKV_ACC_WAVES)
 #pragma unroll 1
   for (uint32_t e = 1; e < trip; e += 2) {
     fetch(e + 1, ent0, p0);
-    if (e < len) xyzz29_madd_fast(acc, entry_point(p1, ent1.y));
+    if (e < len) PipFast::xyzz29_madd_fast(acc, entry_point(p1, ent1.y));
     if (e + 1 < trip) {
       fetch(e + 2, ent1, p1);
-      if (e + 1 < len) xyzz29_madd_fast(acc, entry_point(p0, ent0.y));
+      if (e + 1 < len) PipFast::xyzz29_madd_fast(acc, entry_point(p0, ent0.y));
     }
   }
   if (!valid) return;
@@ -798,7 +816,7 @@ __global__ void __launch_bounds__(256)
       for (uint32_t j = 0; j < np; ++j) {
         const G1Xyzz29 part = parts[piece_slot(o, j, nfull, L, split_slots)];
         bad = bad || xyzz29_is_identity(part);
-        xyzz29_add_skipid_fast(acc, part, bad);
+        PipFast::xyzz29_add_skipid_fast(acc, part, bad);
       }
       bad = bad || xyzz29_is_degenerate(acc);
     }
@@ -846,7 +864,7 @@ __device__ __forceinline__ bool chunk_sums(const G1Xyzz29* __restrict__ bw, uint
     G1Xyzz29 x = second ? acc : run;
     G1Xyzz29 y = second ? run : bw[top - 1 - (op >> 1)];
     if (CAREFUL) xyzz29_add_careful(x, y);
-    else xyzz29_add_skipid_fast(x, y, bad);
+    else PipFast::xyzz29_add_skipid_fast(x, y, bad);
     if (second) acc = x;
     else run = x;
   }
