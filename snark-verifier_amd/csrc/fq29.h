@@ -41,7 +41,7 @@
 // (tests/hosttest).
 #pragma once
 #include <stdint.h>
-#include "fq.h"
+#include "mont29.h"
 
 namespace snarkv {
 
@@ -49,42 +49,19 @@ struct Fq29 {
   int32_t v[9];
 };
 
-constexpr int32_t kMask29 = (1 << 29) - 1;
-
-// radix-2^29 constants (SNARKV_FQ29_P_LIMBS, SNARKV_FQ29_NINV, SNARKV_FQ29_ONE_LIMBS,
-// SNARKV_FQ29_R2_LIMBS) come from bn254_consts.h (gen_consts.py).
-
-SNARKV_HD constexpr int32_t fq29_p(int i) {
-  constexpr int32_t p[9] = SNARKV_FQ29_P_LIMBS;
-  return p[i];
-}
-
-// The Montgomery-friendly multiple of p used by the `_fm` products below: M = NINV * p = -1 (mod 2^29), ten limbs with
-// limb 0 = 2^29 - 1 and limb 1 stored ALREADY INCREMENTED (SNARKV_FQ29_FM_LIMBS, gen_consts.py).  The first kFq29FmSteps of
-// the nine reduction steps add a multiple of M, the last two a multiple of p.  Seven, not eight: with eight the excess
-// over a*b/2^261 reaches 1.14 p (exact-integer model), with seven it stays below (1 + 2^-29) p.
+// The limb-wise operations, the product scanning loop, its two reductions and the canonical tail are stated once, in
+// mont29.h, over the element type and the modulus (Mod29Fq: SNARKV_FQ29_P_LIMBS, SNARKV_FQ29_NINV, SNARKV_FQ29_ONE_LIMBS,
+// SNARKV_FQ29_FM_LIMBS from bn254_consts.h / pallas_consts.h, gen_consts.py); the names below are what callers, the
+// generated asm bodies and the tests know.
+SNARKV_HD constexpr int32_t fq29_p(int i) { return Mod29Fq::p(i); }
+// The Montgomery-friendly multiple of p used by the `_fm` products below: M = NINV * p = -1 (mod 2^29).  The first
+// kFq29FmSteps of the nine reduction steps add a multiple of M, the last two a multiple of p.  Seven, not eight: with eight
+// the excess over a*b/2^261 reaches 1.14 p (exact-integer model), with seven it stays below (1 + 2^-29) p.
+SNARKV_HD constexpr int32_t fq29_fm(int i) { return Mod29Fq::fm(i); }
 constexpr int kFq29FmSteps = 7;
 
-SNARKV_HD constexpr int32_t fq29_fm(int i) {
-  constexpr int32_t m[10] = SNARKV_FQ29_FM_LIMBS;
-  return m[i];
-}
-static_assert(fq29_fm(0) == kMask29, "limb 0 of the friendly multiple must be 2^29 - 1: the digit is the column's low bits");
-
-SNARKV_HD Fq29 fq29_zero() {
-  Fq29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.v[i] = 0;
-  return r;
-}
-
-SNARKV_HD Fq29 fq29_one() {
-  constexpr int32_t c[9] = SNARKV_FQ29_ONE_LIMBS;
-  Fq29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.v[i] = c[i];
-  return r;
-}
+SNARKV_HD Fq29 fq29_zero() { return mont29_zero<Fq29>(); }
+SNARKV_HD Fq29 fq29_one() { return mont29_one<Mod29Fq, Fq29>(); }
 
 // exact all-limbs-zero test (the stored identity marker), NOT a mod-p test
 SNARKV_HD bool fq29_limbs_all_zero(const Fq29& a) {
@@ -94,26 +71,9 @@ SNARKV_HD bool fq29_limbs_all_zero(const Fq29& a) {
   return acc == 0;
 }
 
-SNARKV_HD Fq29 fq29_add(const Fq29& a, const Fq29& b) {
-  Fq29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.v[i] = a.v[i] + b.v[i];
-  return r;
-}
-
-SNARKV_HD Fq29 fq29_sub(const Fq29& a, const Fq29& b) {
-  Fq29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.v[i] = a.v[i] - b.v[i];
-  return r;
-}
-
-SNARKV_HD Fq29 fq29_neg(const Fq29& a) {
-  Fq29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.v[i] = -a.v[i];
-  return r;
-}
+SNARKV_HD Fq29 fq29_add(const Fq29& a, const Fq29& b) { return mont29_add(a, b); }
+SNARKV_HD Fq29 fq29_sub(const Fq29& a, const Fq29& b) { return mont29_sub(a, b); }
+SNARKV_HD Fq29 fq29_neg(const Fq29& a) { return mont29_neg(a); }
 
 SNARKV_HD Fq29 fq29_dbl(const Fq29& a) {
   Fq29 r;
@@ -123,18 +83,7 @@ SNARKV_HD Fq29 fq29_dbl(const Fq29& a) {
 }
 
 // carry-normalise: limbs 0..7 -> [0, 2^29), limb 8 keeps sign; value unchanged
-SNARKV_HD Fq29 fq29_norm(const Fq29& a) {
-  Fq29 r;
-  int32_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    int32_t t = a.v[i] + c;
-    r.v[i] = t & kMask29;
-    c = t >> 29;  // arithmetic
-  }
-  r.v[8] = a.v[8] + c;
-  return r;
-}
+SNARKV_HD Fq29 fq29_norm(const Fq29& a) { return mont29_norm(a); }
 
 // How the products are issued on the device.  The compiler, knowing that masked limbs are non-negative,
 // turns a mixed-sign 32x32+64 product into `v_mad_u64_u32` plus a sign fix-up (shift, move, subtract) and
@@ -146,18 +95,10 @@ SNARKV_HD Fq29 fq29_norm(const Fq29& a) {
 // entry of k_accumulate.  Stepping stones (rounds 1-2, measured): one asm statement per operand product
 // (-12 %), one statement per product of either kind (slower again: the compiler pads consecutive
 // VCC-writing asm statements with s_nop), one statement per column (this form).
-// -DSNARKV_NO_SMAD_ASM keeps the plain C below (host builds always use it).  The pairing (decider.hip), a few
+// -DSNARKV_NO_SMAD_ASM keeps the plain C of mont29_product (host builds always use it).  The pairing (decider.hip), a few
 // latency-bound wavefronts, lost 3 % to the one-statement-per-product form but gains 2-3 % from the column
 // chains (decide 0.887 -> 0.866 ms, 1 024 accumulators 1.51 -> 1.46 ms); Poseidon's Fr products stay plain C.
-SNARKV_HD int64_t fq29_smad(int32_t a, int32_t b, int64_t acc) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(SNARKV_NO_SMAD_ASM)
-  asm("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "vcc");
-  return acc;
-#else
-  return acc + (int64_t)a * b;
-#endif
-}
-
+//
 // Montgomery product a*b*2^-261 (mod p), column-wise (product scanning) with a
 // single 64-bit accumulator: 81 + 81 `v_mad_i64_i32`, 17 64-bit shifts, 9
 // `v_mul_lo_u32`, 18 masks.
@@ -165,30 +106,7 @@ SNARKV_HD Fq29 fq29_mul(const Fq29& a, const Fq29& b) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(SNARKV_NO_SMAD_ASM)
 #include "fq29_mul_asm.inc"  // every column one chain of v_mad_i64_i32 (gen_fq29_mul_asm.py)
 #else
-  int32_t m[9];
-  Fq29 r;
-  int64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int i = 0; i <= k; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
-#pragma unroll
-    for (int i = 0; i < k; ++i) acc += (int64_t)m[i] * fq29_p(k - i);
-    m[k] = (int32_t)(((uint32_t)acc * (uint32_t)SNARKV_FQ29_NINV) & (uint32_t)kMask29);
-    acc += (int64_t)m[k] * fq29_p(0);
-    acc >>= 29;  // low 29 bits are zero
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc += (int64_t)m[i] * fq29_p(k - i);
-    r.v[k - 9] = (int32_t)acc & kMask29;
-    acc >>= 29;
-  }
-  r.v[8] = (int32_t)acc;
-  return r;
+  return mont29_product<Mod29Fq, kMont29Mul, 0>(a, b, a, a);  // mul has no c, d: any element, never read
 #endif
 }
 
@@ -200,34 +118,7 @@ SNARKV_HD Fq29 fq29_mul2(const Fq29& a, const Fq29& b, const Fq29& c, const Fq29
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(SNARKV_NO_SMAD_ASM)
 #include "fq29_mul2_asm.inc"
 #else
-  int32_t m[9];
-  Fq29 r;
-  int64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int i = 0; i <= k; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
-#pragma unroll
-    for (int i = 0; i <= k; ++i) acc = fq29_smad(c.v[i], d.v[k - i], acc);
-#pragma unroll
-    for (int i = 0; i < k; ++i) acc += (int64_t)m[i] * fq29_p(k - i);
-    m[k] = (int32_t)(((uint32_t)acc * (uint32_t)SNARKV_FQ29_NINV) & (uint32_t)kMask29);
-    acc += (int64_t)m[k] * fq29_p(0);
-    acc >>= 29;
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc = fq29_smad(c.v[i], d.v[k - i], acc);
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc += (int64_t)m[i] * fq29_p(k - i);
-    r.v[k - 9] = (int32_t)acc & kMask29;
-    acc >>= 29;
-  }
-  r.v[8] = (int32_t)acc;
-  return r;
+  return mont29_product<Mod29Fq, kMont29Mul2, 0>(a, b, c, d);
 #endif
 }
 
@@ -236,34 +127,7 @@ SNARKV_HD Fq29 fq29_sqr(const Fq29& a) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(SNARKV_NO_SMAD_ASM)
 #include "fq29_sqr_asm.inc"
 #else
-  int32_t m[9], a2[9];
-  Fq29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) a2[i] = a.v[i] * 2;
-  int64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int i = 0; 2 * i < k; ++i) acc = fq29_smad(a2[i], a.v[k - i], acc);
-    if ((k & 1) == 0) acc = fq29_smad(a.v[k / 2], a.v[k / 2], acc);
-#pragma unroll
-    for (int i = 0; i < k; ++i) acc += (int64_t)m[i] * fq29_p(k - i);
-    m[k] = (int32_t)(((uint32_t)acc * (uint32_t)SNARKV_FQ29_NINV) & (uint32_t)kMask29);
-    acc += (int64_t)m[k] * fq29_p(0);
-    acc >>= 29;
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int i = k - 8; 2 * i < k; ++i) acc = fq29_smad(a2[i], a.v[k - i], acc);
-    if ((k & 1) == 0) acc = fq29_smad(a.v[k / 2], a.v[k / 2], acc);
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc += (int64_t)m[i] * fq29_p(k - i);
-    r.v[k - 9] = (int32_t)acc & kMask29;
-    acc >>= 29;
-  }
-  r.v[8] = (int32_t)acc;
-  return r;
+  return mont29_product<Mod29Fq, kMont29Sqr, 0>(a, a, a, a);
 #endif
 }
 
@@ -282,55 +146,11 @@ SNARKV_HD Fq29 fq29_sqr(const Fq29& a) {
 // their interval argument); canonicalisation, the careful adders and everything outside the Pippenger keep the pinned ones.
 // On pallas p_0 = 1 and three limbs of p are zero where only two of M are: the `_fm` form is one multiply-add per step
 // MORE there, so the pasta build's Pippenger does not select it (SNARKV_FQ29_FM, msm_pippenger.hip).
-
-// reduction products of column k: digit i against M (i < kFq29FmSteps) or against p
-SNARKV_HD int64_t fq29_fm_column(int k, const int32_t m[9], int64_t acc) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    if (i >= k) continue;
-    if (i < kFq29FmSteps) {
-      if (k - i <= 9) acc += (int64_t)m[i] * fq29_fm(k - i);
-    } else if (k - i <= 8) {
-      acc += (int64_t)m[i] * fq29_p(k - i);
-    }
-  }
-  return acc;
-}
-
-// digit of column k < 9, and the column's carry
-SNARKV_HD int64_t fq29_fm_digit(int k, int32_t m[9], int64_t acc) {
-  if (k < kFq29FmSteps) {
-    m[k] = (int32_t)acc & kMask29;  // acc + m[k] (2^29 - 1) = (acc >> 29) 2^29 + m[k] 2^29: the + m[k] is in fq29_fm(1)
-  } else {
-    m[k] = (int32_t)(((uint32_t)acc * (uint32_t)SNARKV_FQ29_NINV) & (uint32_t)kMask29);
-    acc += (int64_t)m[k] * fq29_p(0);
-  }
-  return acc >> 29;
-}
-
 SNARKV_HD Fq29 fq29_mul_fm(const Fq29& a, const Fq29& b) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(SNARKV_NO_SMAD_ASM)
 #include "fq29_mul_fm_asm.inc"
 #else
-  int32_t m[9];
-  Fq29 r;
-  int64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int i = 0; i <= k; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
-    acc = fq29_fm_digit(k, m, fq29_fm_column(k, m, acc));
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
-    acc = fq29_fm_column(k, m, acc);
-    r.v[k - 9] = (int32_t)acc & kMask29;
-    acc >>= 29;
-  }
-  r.v[8] = (int32_t)acc;
-  return r;
+  return mont29_product<Mod29Fq, kMont29Mul, kFq29FmSteps>(a, b, a, a);
 #endif
 }
 
@@ -338,29 +158,7 @@ SNARKV_HD Fq29 fq29_mul2_fm(const Fq29& a, const Fq29& b, const Fq29& c, const F
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(SNARKV_NO_SMAD_ASM)
 #include "fq29_mul2_fm_asm.inc"
 #else
-  int32_t m[9];
-  Fq29 r;
-  int64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int i = 0; i <= k; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
-#pragma unroll
-    for (int i = 0; i <= k; ++i) acc = fq29_smad(c.v[i], d.v[k - i], acc);
-    acc = fq29_fm_digit(k, m, fq29_fm_column(k, m, acc));
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc = fq29_smad(a.v[i], b.v[k - i], acc);
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc = fq29_smad(c.v[i], d.v[k - i], acc);
-    acc = fq29_fm_column(k, m, acc);
-    r.v[k - 9] = (int32_t)acc & kMask29;
-    acc >>= 29;
-  }
-  r.v[8] = (int32_t)acc;
-  return r;
+  return mont29_product<Mod29Fq, kMont29Mul2, kFq29FmSteps>(a, b, c, d);
 #endif
 }
 
@@ -368,29 +166,7 @@ SNARKV_HD Fq29 fq29_sqr_fm(const Fq29& a) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(SNARKV_NO_SMAD_ASM)
 #include "fq29_sqr_fm_asm.inc"
 #else
-  int32_t m[9], a2[9];
-  Fq29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) a2[i] = a.v[i] * 2;
-  int64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int i = 0; 2 * i < k; ++i) acc = fq29_smad(a2[i], a.v[k - i], acc);
-    if ((k & 1) == 0) acc = fq29_smad(a.v[k / 2], a.v[k / 2], acc);
-    acc = fq29_fm_digit(k, m, fq29_fm_column(k, m, acc));
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int i = k - 8; 2 * i < k; ++i) acc = fq29_smad(a2[i], a.v[k - i], acc);
-    if ((k & 1) == 0) acc = fq29_smad(a.v[k / 2], a.v[k / 2], acc);
-    acc = fq29_fm_column(k, m, acc);
-    r.v[k - 9] = (int32_t)acc & kMask29;
-    acc >>= 29;
-  }
-  r.v[8] = (int32_t)acc;
-  return r;
+  return mont29_product<Mod29Fq, kMont29Sqr, kFq29FmSteps>(a, a, a, a);
 #endif
 }
 
@@ -411,31 +187,9 @@ struct Fq29Fm {
 // instructions per bucket addition, one MSM alone level, four in flight 1-5 % slower: profiles/r02_ab_pairs.txt, git tag
 // exp/madd-pairs.)
 
-// Unique representative in [0, p), carry-normalised.
-// canonical limbs of a value y in (-p, 2p) whose limbs 0..7 are already in [0, 2^29) -- in particular any OUTPUT of
-// fq29_mul / fq29_mul2 / fq29_sqr of operands within (-8p, 8p) (value in (-p/2, 3p/2)): one conditional +p, one
-// conditional -p, no product
-SNARKV_HD Fq29 fq29_canon_of_product(const Fq29& y) {
-  Fq29 t;
-  int32_t neg = y.v[8] >> 31;  // all ones if negative
-#pragma unroll
-  for (int i = 0; i < 9; ++i) t.v[i] = y.v[i] + (fq29_p(i) & neg);
-  t = fq29_norm(t);
-  // subtract p if t >= p
-  Fq29 d;
-  int32_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    int32_t s = t.v[i] - fq29_p(i) + c;
-    d.v[i] = s & kMask29;
-    c = s >> 29;
-  }
-  d.v[8] = t.v[8] - fq29_p(8) + c;
-  int32_t keep = d.v[8] >> 31;  // negative -> t < p -> keep t
-#pragma unroll
-  for (int i = 0; i < 9; ++i) t.v[i] = (t.v[i] & keep) | (d.v[i] & ~keep);
-  return t;
-}
+// Unique representative in [0, p), carry-normalised, of a value y in (-p, 2p) whose limbs 0..7 are already in [0, 2^29) --
+// in particular any OUTPUT of fq29_mul / fq29_mul2 / fq29_sqr of operands within (-8p, 8p) (value in (-p/2, 3p/2))
+SNARKV_HD Fq29 fq29_canon_of_product(const Fq29& y) { return mont29_canon_of_product<Mod29Fq>(y); }
 
 // canonical limbs of ANY lazy value (the contract's (-8p, 8p)): one Montgomery product by 2^261 (i.e. by `one`) squeezes
 // the value into (-p/16, p + p/16) without changing the residue (x * R * R^-1), then at most one +p and one -p
@@ -446,18 +200,7 @@ SNARKV_HD bool fq29_is_zero_mod_p(const Fq29& x) { return fq29_limbs_all_zero(fq
 // boundary codecs: 8 x u32 words <-> Montgomery (R = 2^261) limbs.  The words are the canonical integer a < p
 // (`PrimeField::to_repr`, the wire form) or, with `mont`, halo2curves' IN-MEMORY form: the four u64 limbs of
 // a * 2^256 mod p.  Either way ONE product by a constant: 2^522 / 2^266 on the way in, 1 / 2^256 on the way out.
-SNARKV_HD Fq29 fq29_limbs_of_words(const uint32_t w[8]) {
-  Fq29 a;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    int bit = 29 * i;
-    int word = bit >> 5, sh = bit & 31;
-    uint64_t v = w[word];
-    if (word + 1 < 8) v |= (uint64_t)w[word + 1] << 32;
-    a.v[i] = (int32_t)((uint32_t)(v >> sh) & (uint32_t)kMask29);
-  }
-  return a;
-}
+SNARKV_HD Fq29 fq29_limbs_of_words(const uint32_t w[8]) { return mont29_limbs_of_words<Fq29>(w); }
 SNARKV_HD Fq29 fq29_from_words(const uint32_t w[8], bool mont) {
   constexpr int32_t r2[9] = SNARKV_FQ29_R2_LIMBS;
   constexpr int32_t m_in[9] = SNARKV_FQ29_M256_IN_LIMBS;
@@ -473,35 +216,8 @@ SNARKV_HD void fq29_to_words(const Fq29& a, uint32_t w[8], bool mont) {
   Fq29 mult;
 #pragma unroll
   for (int i = 0; i < 9; ++i) mult.v[i] = mont ? m_out[i] : (i == 0 ? 1 : 0);
-  Fq29 y = fq29_mul(fq29_norm(a), mult);  // a * R^-1 [* 2^256]: out of the 2^261 domain
-  // canonicalise the residue
-  Fq29 t;
-  int32_t neg = y.v[8] >> 31;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) t.v[i] = y.v[i] + (fq29_p(i) & neg);
-  t = fq29_norm(t);
-  Fq29 d;
-  int32_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    int32_t s = t.v[i] - fq29_p(i) + c;
-    d.v[i] = s & kMask29;
-    c = s >> 29;
-  }
-  d.v[8] = t.v[8] - fq29_p(8) + c;
-  int32_t keep = d.v[8] >> 31;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) t.v[i] = (t.v[i] & keep) | (d.v[i] & ~keep);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) w[j] = 0;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    int bit = 29 * i;
-    int word = bit >> 5, sh = bit & 31;
-    uint64_t v = (uint64_t)(uint32_t)t.v[i] << sh;
-    w[word] |= (uint32_t)v;
-    if (word + 1 < 8) w[word + 1] |= (uint32_t)(v >> 32);
-  }
+  // a * R^-1 [* 2^256]: out of the 2^261 domain
+  mont29_words_of_limbs(fq29_canon_of_product(fq29_mul(fq29_norm(a), mult)), w);
 }
 SNARKV_HD void fq29_to_canonical(const Fq29& a, uint32_t w[8]) { fq29_to_words(a, w, false); }
 

@@ -68,18 +68,7 @@ SNARKV_HD void fq29_pack256(const Fq29& a, uint32_t w[8]) {  // a: canonical res
   }
 }
 
-SNARKV_HD Fq29 fq29_unpack256(const uint32_t w[8]) {
-  Fq29 a;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    int bit = 29 * i;
-    int word = bit >> 5, sh = bit & 31;
-    uint64_t v = w[word];
-    if (word + 1 < 8) v |= (uint64_t)w[word + 1] << 32;
-    a.v[i] = (int32_t)((uint32_t)(v >> sh) & (uint32_t)kMask29);
-  }
-  return a;
-}
+SNARKV_HD Fq29 fq29_unpack256(const uint32_t w[8]) { return fq29_limbs_of_words(w); }
 
 SNARKV_HD G1Packed g1a29_pack(const G1Affine29& p) {
   G1Packed r;

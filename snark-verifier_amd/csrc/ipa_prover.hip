@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(256) k_ipa_powers(const uint32_t* __restrict__
 // xi_pair[8..16) = xi_pair[0..8)^(r-2), on one lane (254 squarings)
 __global__ void k_ipa_xi_inv(uint32_t* __restrict__ xi_pair) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  st_fr(xi_pair + 8, fr_inv(ld_fr(xi_pair)));
+  fr_inv_store(xi_pair + 8, fr_inv(ld_fr(xi_pair)));
 }
 
 // coeffs[j] += xi^-1 coeffs[half + j],  zs[j] += xi zs[half + j]   (in place: lane j alone reads half+j and writes j)

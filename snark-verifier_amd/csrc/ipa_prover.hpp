@@ -24,6 +24,74 @@ __device__ __forceinline__ void st_fr(uint32_t* __restrict__ p, const Fr29& v) {
 }
 // a + b brought back to (-r/8, 9r/8) (one Montgomery product by 1), so sums of any length stay in fr29_mul's range
 __device__ __forceinline__ Fr29 fr_add_red(const Fr29& a, const Fr29& b) { return fr29_mul(fr29_add(a, b), fr29_one()); }
+// ---- fr29_mul and fr29_to_canonical with their loops spelled out, for the one-lane inversion k_ipa_xi_inv alone.  That
+// kernel is wave-uniform, a serial chain of 380 products on the scalar unit, once per round of the prover.  Through
+// mont29_product and the shared tail its loop body compiled 3 % longer on pallas (1 143 -> 1 177 instructions per exponent
+// bit; the two together, either one alone changes nothing), and the prover's fold phase at k = 16 measured 14.49 -> 14.76 ms,
+// slower in every round with disjoint ranges (profiles/r09_field_layer_refactor.txt).  With these two bodies the loop is
+// instruction for instruction what it was.  Same column schedule, same limbs as fr29_mul; same words as fr29_to_canonical.
+__device__ __forceinline__ Fr29 fr_inv_mul(const Fr29& a, const Fr29& b) {
+  int32_t m[9];
+  Fr29 r;
+  int64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+#pragma unroll
+    for (int i = 0; i <= k; ++i) acc += (int64_t)a.v[i] * b.v[k - i];
+#pragma unroll
+    for (int i = 0; i < k; ++i) acc += (int64_t)m[i] * fr29_r(k - i);
+    m[k] = (int32_t)(((uint32_t)acc * (uint32_t)SNARKV_FR29_NINV) & (uint32_t)kMask29);
+    acc += (int64_t)m[k] * fr29_r(0);
+    acc >>= 29;
+  }
+#pragma unroll
+  for (int k = 9; k < 17; ++k) {
+#pragma unroll
+    for (int i = k - 8; i < 9; ++i) acc += (int64_t)a.v[i] * b.v[k - i];
+#pragma unroll
+    for (int i = k - 8; i < 9; ++i) acc += (int64_t)m[i] * fr29_r(k - i);
+    r.v[k - 9] = (int32_t)acc & kMask29;
+    acc >>= 29;
+  }
+  r.v[8] = (int32_t)acc;
+  return r;
+}
+__device__ __forceinline__ void fr_inv_store(uint32_t* __restrict__ p, const Fr29& a) {
+  Fr29 one_raw = fr29_zero();
+  one_raw.v[0] = 1;
+  Fr29 y = fr_inv_mul(fr29_norm(a), one_raw);  // a * R^-1
+  Fr29 t;
+  int32_t neg = y.v[8] >> 31;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) t.v[i] = y.v[i] + (fr29_r(i) & neg);
+  t = fr29_norm(t);
+  Fr29 d;
+  int32_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    int32_t s = t.v[i] - fr29_r(i) + c;
+    d.v[i] = s & kMask29;
+    c = s >> 29;
+  }
+  d.v[8] = t.v[8] - fr29_r(8) + c;
+  int32_t keep = d.v[8] >> 31;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) t.v[i] = (t.v[i] & keep) | (d.v[i] & ~keep);
+  uint32_t w[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) w[j] = 0;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    int bit = 29 * i;
+    int word = bit >> 5, sh = bit & 31;
+    uint64_t v = (uint64_t)(uint32_t)t.v[i] << sh;
+    w[word] |= (uint32_t)v;
+    if (word + 1 < 8) w[word + 1] |= (uint32_t)(v >> 32);
+  }
+  uint4* o = reinterpret_cast<uint4*>(p);
+  o[0] = make_uint4(w[0], w[1], w[2], w[3]);
+  o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
 // x^(r-2): 254 squarings on the calling lane; 0 -> 0
 __device__ __forceinline__ Fr29 fr_inv(const Fr29& x) {
   constexpr uint32_t rw[8] = SNARKV_FR_R_LIMBS;
@@ -37,8 +105,8 @@ __device__ __forceinline__ Fr29 fr_inv(const Fr29& x) {
   Fr29 acc = fr29_one();
 #pragma unroll 1
   for (int b = 255; b >= 0; --b) {
-    acc = fr29_mul(acc, acc);
-    if ((e[b >> 5] >> (b & 31)) & 1u) acc = fr29_mul(acc, x);
+    acc = fr_inv_mul(acc, acc);
+    if ((e[b >> 5] >> (b & 31)) & 1u) acc = fr_inv_mul(acc, x);
   }
   return acc;
 }

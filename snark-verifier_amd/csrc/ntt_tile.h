@@ -29,40 +29,14 @@ constexpr uint32_t kNttReduceEvery = 6;
 constexpr double kNttBound = 7.5;  // |multiplier input| / r stays below this
 SNARKV_HD bool ntt_reduce_after(uint32_t level) { return level % kNttReduceEvery == kNttReduceEvery - 1; }
 
-SNARKV_HD Fr29 fr29_sub(const Fr29& a, const Fr29& b) {
-  Fr29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.v[i] = a.v[i] - b.v[i];
-  return r;
-}
-SNARKV_HD Fr29 fr29_limbs(const int32_t (&l)[9]) {
-  Fr29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.v[i] = l[i];
-  return r;
-}
 // the constant factors: 2^522 mod r (words in -> Montgomery domain) and the integer 1 (Montgomery domain -> words out)
 SNARKV_HD Fr29 ntt_factor_in() {
   constexpr int32_t r2[9] = SNARKV_FR29_R2_LIMBS;
   return fr29_limbs(r2);
 }
-SNARKV_HD Fr29 ntt_factor_out() {
-  Fr29 one_raw = fr29_zero();
-  one_raw.v[0] = 1;
-  return one_raw;
-}
+SNARKV_HD Fr29 ntt_factor_out() { return fr29_small(1); }
 // the 9 x 29-bit limbs of 8 words as they stand
-SNARKV_HD Fr29 ntt_raw_limbs(const uint32_t w[8]) {
-  Fr29 a;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const int bit = 29 * i, word = bit >> 5, sh = bit & 31;
-    uint64_t v = w[word];
-    if (word + 1 < 8) v |= (uint64_t)w[word + 1] << 32;
-    a.v[i] = (int32_t)((uint32_t)(v >> sh) & (uint32_t)kMask29);
-  }
-  return a;
-}
+SNARKV_HD Fr29 ntt_raw_limbs(const uint32_t w[8]) { return fr29_limbs_of_words(w); }
 
 // words in: x f, with f = 2^522 f' the wanted factor f' twice in the Montgomery domain (ntt_factor_in() for f' = 1)
 SNARKV_HD Fr29 ntt_load(const uint32_t w[8], const Fr29& f) { return fr29_mul(ntt_raw_limbs(w), f); }
@@ -72,33 +46,7 @@ SNARKV_HD Fr29 ntt_load(const uint32_t w[8], const Fr29& f) { return fr29_mul(nt
 SNARKV_HD void ntt_store(const Fr29& a, const Fr29& f, uint32_t w[8]) {
   const Fr29 an = fr29_norm(a);
   SNARKV_NTT_PROBE(an);
-  const Fr29 y = fr29_mul(an, f);
-  Fr29 t;
-  const int32_t neg = y.v[8] >> 31;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) t.v[i] = y.v[i] + (fr29_r(i) & neg);
-  t = fr29_norm(t);
-  Fr29 d;
-  int32_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int32_t s = t.v[i] - fr29_r(i) + c;
-    d.v[i] = s & kMask29;
-    c = s >> 29;
-  }
-  d.v[8] = t.v[8] - fr29_r(8) + c;
-  const int32_t keep = d.v[8] >> 31;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) t.v[i] = (t.v[i] & keep) | (d.v[i] & ~keep);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) w[j] = 0;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const int bit = 29 * i, word = bit >> 5, sh = bit & 31;
-    const uint64_t v = (uint64_t)(uint32_t)t.v[i] << sh;
-    w[word] |= (uint32_t)v;
-    if (word + 1 < 8) w[word + 1] |= (uint32_t)(v >> 32);
-  }
+  fr29_words_of_product(an, f, w);
 }
 
 // one butterfly of level `level`, in place: the pairs of a level are disjoint

@@ -82,15 +82,7 @@ __device__ __forceinline__ Fr29 ld_raw(const uint32_t* __restrict__ p) {
   const uint4* s = reinterpret_cast<const uint4*>(p);
   const uint4 a = s[0], b = s[1];
   const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  Fr29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const int bit = 29 * i, word = bit >> 5, sh = bit & 31;
-    uint64_t v = w[word];
-    if (word + 1 < 8) v |= (uint64_t)w[word + 1] << 32;
-    r.v[i] = (int32_t)((uint32_t)(v >> sh) & (uint32_t)kMask29);
-  }
-  return r;
+  return fr29_limbs_of_words(w);
 }
 
 // out[i] (+)= sum_{j < count} scalars[j] polys[idx[j]][i], count <= kPolyLincombTerms.  The scalars go to LDS as s R^2, so

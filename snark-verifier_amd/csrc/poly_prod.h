@@ -152,17 +152,7 @@ SNARKV_HD Fr29 prod_inv(const Fr29& x) {
 }
 
 // the 9 x 29-bit limbs of 8 words as they stand, not in the Montgomery domain: the integer itself, < 2^256 < 8r, normalised
-SNARKV_HD Fr29 prod_raw(const uint32_t w[8]) {
-  Fr29 r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const int bit = 29 * i, word = bit >> 5, sh = bit & 31;
-    uint64_t v = w[word];
-    if (word + 1 < 8) v |= (uint64_t)w[word + 1] << 32;
-    r.v[i] = (int32_t)((uint32_t)(v >> sh) & (uint32_t)kMask29);
-  }
-  return r;
-}
+SNARKV_HD Fr29 prod_raw(const uint32_t w[8]) { return fr29_limbs_of_words(w); }
 // s -> s R^2 in the Montgomery domain: its product with raw limbs is the Montgomery form of the product
 SNARKV_HD Fr29 prod_scalar_for_raw(const Fr29& s) {
   constexpr int32_t r2[9] = SNARKV_FR29_R2_LIMBS;

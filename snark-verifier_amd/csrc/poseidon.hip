@@ -34,38 +34,6 @@ struct snarkv_poseidon {
 
 namespace snarkv {
 
-// a*b + c*d, one reduction (inputs carry-normalised, |limb| < 2^29): the MDS dot products
-__device__ __forceinline__ Fr29 fr29_mul2(const Fr29& a, const Fr29& b, const Fr29& c, const Fr29& d) {
-  int32_t m[9];
-  Fr29 r;
-  int64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-#pragma unroll
-    for (int i = 0; i <= k; ++i) acc += (int64_t)a.v[i] * b.v[k - i];
-#pragma unroll
-    for (int i = 0; i <= k; ++i) acc += (int64_t)c.v[i] * d.v[k - i];
-#pragma unroll
-    for (int i = 0; i < k; ++i) acc += (int64_t)m[i] * fr29_r(k - i);
-    m[k] = (int32_t)(((uint32_t)acc * (uint32_t)BN254_FR29_NINV) & (uint32_t)kMask29);
-    acc += (int64_t)m[k] * fr29_r(0);
-    acc >>= 29;
-  }
-#pragma unroll
-  for (int k = 9; k < 17; ++k) {
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc += (int64_t)a.v[i] * b.v[k - i];
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc += (int64_t)c.v[i] * d.v[k - i];
-#pragma unroll
-    for (int i = k - 8; i < 9; ++i) acc += (int64_t)m[i] * fr29_r(k - i);
-    r.v[k - 9] = (int32_t)acc & kMask29;
-    acc >>= 29;
-  }
-  r.v[8] = (int32_t)acc;
-  return r;
-}
-
 __global__ void k_poseidon_tables(const uint32_t* __restrict__ canon, Fr29* __restrict__ out, uint32_t n) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

@@ -37,7 +37,8 @@ OPS = {
     "fq29_mul": (18, 9), "fq29_sqr": (9, 9), "fq29_mul2": (36, 9), "fq29_norm": (9, 9), "fq29_canon_of_product": (9, 9),
     "fq29_canon_residue": (9, 9), "fq29_is_zero_mod_p": (9, 1), "fq29_from_words": (8, 9), "fq29_from_words_mont": (8, 9),
     "fq29_to_words": (9, 8), "fq29_to_words_mont": (9, 8), "fq29_pack256": (9, 8), "fq29_unpack256": (8, 9),
-    "fr29_mul": (18, 9), "fr29_pow5": (9, 9), "fr29_canon_residue": (9, 9), "fq_mul": (16, 8),
+    "fr29_mul": (18, 9), "fr29_mul2": (36, 9), "fr29_from_canonical": (8, 9), "fr29_to_canonical": (9, 8),
+    "fr29_pow5": (9, 9), "fr29_canon_residue": (9, 9), "fq_mul": (16, 8),
     "xyzz29_madd_fast": (54, 36), "xyzz29_add_fast": (72, 36), "xyzz29_madd_careful": (54, 36),
     "xyzz29_add_careful": (72, 36), "xyzz29_add_skipid_fast": (73, 37), "xyzz29_double": (36, 36),
     "jac29_double": (28, 27), "xyzz29_double_n": (37, 36), "jac29_to_xyzz": (27, 36), "xyzz29_is_degenerate": (36, 1),
@@ -568,6 +569,16 @@ def field_cases(C, n=50000):
     cases["fq29_unpack256"] = cases["fq29_from_words"]
     rn, rw, rm, rm2 = _pool(Fr, 11, n, "norm"), _pool(Fr, 12, n, "wide"), _pool(Fr, 13, n, "mid"), _pool(Fr, 14, n, "mid")
     cases["fr29_mul"] = np.concatenate([np.concatenate([rn[:h], rm[h:]]), np.concatenate([rw[:h], rm2[h:]])], axis=1)
+    # a b + c d at the corner of its budget, 27 products per column: every operand carry-normalised or the limb-wise negation
+    # of that, in all sixteen sign patterns; the pools open with limbs 0..7 all at 2^29 - 1, so the first sixteen records are
+    # that corner in every pattern
+    sign = np.array([[1 - 2 * ((i >> j) & 1) for j in range(4)] for i in range(16)], dtype=np.int32)[np.arange(n) % 16]
+    cases["fr29_mul2"] = np.concatenate([_pool(Fr, s, n, "norm") * sign[:, j:j + 1] for j, s in enumerate((11, 16, 17, 19))],
+                                        axis=1)
+    assert (np.abs(cases["fr29_mul2"][:16].reshape(-1, 9)[:, :8]) == MASK).all(), "the corner of the fr29_mul2 budget is missing"
+    # the codecs: 0, 1, r - 1 and uniform residues in; out, every k r and k r +- 1 up to the +-8r of the lazy contract
+    cases["fr29_from_canonical"] = np.array([words_i32(v) for v in _residues(Fr, random.Random(2930), n)], dtype=np.int32)
+    cases["fr29_to_canonical"] = np.concatenate([kp_spellings(Fr, 18), rm[:h], rw[h:]])[:n]
     cases["fr29_pow5"] = rm
     cases["fr29_canon_residue"] = np.concatenate([kp_spellings(Fr, 15), rw])[:n]
     # 8 x 32: all-ones clipped below p, p - 1, single bits, random
@@ -586,6 +597,7 @@ def field_cases(C, n=50000):
     A, B = cases["fr29_mul"][:, :9], cases["fr29_mul"][:, 9:]
     assert budget_mask(Fr, A, B).all()
     assert (np.abs(cases["fq29_mul2"].astype(np.int64)) < (1 << 29)).all()
+    assert (np.abs(cases["fr29_mul2"].astype(np.int64)) < (1 << 29)).all()
     for name, arr in cases.items():
         assert arr.shape[1] == OPS[name][0] and len(arr) >= n, name
     _CACHE[key] = cases
@@ -615,7 +627,8 @@ def field_suite(C, run, n=50000, model_rows=2000):
         outs[name] = np.asarray(run(name, inp))
         assert outs[name].shape == (len(inp), OPS[name][1]), name
     # products: residue, shape, range, and the model's nine limbs
-    for name, fld, npairs in (("fq29_mul", F, 1), ("fq29_sqr", F, 0), ("fq29_mul2", F, 2), ("fr29_mul", Fr, 1)):
+    for name, fld, npairs in (("fq29_mul", F, 1), ("fq29_sqr", F, 0), ("fq29_mul2", F, 2), ("fr29_mul", Fr, 1),
+                              ("fr29_mul2", Fr, 2)):
         inp = cases[name]
         if npairs == 0:
             v = vals(inp)
@@ -656,6 +669,10 @@ def field_suite(C, run, n=50000, model_rows=2000):
     checked["fq29_pack256"] = _eq(outs["fq29_pack256"], exp, C.name + " fq29_pack256")
     exp = np.array([spell(x) for x in w], dtype=np.int32)
     checked["fq29_unpack256"] = _eq(outs["fq29_unpack256"], exp, C.name + " fq29_unpack256")
+    w = np.array([int_of_words(r) * (Fr.R * Fr.R % Fr.q) for r in cases["fr29_from_canonical"].tolist()], dtype=object)
+    checked["fr29_from_canonical"] = check_product(Fr, outs["fr29_from_canonical"], w, C.name + " fr29_from_canonical")
+    exp = np.array([words_i32(v * Fr.rinv % Fr.q) for v in vals(cases["fr29_to_canonical"])], dtype=np.int32)
+    checked["fr29_to_canonical"] = _eq(outs["fr29_to_canonical"], exp, C.name + " fr29_to_canonical")
     # x^5 through three products, limb for limb
     exp = []
     for r in cases["fr29_pow5"].tolist():

@@ -106,6 +106,19 @@ SNARKV_HD void op_fq29_unpack256(const int32_t* in, int32_t* out) {
   stq(fq29_unpack256(w), out);
 }
 SNARKV_HD void op_fr29_mul(const int32_t* in, int32_t* out) { str(fr29_mul(ldr(in), ldr(in + 9)), out); }
+SNARKV_HD void op_fr29_mul2(const int32_t* in, int32_t* out) {
+  str(fr29_mul2(ldr(in), ldr(in + 9), ldr(in + 18), ldr(in + 27)), out);
+}
+SNARKV_HD void op_fr29_from_canonical(const int32_t* in, int32_t* out) {
+  uint32_t w[8];
+  ldw(in, w);
+  str(fr29_from_canonical(w), out);
+}
+SNARKV_HD void op_fr29_to_canonical(const int32_t* in, int32_t* out) {
+  uint32_t w[8];
+  fr29_to_canonical(ldr(in), w);
+  stw(w, out);
+}
 SNARKV_HD void op_fr29_pow5(const int32_t* in, int32_t* out) { str(fr29_pow5(ldr(in)), out); }
 SNARKV_HD void op_fr29_canon_residue(const int32_t* in, int32_t* out) { str(fr29_canon_residue(ldr(in)), out); }
 // the 8 x 32 Montgomery product of fq.h (R = 2^256; device body fq_mul_asm.inc); fq_sqr is fq_mul(a, a)
@@ -265,6 +278,9 @@ SNARKV_HD void op_wt_fq2inv(const int32_t* in, int32_t* out) {
   X(fq29_pack256, 9, 8)                  \
   X(fq29_unpack256, 8, 9)                \
   X(fr29_mul, 18, 9)                     \
+  X(fr29_mul2, 36, 9)                    \
+  X(fr29_from_canonical, 8, 9)           \
+  X(fr29_to_canonical, 9, 8)             \
   X(fr29_pow5, 9, 9)                     \
   X(fr29_canon_residue, 9, 9)            \
   X(fq_mul, 16, 8)                       \
