@@ -44,6 +44,7 @@ from . import ipa_fold  # noqa: F401,E402  (decide_all as one folded check: incl
 from . import ipa_create  # noqa: F401,E402  (Ipa::create_proof in one call, Blake2b transcript on the device: include/snarkv_ipa_create.h)
 from . import poly  # noqa: F401,E402  (resident polynomials: linear combination, evaluation, division: include/snarkv_poly.h)
 from . import ntt  # noqa: F401,E402  (forward, inverse and coset transforms of resident polynomials: include/snarkv_ntt.h)
+from . import g1_ntt  # noqa: F401,E402  (the transform over group elements, a key's Lagrange basis: include/snarkv_g1_ntt.h)
 from . import poly_prod  # noqa: F401,E402  (column products: batch inversion, grand product, permutation Z: include/snarkv_poly_prod.h)
 from . import quotient  # noqa: F401,E402  (the quotient on the extended coset: extension, gate program, vanishing division: include/snarkv_quotient.h)
 from . import lookup  # noqa: F401,E402  (the lookup argument: sort, permuted columns, product Z: include/snarkv_lookup.h)
@@ -52,6 +53,7 @@ from . import poly_batch  # noqa: F401,E402  (many evaluations of resident polyn
 from . import kzg_multiopen  # noqa: F401,E402  (the Gwc19 and Bdfg21 multi-open provers, BN254: include/snarkv_kzg_multiopen.h)
 from . import host_kzg_open  # noqa: F401,E402  (the same through the host mirror and its transcripts: include/snarkv_host_kzg_open.h)
 from . import host_plonk_prove  # noqa: F401,E402  (the PLONK prover session of the host mirror: include/snarkv_host_plonk_prove.h)
+from . import host_plonk_prove_pallas_ci  # noqa: F401,E402  (... with committed instances: include/snarkv_host_pallas_plonk_prove_ci.h)
 from . import host_plonk_prove_pallas  # noqa: F401,E402  (... on pallas over IPA: include/snarkv_host_pallas_plonk_prove.h)
 
 __all__ = [
@@ -64,6 +66,7 @@ __all__ = [
     "ipa_create",
     "poly",
     "ntt",
+    "g1_ntt",
     "poly_prod",
     "quotient",
     "lookup",
@@ -73,6 +76,7 @@ __all__ = [
     "host_kzg_open",
     "host_plonk_prove",
     "host_plonk_prove_pallas",
+    "host_plonk_prove_pallas_ci",
     "IpaProver",
     "Context",
     "DecidingKey",

@@ -15,7 +15,7 @@ BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libsnarkv_amd.so")
 UNITS = ["ctx", "msm_api", "capi", "msm_naive", "msm_pippenger", "decider", "sample", "poseidon", "ipa", "ipa_prover", "mgpu",
          "decompress", "msm_shared", "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen", "ntt",
-         "poly_prod", "quotient", "lookup", "poly_batch", "kzg_multiopen", "plonk_prove"]
+         "poly_prod", "quotient", "lookup", "poly_batch", "kzg_multiopen", "plonk_prove", "g1_ntt"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
@@ -24,7 +24,7 @@ FLAGS += os.environ.get("SNARKV_EXTRA_FLAGS", "").split()
 # the public headers the device units include (include/; the host mirror's are in _host_stale)
 DEVICE_HEADERS = ("amd", "pallas", "pallas_decompress", "ipa_prover", "ipa_batch", "ipa_fold", "ipa_create", "poly", "ipa_multiopen",
                   "ntt", "poly_prod", "quotient", "quotient_cosets", "lookup", "poly_batch", "kzg_multiopen", "plonk_prove",
-                  "ipa_commit_blinded", "pallas_session")
+                  "ipa_commit_blinded", "pallas_session", "g1_ntt")
 
 
 def _deps():
@@ -79,7 +79,7 @@ def _link(lib, res, extra):
 # The pasta build of the curve-generic units (csrc/pallas.hip explains the flags, csrc/ctx.hpp the policy they select).
 PALLAS_UNITS = ["ctx", "msm_api", "pallas", "msm_pippenger", "msm_naive", "ipa", "ipa_prover", "decompress_pallas", "msm_shared",
                 "ipa_fold", "ipa_opening", "ipa_create", "poly", "ipa_multiopen", "ntt", "poly_prod", "quotient", "lookup",
-                "poly_batch", "session"]
+                "poly_batch", "session", "g1_ntt"]
 PALLAS_FLAGS = ["-DSNARKV_CURVE_PALLAS", "-Dsnarkv=snarkv_pallas"]
 PALLAS_LIB = os.path.join(HERE, "libsnarkv_pallas.so")
 
@@ -108,8 +108,10 @@ def devtest_sources():
 #   quotient_cosets  the join of the coset-at-a-time quotient, tile by tile (csrc/quotient.h)
 #   blind      the blind term of a blinded commitment, lane by lane and level by level (csrc/msm_blind.h)
 #   curve_fm   the friendly-multiple products of csrc/fq29.h and the fast adders of csrc/g1_29.h on them, raw limbs
+#   g1_ntt     the pass body of the transform over group elements, lane by lane and pass by pass (csrc/g1_ntt.h)
 HOSTTEST_DIR = os.path.join(HERE, "..", "tests", "hosttest")
-HOSTTESTS = ("curve", "poly", "ntt", "poly_prod", "quotient", "lookup", "args", "kzg_open", "quotient_cosets", "blind", "curve_fm")
+HOSTTESTS = ("curve", "poly", "ntt", "poly_prod", "quotient", "lookup", "args", "kzg_open", "quotient_cosets", "blind", "curve_fm",
+             "g1_ntt")
 HOSTTEST_EXCEPTIONS = {"curve": ("libhosttest_%s.so", ("curve_ops.h",))}  # the others: libhosttest_<name>_<curve>.so, one source
 
 
@@ -163,6 +165,8 @@ HOST_PALLAS_FOLD_LIB = os.path.join(HERE, "libsnarkv_host_pallas_fold.so")
 HOST_PALLAS_PROVE_LIB = os.path.join(HERE, "libsnarkv_host_pallas_prove.so")
 # the PLONK prover session over IPA on top of it (host/capi_pallas_plonk_prove.cpp, include/snarkv_host_pallas_plonk_prove.h)
 HOST_PALLAS_PLONK_PROVE_LIB = os.path.join(HERE, "libsnarkv_host_pallas_plonk_prove.so")
+# ... and the same session with committed instances (host/capi_pallas_plonk_prove_ci.cpp, include/snarkv_host_pallas_plonk_prove_ci.h)
+HOST_PALLAS_PLONK_PROVE_CI_LIB = os.path.join(HERE, "libsnarkv_host_pallas_plonk_prove_ci.so")
 
 
 def _host_stale(out, dev_lib):
@@ -172,7 +176,7 @@ def _host_stale(out, dev_lib):
         "snarkv_host_pallas_prove.h", "snarkv_ipa_create.h", "snarkv_kzg_multiopen.h", "snarkv_host_kzg_open.h",
         "snarkv_host_plonk_prove.h", "snarkv_host_plonk_prove_opts.h", "snarkv_plonk_prove.h", "snarkv_quotient.h",
         "snarkv_quotient_cosets.h", "snarkv_ntt.h", "snarkv_poly.h", "snarkv_poly_batch.h", "snarkv_host_pallas_plonk_prove.h",
-        "snarkv_pallas_session.h", "snarkv_ipa_multiopen.h", "snarkv_ipa_commit_blinded.h")]
+        "snarkv_pallas_session.h", "snarkv_ipa_multiopen.h", "snarkv_ipa_commit_blinded.h", "snarkv_host_pallas_plonk_prove_ci.h")]
     newest = max([os.path.getmtime(f) for f in srcs] + [os.path.getmtime(dev_lib)])
     return not os.path.exists(out) or os.path.getmtime(out) < newest
 
@@ -216,6 +220,8 @@ def build_host_driver():
         _gxx(HOST_PALLAS_PROVE_LIB, "capi_pallas_prove.cpp", pasta, "snarkv_pallas", ["snarkv_host_pallas"])
     if os.path.exists(HOST_PALLAS_API_LIB) and _host_stale(HOST_PALLAS_PLONK_PROVE_LIB, HOST_PALLAS_API_LIB):
         _gxx(HOST_PALLAS_PLONK_PROVE_LIB, "capi_pallas_plonk_prove.cpp", pasta, "snarkv_pallas", ["snarkv_host_pallas"])
+    if os.path.exists(HOST_PALLAS_API_LIB) and _host_stale(HOST_PALLAS_PLONK_PROVE_CI_LIB, HOST_PALLAS_API_LIB):
+        _gxx(HOST_PALLAS_PLONK_PROVE_CI_LIB, "capi_pallas_plonk_prove_ci.cpp", pasta, "snarkv_pallas", ["snarkv_host_pallas"])
     return HOST_LIB
 
 
@@ -242,6 +248,11 @@ def build_host_api_pallas_prove():
 def build_host_api_pallas_plonk_prove():
     build_host_driver()
     return HOST_PALLAS_PLONK_PROVE_LIB
+
+
+def build_host_api_pallas_plonk_prove_ci():
+    build_host_driver()
+    return HOST_PALLAS_PLONK_PROVE_CI_LIB
 
 
 if __name__ == "__main__":

@@ -85,6 +85,7 @@ enum Slot {
   SLOT_LOOKUP,       // the lookup argument (lookup.hip): the sort's partition points, the flags and the totals of the count scans
   SLOT_POLY_BATCH,   // the batched evaluation (poly_batch.hip): a chunk's indices, and per query the roots and totals of the levels
   SLOT_BLIND_ROWS,   // the blind term of a blinded commitment (msm_shared.hip): the rows 2^(8 w) S of the last S, S, staging
+  SLOT_G1_NTT,       // the transform over group elements (g1_ntt.hip): the twiddles, two working buffers, the window tables
   SLOT_COUNT
 };
 

@@ -5,7 +5,14 @@
 #ifndef SNARKV_HOST_PALLAS
 #error "compile with -DSNARKV_HOST_PALLAS"
 #endif
+// capi_pallas_plonk_prove_ci.cpp includes this file under other names (PROVER_T, PROVER_FN) with PROVER_CI true: the same
+// session with plan_prover's committed-instances option on -> libsnarkv_host_pallas_plonk_prove_ci.so.
+#ifndef PROVER_T
 #include "../../include/snarkv_host_pallas_plonk_prove.h"
+#define PROVER_T snarkv_host_pallas_plonk_prover
+#define PROVER_FN(name) snarkv_host_pallas_plonk_prover_##name
+#define PROVER_CI false
+#endif
 
 #include <cstring>
 #include <memory>
@@ -18,7 +25,7 @@
 
 using namespace snarkv_host;
 
-struct snarkv_host_pallas_plonk_prover {
+struct PROVER_T {
   PlonkProver<Bgh19, Blake2bTranscript> s;
   size_t next_phase = 0;
   bool closed = false;  // finish has returned a verdict, or a call has failed past its argument checks: only destroy is left
@@ -63,15 +70,15 @@ int guarded(F&& f) {
 
 extern "C" {
 
-const char* snarkv_host_pallas_plonk_prover_last_error(void) { return g_last_error.c_str(); }
+const char* PROVER_FN(last_error)(void) { return g_last_error.c_str(); }
 
-int snarkv_host_pallas_plonk_prover_plan(const snarkv_host_pallas_protocol* protocol, uint32_t flags, uint32_t* e, size_t* n_cols,
+int PROVER_FN(plan)(const snarkv_host_pallas_protocol* protocol, uint32_t flags, uint32_t* e, size_t* n_cols,
                                          size_t* n_instr, size_t* n_consts, size_t* bytes) {
   if (!protocol) return arg_error("null argument");
   if (flags & ~kPlonkKnownFlags) return arg_error("unknown flag bit");
   return guarded([&] {
     try {
-      const ProverPlan plan = plan_prover(protocol->pr, snarkv_pallas_ntt_max_k());
+      const ProverPlan plan = plan_prover(protocol->pr, snarkv_pallas_ntt_max_k(), PROVER_CI);
       if (e) *e = plan.num.e;
       if (n_cols) *n_cols = plan.num.n_cols;
       if (n_instr) *n_instr = plan.num.prog.size();
@@ -84,10 +91,10 @@ int snarkv_host_pallas_plonk_prover_plan(const snarkv_host_pallas_protocol* prot
   });
 }
 
-int snarkv_host_pallas_plonk_prover_begin(const snarkv_host_pallas_protocol* protocol, uint32_t flags, snarkv_ctx* ctx,
+int PROVER_FN(begin)(const snarkv_host_pallas_protocol* protocol, uint32_t flags, snarkv_ctx* ctx,
                                           const snarkv_ipa_dk* dk, const uint8_t h64[64], const uint8_t s64[64],
                                           const void* d_preprocessed32, const uint8_t* pre_blinds32, const uint8_t* instances,
-                                          size_t instances_len, snarkv_host_pallas_plonk_prover** out) {
+                                          size_t instances_len, PROVER_T** out) {
   if (!out) return arg_error("null argument");
   *out = nullptr;
   if (!protocol || !ctx || !dk || !instances) return arg_error("null argument");
@@ -99,18 +106,18 @@ int snarkv_host_pallas_plonk_prover_begin(const snarkv_host_pallas_protocol* pro
   if (snarkv_pallas_ipa_dk_k(dk) != protocol->pr.domain.k) return arg_error("the key is not one of 2^k points with k the protocol's");
   return guarded([&] {
     const std::vector<std::vector<Fr>> inst = wire::parse_instances(instances, instances_len);
-    auto p = std::make_unique<snarkv_host_pallas_plonk_prover>();
+    auto p = std::make_unique<PROVER_T>();
     p->s.scheme.dk = dk;
     p->s.scheme.h = G1Affine::from_bytes(h64);
     p->s.scheme.s = G1Affine::from_bytes(s64);
-    const Error e = p->s.begin(protocol->pr, ctx, d_preprocessed32, inst, flags, pre_blinds32);
+    const Error e = p->s.begin(protocol->pr, ctx, d_preprocessed32, inst, flags, pre_blinds32, PROVER_CI);
     if (!e.ok()) return e.kind == Error::AssertionFailure ? SNARKV_HOST_ERR_OTHER : error_code(e);
     *out = p.release();
     return 1;
   });
 }
 
-int snarkv_host_pallas_plonk_prover_phase(snarkv_host_pallas_plonk_prover* p, const void* d_witness32, int form,
+int PROVER_FN(phase)(PROVER_T* p, const void* d_witness32, int form,
                                           const uint8_t* blinds32, uint8_t* challenges_out32, size_t cap, size_t* n_challenges) {
   if (!p || !n_challenges) return arg_error("null argument");
   *n_challenges = 0;
@@ -138,7 +145,7 @@ int snarkv_host_pallas_plonk_prover_phase(snarkv_host_pallas_plonk_prover* p, co
   return rc;
 }
 
-int snarkv_host_pallas_plonk_prover_finish(snarkv_host_pallas_plonk_prover* p, const uint8_t* chunk_blinds32,
+int PROVER_FN(finish)(PROVER_T* p, const uint8_t* chunk_blinds32,
                                            const uint8_t f_blind32[32], const void* d_pbar32, const uint8_t omega_bar32[32],
                                            uint8_t* proof_out, size_t proof_cap, size_t* proof_len, uint8_t* acc_out) {
   if (!p || !proof_len) return arg_error("null argument");
@@ -168,6 +175,6 @@ int snarkv_host_pallas_plonk_prover_finish(snarkv_host_pallas_plonk_prover* p, c
   });
 }
 
-void snarkv_host_pallas_plonk_prover_destroy(snarkv_host_pallas_plonk_prover* p) { delete p; }
+void PROVER_FN(destroy)(PROVER_T* p) { delete p; }
 
 }  // extern "C"

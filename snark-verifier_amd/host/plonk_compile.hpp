@@ -294,6 +294,7 @@ struct ProverPlan {
   size_t n_pre = 0, n_inst = 0, n_wit = 0, q_index = 0, num_chunk = 0, phases = 0;
   size_t k = 0, n = 0, N = 0;
   size_t device_bytes = 0;  // the columns, the quotient's work buffer and h
+  bool committed_instances = false;  // the option is on and the protocol has an instance_committing_key
   size_t cols_total() const { return num.first_poly + q_index + 1; }  // extra | protocol order | the quotient's slot
   // the quotient's work buffer in elements: every column on the extended coset, or on one coset of the domain at a time
   // (snarkv_quotient_cosets.h)
@@ -301,11 +302,21 @@ struct ProverPlan {
   size_t device_bytes_of(bool by_cosets) const { return device_bytes - 32 * (work_elems(false) - work_elems(by_cosets)); }
 };
 
-inline ProverPlan plan_prover(const PlonkProtocol& pr, uint32_t max_k = 28) {
+// `committed_instances`: a protocol with an instance_committing_key is taken -- its instance polynomials are committed by the
+// session and may be queried and evaluated like witness polynomials.  Off (the default), or without a key, nothing changes:
+// the key is refused, and so is any query or evaluation of an instance polynomial (the verifier computes those itself).
+inline ProverPlan plan_prover(const PlonkProtocol& pr, uint32_t max_k = 28, bool committed_instances = false) {
   if (pr.linearization != Linearization::None) throw InvalidProtocol("a linearization other than none is not supported by the prover");
-  if (pr.instance_committing_key) throw InvalidProtocol("an instance_committing_key (committed instances) is not supported by the prover");
+  if (pr.instance_committing_key && !committed_instances)
+    throw InvalidProtocol("an instance_committing_key (committed instances) is not supported by the prover");
   if (pr.quotient.chunk_degree != 1) throw InvalidProtocol("chunk_degree != 1 is not supported by the prover");
   ProverPlan p;
+  p.committed_instances = committed_instances && pr.instance_committing_key;
+  if (p.committed_instances)
+    for (size_t i = 0; i < pr.num_instance.size(); ++i)
+      if (pr.num_instance[i] > pr.instance_committing_key->bases.size())  // the verifier would silently truncate the column
+        throw InvalidProtocol("num_instance[" + std::to_string(i) + "] = " + std::to_string(pr.num_instance[i]) + " is above the " +
+                              std::to_string(pr.instance_committing_key->bases.size()) + " bases of the instance_committing_key");
   p.n_pre = pr.preprocessed.size();
   p.n_inst = pr.num_instance.size();
   p.n_wit = plonk_num_witness(pr);
@@ -317,7 +328,7 @@ inline ProverPlan plan_prover(const PlonkProtocol& pr, uint32_t max_k = 28) {
   for (auto& l : lists)
     for (auto& q : *l.second) {
       const std::string what = l.first;
-      if (q.poly >= p.n_pre && q.poly < p.n_pre + p.n_inst) throw InvalidProtocol(what + " of an instance polynomial is not supported by the prover");
+      if (!p.committed_instances && q.poly >= p.n_pre && q.poly < p.n_pre + p.n_inst) throw InvalidProtocol(what + " of an instance polynomial is not supported by the prover");
       // the quotient is opened at z and has no listed evaluation: the verifier computes it from the numerator
       if (q.poly > p.q_index || (q.poly == p.q_index && (l.second == &pr.evaluations || q.rotation != 0)))
         throw InvalidProtocol(what + " names polynomial " + std::to_string(q.poly) +

@@ -24,7 +24,7 @@
 //            batched call (sync 2) -> Q = sum (z^n)^i h_i into the quotient slot -> the verifier's own identity check on the
 //            host -> MOS::create_proof (Gwc19: one more synchronisation, Bdfg21: two, Bgh19: three).
 // Over IPA the session also keeps one blind per polynomial below the quotient (0 for the instance polynomials, which are never
-// committed or queried) and forms blind(Q) = sum (z^n)^i blind(h_i) on the host, next to Q.
+// committed or queried -- unless begin is told to take an instance_committing_key: see begin) and forms blind(Q) = sum (z^n)^i blind(h_i) on the host, next to Q.
 // The prover draws no randomness: blinding rows and the random polynomial are the caller's columns, and so are the blinds and
 // the randomness of the IPA opening.
 #pragma once
@@ -146,6 +146,7 @@ struct PlonkScheme {  // KZG: the key is the SRS, nothing is blinded
   size_t opening_length(size_t) const { return kPointBytes * (std::is_same<MOS, Gwc19>::value ? n_sets : 2); }
   void start(TR&) {}
   void note_blinds(size_t, size_t, const uint8_t*) {}
+  Error instance_key(const InstanceCommittingKey&, size_t, size_t) { return Error{Error::InvalidProtocol, "committed instances are not supported over KZG"}; }
   void commit(snarkv_ctx* ctx, const uint8_t* d_first, size_t n, size_t, size_t count, uint8_t* d_out64) {
     std::vector<const void*> d_s(count), d_p(count, d_srs);
     std::vector<size_t> ns(count, n);
@@ -187,6 +188,14 @@ struct PlonkScheme<Bgh19, Blake2bTranscript> {  // IPA: the resident key with h 
   void note_blinds(size_t first, size_t count, const uint8_t* b32) {
     for (size_t i = 0; i < count; ++i)
       if (!Fr::from_bytes(b32 + 32 * i, &blinds.at(first + i))) throw Panic("non-canonical blind");
+  }
+  // committed instances: the verifier adds `constant` to every column's MSM, so the polynomial's blind is 1 over a constant
+  // that is the key's s (anything else is no commitment of this key) and 0 without one
+  Error instance_key(const InstanceCommittingKey& ick, size_t first, size_t count) {
+    if (ick.constant && !(*ick.constant == s))
+      return Error{Error::InvalidProtocol, "the constant of the instance_committing_key is not the key's s"};
+    for (size_t i = 0; i < count; ++i) blinds.at(first + i) = ick.constant ? Fr::one() : Fr::zero();
+    return Error{};
   }
   // `first`: the session's index of the first polynomial, whose blinds note_blinds has (chunk i of h: q_index + 1 + i)
   void commit(snarkv_ctx* ctx, const uint8_t* d_first, size_t n, size_t first, size_t count, uint8_t* d_out64) {
@@ -248,14 +257,18 @@ struct PlonkProver : PlonkProverSession {
 
   // d_preprocessed: the n_pre polynomials as coefficients, n each, in the protocol's order.  `scheme` has its key already;
   // pre_blinds32: the blinds of the preprocessed polynomials' commitments (IPA; null over KZG)
+  // committed_instances: plan_prover's option.  With it and a key, the n_inst instance polynomials are committed in one
+  // batch (blind 1 over the key's constant, 0 without one), the points are downloaded -- ONE synchronisation, the only one of
+  // begin -- and the transcript absorbs them by common_ec_point where it otherwise absorbs the scalars (proof.rs:75-108); they
+  // are not proof bytes.  An identity among them is the transcript's refusal.
   Error begin(const PlonkProtocol& protocol, snarkv_ctx* c, const void* d_preprocessed, const std::vector<std::vector<Fr>>& inst,
-              uint32_t session_flags = 0, const uint8_t* pre_blinds32 = nullptr) {
+              uint32_t session_flags = 0, const uint8_t* pre_blinds32 = nullptr, bool committed_instances = false) {
     pr = protocol;
     flags = session_flags;
     ctx = c;
     instances = inst;
     try {
-      plan = plan_prover(pr, SNARKV_PLONK_DEV(ntt_max_k)());
+      plan = plan_prover(pr, SNARKV_PLONK_DEV(ntt_max_k)(), committed_instances);
     } catch (const InvalidProtocol& e) {
       return Error{Error::InvalidProtocol, e.what()};
     }
@@ -275,8 +288,13 @@ struct PlonkProver : PlonkProverSession {
     if (pr.queries.empty()) return Error{Error::InvalidProtocol, "the protocol has no queries"};
     scheme.prepare(pr, plan);
     if (pre_blinds32) scheme.note_blinds(0, plan.n_pre, pre_blinds32);
+    if (plan.committed_instances) {
+      Error e = scheme.instance_key(*pr.instance_committing_key, plan.n_pre, plan.n_inst);
+      if (!e.ok()) return e;
+    }
     // the layout
     size_t most = plan.num_chunk;
+    if (plan.committed_instances) most = std::max(most, plan.n_inst);  // the point block holds the instance commitments too
     for (size_t ph = 0; ph < plan.phases; ++ph) most = std::max(most, pr.num_witness[ph]);
     off_polys = 32 * n * plan.num.first_poly;
     off_h = 32 * n * plan.cols_total();
@@ -313,6 +331,17 @@ struct PlonkProver : PlonkProverSession {
     if (pr.transcript_initial_state) {
       Error e = t.common_scalar(*pr.transcript_initial_state);
       if (!e.ok()) return e;
+    }
+    if (plan.committed_instances) {
+      if (plan.n_inst == 0) return Error{};
+      scheme.commit(ctx, poly(plan.n_pre), n, plan.n_pre, plan.n_inst, commits());
+      std::vector<uint8_t> out(64 * plan.n_inst);
+      dev(Scheme::download(ctx, out.data(), commits(), out.size()), "session_download");
+      for (size_t i = 0; i < plan.n_inst; ++i) {
+        Error e = t.common_ec_point(G1Affine::from_bytes(&out[64 * i]));
+        if (!e.ok()) return e;
+      }
+      return Error{};
     }
     for (auto& column : inst)
       for (auto& x : column) {

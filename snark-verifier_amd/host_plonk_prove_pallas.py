@@ -96,11 +96,18 @@ class PlonkProver:
     key's two other points, 64 bytes each.  `instances`: [[int]] or a packed block.  The key and whatever a phase is given stay
     the caller's; the session keeps its own copy of every polynomial."""
 
+    _api = staticmethod(api)  # the library of the session's six calls (host_plonk_prove_pallas_ci binds another)
+
+    def _check(self, rc):
+        if rc < 0:
+            raise H.HostError(rc, self._a.last_error())
+        return rc
+
     def __init__(self, protocol, ctx, dk, h, s, d_preprocessed, pre_blinds, instances, flags=0):
-        self._a, self._h = api(), None
+        self._a, self._h = self._api(), None
         inst = bytes(instances) if isinstance(instances, (bytes, bytearray)) else pack_instances(instances)
         hd = _vp()
-        _check(self._a.begin(protocol._h, flags, ctx._h, dk._h, None if h is None else bytes(h), None if s is None else bytes(s),
+        self._check(self._a.begin(protocol._h, flags, ctx._h, dk._h, None if h is None else bytes(h), None if s is None else bytes(s),
                              _addr(d_preprocessed), _blinds(pre_blinds), inst, len(inst), ctypes.byref(hd)))
         self._h, self._keep, self.k = hd, (protocol, ctx, dk), dk.k
 
@@ -109,7 +116,7 @@ class PlonkProver:
         them, as ints"""
         n = _sz(0)
         out = ctypes.create_string_buffer(32 * 64)
-        _check(self._a.phase(self._h, _addr(d_witness), form, _blinds(blinds), out, 64, ctypes.byref(n)))
+        self._check(self._a.phase(self._h, _addr(d_witness), form, _blinds(blinds), out, 64, ctypes.byref(n)))
         return [int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(n.value)]
 
     def finish(self, chunk_blinds, f_blind, d_pbar, omega_bar):
@@ -118,10 +125,10 @@ class PlonkProver:
         n = _sz(0)
         rc = self._a.finish(self._h, None, None, None, None, None, 0, ctypes.byref(n), None)
         if rc != H.ERR_CAPACITY:
-            _check(rc)
+            self._check(rc)
             raise H.HostError(H.ERR_OTHER, "finish: a proof of no bytes")
         out, acc = ctypes.create_string_buffer(n.value), ctypes.create_string_buffer(32 * self.k + 64)
-        rc = _check(self._a.finish(self._h, _blinds(chunk_blinds), _fe(f_blind), _addr(d_pbar), _fe(omega_bar), out, len(out),
+        rc = self._check(self._a.finish(self._h, _blinds(chunk_blinds), _fe(f_blind), _addr(d_pbar), _fe(omega_bar), out, len(out),
                                    ctypes.byref(n), acc))
         return (out.raw[:n.value], acc.raw) if rc == 1 else (None, None)
 

@@ -60,7 +60,9 @@ def main():
     import plonk_prover_pallas_util as PP
     import plonk_synth as S
     from snark_verifier_amd import host_api_pallas as HA
+    from snark_verifier_amd import g1_ntt
     from snark_verifier_amd import host_plonk_prove_pallas as HP
+    from snark_verifier_amd import host_plonk_prove_pallas_ci as HC
     from snark_verifier_amd import ipa_commit_blinded, ipa_multiopen, ntt, poly, poly_batch, poly_prod
     from snark_verifier_amd import pallas as PL
 
@@ -131,32 +133,52 @@ def main():
         torch.cuda.synchronize()
         ntt.intt_dev(ctx, d_pre, d_pre, k, 8)
         ctx.sync()
-        dk = ctx.ipa_dk_create(key_points(PA, n))
+        g_raw = key_points(PA, n)
+        dk = ctx.ipa_dk_create(g_raw)
         with PP.on_pallas():
             pr = PP.CircuitB(4).protocol  # the constraints; the domain and the commitments are this size's
             pr = dict(pr, domain=PP.P.Domain(k), preprocessed=[PA.G1_GEN] * 8)
             protocol = HA.Protocol(S.pack_protocol(pr))
             shifts = [pr["domain"].rotate_scalar(1, rot) for _, rot in pr["queries"]]
             n_sets = len(PP.K.bdfg21_query_sets([(p, sh, 0) for (p, _), sh in zip(pr["queries"], shifts)]))
+            # the same protocol as halo2 states it over IPA: the instance column committed over the first points of the key's
+            # Lagrange basis (made on the device from the resident key), constant s, and its polynomial queried at z
+            d_lag = torch.empty(64 * n, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            g1_ntt.dk_lagrange_dev(ctx, dk, d_lag)
+            ctx.sync()
+            lag = d_lag[:128].cpu().numpy().tobytes()
+            del d_lag
+            ick = {"bases": [PA.g1_from_bytes(lag[:64]), PA.g1_from_bytes(lag[64:])], "constant": PA.g1_from_bytes(s_pt)}
+            pr_ci = dict(pr, instance_committing_key=ick, evaluations=pr["evaluations"] + [(8, 0)], queries=pr["queries"] + [(8, 0)])
+            protocol_ci = HA.Protocol(S.pack_protocol(pr_ci))
         plan = HP.plan(protocol)
         pre_blinds, w_blinds, z_blinds, chunk_blinds = [1] * 8, [101, 102, 103], [104, 105, 106], [107, 108, 109]
         f_blind, omega_bar = 110, 111
 
-        def session(make_z):
-            with HP.PlonkProver(protocol, ctx, dk, h_pt, s_pt, d_pre, pre_blinds, inst) as p:
+        def session(make_z, committed=False):
+            # the challenges differ between the two transcripts, and with them the Z columns: each flavour has its own
+            mod, prot, w2 = (HC, protocol_ci, d_w2_ci) if committed else (HP, protocol, d_w2)
+            with mod.PlonkProver(prot, ctx, dk, h_pt, s_pt, d_pre, pre_blinds, inst) as p:
                 ch = p.phase(V[:col * 3], w_blinds, HP.FORM_VALUES)
                 ch += p.phase(None)
                 if make_z:
-                    poly_prod.perm_product_dev(ctx, V, n, COLS, [0, 1], [15, 16], [8, 9], ch[1], ch[2], d_work, d_w2.data_ptr())
-                    poly_prod.perm_product_dev(ctx, V, n, COLS, [2], [17], [10], ch[1], ch[2], d_work, d_w2.data_ptr() + col,
-                                               d_start=d_w2.data_ptr() + 32 * u)
+                    poly_prod.perm_product_dev(ctx, V, n, COLS, [0, 1], [15, 16], [8, 9], ch[1], ch[2], d_work, w2.data_ptr())
+                    poly_prod.perm_product_dev(ctx, V, n, COLS, [2], [17], [10], ch[1], ch[2], d_work, w2.data_ptr() + col,
+                                               d_start=w2.data_ptr() + 32 * u)
                     ctx.sync()
-                p.phase(d_w2, z_blinds, HP.FORM_VALUES)
+                p.phase(w2, z_blinds, HP.FORM_VALUES)
                 proof, _ = p.finish(chunk_blinds, f_blind, d_pbar, omega_bar)
             assert proof, "the bench witness does not satisfy circuit B"
             return proof
 
         proof = session(True)
+        d_w2_ci = d_w2.clone()
+        torch.cuda.synchronize()
+        proof_ci = session(True, committed=True)
+        # (no verifier here: the bench protocol's `preprocessed` are placeholders, as for the plain session; acceptance of
+        # such proofs is tests/test_gpu_plonk_prove_pallas_ci.py's)
+        assert proof_ci != proof and len(proof_ci) == len(proof) + 32
         # the floor's inputs: sixteen polynomials as coefficients (8 preprocessed, the instance's, 6 witness, and one more in the
         # quotient's place), the protocol's queries with their true evaluations at x * shift
         D = torch.zeros(col * 16, dtype=torch.uint8, device="cuda")
@@ -187,20 +209,27 @@ def main():
             return ipa_multiopen.create_proof_dev(ctx, dk, h_pt, s_pt, D.data_ptr(), 16, blinds16, x, queries, f_blind, d_pbar.data_ptr(), omega_bar)
 
         opened = floor()
-        ts, tf = [], []
+        ts, tf, tc = [], [], []
         for it in range(WARMUPS + RUNS):
             t0 = time.perf_counter()
             again = session(False)
             t1 = time.perf_counter()
             again_opened = floor()
             t2 = time.perf_counter()
-            assert again == proof and again_opened == opened
+            again_ci = session(False, committed=True)
+            t3 = time.perf_counter()
+            assert again == proof and again_opened == opened and again_ci == proof_ci
             if it >= WARMUPS:
                 ts.append(1e3 * (t1 - t0))
                 tf.append(1e3 * (t2 - t1))
+                tc.append(1e3 * (t3 - t2))
         ms, mf = statistics.median(ts), statistics.median(tf)
         lines.append("  %2d  %7d  %4d  %9.3f [%9.3f .. %9.3f]  %9.3f [%9.3f .. %9.3f]  %7.2f  %10.1f"
                      % (k, 9, n_sets, ms, min(ts), max(ts), mf, min(tf), max(tf), ms / mf, plan["bytes"] / 2 ** 20))
+        print(lines[-1], flush=True)
+        mc = statistics.median(tc)
+        lines.append("# %2d  the session with committed instances (host_plonk_prove_pallas_ci: one more commitment and a synchronisation in"
+                     " begin, 21 queries)  %9.3f [%9.3f .. %9.3f]  /session %5.2f" % (k, mc, min(tc), max(tc), mc / ms))
         print(lines[-1], flush=True)
         dk.close()
         del V, D, d_pre, d_w2, d_work, d_pbar
